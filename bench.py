@@ -2,6 +2,7 @@
 """bench.py -- predicted frames / s of the iVideoGPT prediction hot path on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    (+ the last timed step's frames / metric rows as DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the hot path over one batch of synthetic clips already resident in HBM:
@@ -34,11 +35,9 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only on this driver: RCCL needs it (multi-process runs)
-# HIP deals its streams round-robin over GPU_MAX_HW_QUEUES hardware queues (default 4): the null stream, this benchmark's main stream,
-# the lane streams, the gatherer's stream and RCCL's own must not share one -- two lanes on one hardware queue run one after the other
-# (4,987 instead of 5,355 frames/s at four lanes with 4 queues; with a process group 5,069 at 8 queues, 5,617 at 16:
-# profiles/r04_lanes.txt).  Has to be in the environment before the runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# HIP deals its streams round-robin over the process's hardware queues (GPU_MAX_HW_QUEUES): lanes whose streams share a queue run one
+# after the other (profiles/r04_lanes.txt).  The benchmark takes the queue count from the environment: on a GPU shared with other
+# processes every process's queues take slots of the card's fixed set, so it is not raised here.
 
 import torch  # noqa: E402
 
@@ -50,12 +49,12 @@ from ivideogpt_amd import CompressiveVQModel, LlamaForCausalLM, weights as W  # 
 from ivideogpt_amd import _lib, parallel  # noqa: E402
 from ivideogpt_amd.pipeline import frame_metrics, predict_frames  # noqa: E402
 
-PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak of the MI355X
 # What a PURE stream of v_mfma_f32_16x16x32_bf16 sustains on this part with random operands: the socket reaches its 1,400 W limit and
 # the shader clock falls to ~2.0 GHz (tools/ubench/mfma_power.hip, profiles/r05_mfma_power.txt: 1,946-1,999 TFLOP/s; 2,397-2,417 on
 # all-zero operands).  Printed beside `frac` as `frac_of_sustained`; `frac` keeps the nominal peak as its denominator.
 SUSTAINED_BF16_TFLOPS = 1950.0
-PEAK_F32_TFLOPS = 157.3     # f32-input MFMA peak (same guide)
+PEAK_F32_TFLOPS = 157.3     # f32-input MFMA peak
 PEAK_HBM_GBS = 8000.0
 
 
@@ -455,6 +454,37 @@ def in_flight_pass(lanes, ctx, F, greedy, with_actions):
                         "traffic would be the one-lane figure by construction"}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, written as <out_dir>/<name>.npy (float32;
+    float64 stays float64), at most DUMP_BUDGET_BYTES in all.  Arrays of up to 1 MiB are written whole; over the budget, the larger ones
+    are cut to the same fraction of their elements: a fixed sample (numpy default_rng(DUMP_SAMPLE_SEED), flattened indices in ascending
+    order), so that two builds given the same arguments write comparable files.
+    -> {name: {"shape", "dtype", "elements" written, "sampled"}} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy() for k, v in arrays.items()}
+    small = {k for k, x in host.items() if x.nbytes <= 2**20}
+    room = DUMP_BUDGET_BYTES - 4096 * len(host) - sum(host[k].nbytes for k in small)    # (4096: an .npy header, generously)
+    big = sum(x.nbytes for k, x in host.items() if k not in small)
+    frac = min(1.0, max(0.0, room) / big) if big else 1.0
+    info = {}
+    for name, x in host.items():
+        full_shape = list(x.shape)
+        flat = x.reshape(-1)
+        sampled = frac < 1.0 and name not in small
+        if sampled:
+            k = int(flat.size * frac)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, size=k, replace=False))
+            x = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        info[name] = {"shape": full_shape, "dtype": str(x.dtype), "elements": int(x.size), "sampled": sampled}
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -492,9 +522,14 @@ def main():
     ap.add_argument("--gather-mode", default="thread", choices=["thread", "lanes"],
                     help="several lanes + a process group: the per-step metric all-gather is issued by one thread on its own stream in step "
                          "order (parallel.OrderedGatherer; default) or by the lanes themselves in ticket order (parallel.Turnstile; A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (frames.npy: the predicted clips, metrics.npy: the "
+                         "gathered (mse, psnr, ssim) rows) under DIR, rank 0 only; over 64 MB a fixed seeded sample of the elements")
     ap.add_argument("--cu-split", type=int, default=0, help="experiment: CUs (of 256) given to the convolution phases of all lanes; the rollouts "
                                                              "run on the others (CU-masked streams); 0: off")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     default_run = not a.config and not (a.medium or a.action_dim or a.res != 64 or a.frames != 16 or a.ctx or a.batch != 64)
     if a.config:
         for k, v in CONFIGS[a.config].items():
@@ -534,7 +569,7 @@ def main():
 
     kw = {"action": actions} if a.action_dim else {}
     # Every pass of this benchmark runs on an explicit stream of its own: the engines then launch on the caller's stream and never
-    # create their dedicated one.  Streams are dealt round-robin over the (4) hardware queues in creation order -- a stream nobody
+    # create their dedicated one.  Streams are dealt round-robin over the hardware queues in creation order -- a stream nobody
     # uses still takes a slot, and two lanes whose streams share a hardware queue run one after the other.
     main_stream = torch.cuda.Stream(device=dev)
     lane_streams = [main_stream] + [torch.cuda.Stream(device=dev) for _ in range(max(0, a.lanes - 1))]   # all of them NOW, next to each other
@@ -576,6 +611,9 @@ def main():
               "note": "one batch in flight (lane 0 alone): the latency of a batch through encode -> rollout -> decode"}
     steps_timed = n1
     in_flight = None
+    dumped = None
+    if a.dump_outputs and a.lanes <= 1 and rank == 0:     # this loop is the headline: its last step
+        dumped = dump_outputs(a.dump_outputs, {"frames": frames, "metrics": rows})
 
     # ---- the headline: `lanes` batches in flight per GPU, clean loop, no hooks
     if a.lanes > 1:
@@ -606,6 +644,9 @@ def main():
                                                            gatherer if a.gather_mode == "thread" else None)
         for fr, rw in zip(lane_frames, lane_rows):
             assert torch.isfinite(fr).all() and rw.shape == (global_b, 3) and torch.isfinite(rw).all()
+        if a.dump_outputs and rank == 0:    # the last timed step (global index steps - 1) ran on lane (steps - 1) % lanes
+            last_lane = (a.steps - 1) % a.lanes
+            dumped = dump_outputs(a.dump_outputs, {"frames": lane_frames[last_lane], "metrics": lane_rows[last_lane]})
         steps_timed = a.steps
         if not a.no_profile:
             in_flight = in_flight_pass(lanes, ctx, F, a.greedy, actions is not None)
@@ -862,6 +903,8 @@ def main():
         }
         if in_flight:
             out["roofline_in_flight"] = in_flight
+        if dumped:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped, "sample_seed": DUMP_SAMPLE_SEED}
         if single:
             out["single_lane"] = single
         out.update(alt)

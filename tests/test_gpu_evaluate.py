@@ -218,6 +218,29 @@ def test_bench_two_lanes_small_run():
     assert abs(d["value"] - 4 * 4 * 4 / (d["ms_per_step"] * 4e-3)) < 1e-6 * d["value"]      # frames of exactly 4 steps over the wall clock
 
 
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """``bench.py --dump-outputs DIR``: the last timed step's clips (B, T, 3, H, W) and gathered metric rows (B, 3) as float32 .npy;
+    two runs with the same arguments write identical files, and the line counts exactly --steps timed steps."""
+    import json
+    import numpy as np
+    got = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lanes", "2", "--batch", "4", "--frames", "6", "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--no-fp32-mode", "--no-profile", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and abs(d["value"] - 4 * 4 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        arrays = d["dump_outputs"]["arrays"]
+        assert arrays["frames"]["shape"] == [4, 6, 3, 64, 64] and arrays["metrics"]["shape"] == [4, 3]
+        assert not arrays["frames"]["sampled"] and not arrays["metrics"]["sampled"]
+        got.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("frames", "metrics")})
+    for k in ("frames", "metrics"):
+        assert got[0][k].dtype == np.float32 and np.isfinite(got[0][k]).all()
+        assert np.array_equal(got[0][k], got[1][k]), k
+    assert got[0]["frames"].min() >= 0 and got[0]["frames"].max() <= 1
+
+
 def test_engine_runs_on_the_callers_stream_and_orders_a_switch_of_streams():
     """engine.Engine._On: under a stream the caller made current the launches go to THAT stream; a call on another stream than the
     previous call's waits for it (the engine's workspace belongs to one stream at a time).  Same ids on every route."""

@@ -259,6 +259,29 @@ def test_bench_launch_line_and_config_presets():
     assert c[5]["medium"] and c[5]["batch"] * 8 == 512 and 257 * 2 - 1 + 17 * (c[5]["frames"] - 2) + 1 == 990   # 989-token sequences
 
 
+def test_bench_dump_outputs_keeps_the_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: arrays under the budget are written whole and exact (float32; float64 stays float64); over 64 MB the
+    large ones are cut to a fixed seeded sample of their elements -- the same files from run to run, the small arrays still whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    frames, rows = torch.rand(4, 6, 3, 64, 64).to(torch.bfloat16), torch.rand(4, 3, dtype=torch.float64)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"frames": frames, "metrics": rows})
+    assert not info["frames"]["sampled"] and not info["metrics"]["sampled"]
+    got = np.load(tmp_path / "a" / "frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frames.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "metrics.npy"), rows.numpy())
+    big = torch.rand(16, 16, 3, 256, 256)                      # BASELINE config 4's clips: 201 MB in float32
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), {"frames": big, "metrics": rows})
+    assert info["frames"]["sampled"] and info["frames"]["shape"] == [16, 16, 3, 256, 256] and not info["metrics"]["sampled"]
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= bench.DUMP_BUDGET_BYTES
+    b, c = np.load(tmp_path / "b" / "frames.npy"), np.load(tmp_path / "c" / "frames.npy")
+    assert b.dtype == np.float32 and b.size == info["frames"]["elements"] > 0.99 * (bench.DUMP_BUDGET_BYTES - 8192) / 4
+    assert np.array_equal(b, c) and np.isin(b[:1000], big.numpy()).all()
+
+
 def test_lds_swizzle_keys_are_conflict_free_for_their_access_shapes():
     """csrc/conv3x3.hip reads its LDS tiles with ds_read_b128 under two XOR keys; tools/lds_swizzle_check.py restates the bank
     model of the microarchitecture guide.  The plain key serves 16 consecutive rows from any start row, the upsampling key both
