@@ -342,6 +342,13 @@ int ivg_op_conv_in(const void* video, int video_dtype, const float* w, const flo
  * every trajectory b its own rows [P, pos) in cache row b; out (B, heads * hd).  With G = 1 and P = 0: the plain step. */
 int ivg_op_shared_decode_attn(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int hd, int Lmax,
                               int pos, int P, int G, int row0, int dtype, ivg_stream stream);
+/* One prefill layer's attention over a prompt at positions [0, L) (1 <= L <= Lmax; hd even; dtype IVG_F32 or IVG_BF16): qkv [B * L][3 * heads * hd]
+ * gets RoPE applied to q in place; the roped k and the v of row (b, l) are written to row l of kc / vc [B][heads][Lmax][hd] (rows >= L are
+ * not touched); vt [B][heads][hd][Lp], Lp = rup(L, 64), receives V^T with columns [L, Lp) zeroed (NULL: skipped).  With out != NULL
+ * (needs vt, qkv 16-byte and out 8-byte aligned), out [B * L][heads * hd] = softmax(q k^T / sqrt(hd), causal) v by the one-pass kernel,
+ * which covers bf16 and hd = 64 only: IVG_ERR_INVALID otherwise.  cos_t / sin_t: [Lmax][hd / 2] fp32 as the engine holds them. */
+int ivg_op_prefill_attn(void* qkv, void* kc, void* vc, void* vt, void* out, const float* cos_t, const float* sin_t, int B, int L, int heads, int hd,
+                        int Lmax, int dtype, ivg_stream stream);
 /* one top-k draw per logits row [B][V] fp32 with the rollout's sampler (uniforms [B] in [0,1), or NULL = greedy): HF
  * TemperatureLogitsWarper (logits / temperature, > 0) + TopKLogitsWarper + softmax + draw as restated by oracle/llama.py
  * sample_from_logits */

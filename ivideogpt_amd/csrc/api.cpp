@@ -927,6 +927,20 @@ int ivg_op_shared_decode_attn(const void* qkv, void* kc, void* vc, void* out, co
   return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
 }
 
+int ivg_op_prefill_attn(void* qkv, void* kc, void* vc, void* vt, void* out, const float* cos_t, const float* sin_t, int B, int L, int heads,
+                        int hd, int Lmax, int dtype, ivg_stream stream) {
+  // unit-test hook of one prefill layer's attention: rope_kv (q in place, K / V appended at positions [0, L), V^T with pitch
+  // rup(L, 64)) then, with out, flash_prefill_kernel -- what Run::prefill launches per layer
+  if (B <= 0 || heads <= 0 || L < 1 || L > Lmax || hd <= 0 || hd % 2 || (dtype != IVG_F32 && dtype != IVG_BF16)) return IVG_ERR_INVALID;
+  // the one-pass kernel covers bf16 at head_dim 64 and loads / stores in 16- / 8-byte vectors: refused before anything is written
+  if (out && (dtype != IVG_BF16 || hd != 64 || !vt || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 7))) return IVG_ERR_INVALID;
+  const int Lp = (L + 63) / 64 * 64;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_rope_kv(qkv, kc, vc, vt, Lp, cos_t, sin_t, B, L, heads, hd, Lmax, nullptr, 0, (DType)dtype, st);
+  if (rc == 0 && out) rc = launch_flash_prefill(qkv, kc, vt, out, B, L, Lp, heads, hd, Lmax, (DType)dtype, st);
+  return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
+}
+
 int ivg_op_kv24_pack(const float* k32, const float* v32, void* kc, void* vc, int BH, int L, int Lmax, ivg_stream stream) {
   if (BH <= 0 || L < 0 || L > Lmax) return IVG_ERR_INVALID;
   return launch_kv24_pack(k32, v32, kc, vc, BH, L, Lmax, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;

@@ -170,9 +170,11 @@ int launch_rope_kv(void* qkv, void* kc, void* vc, void* vt, int ldvt, const floa
                    int heads, int hd, int Lmax, const StepState* state, int pos0, DType dt, hipStream_t st) {
   const long total = (long)B * L * heads * (hd / 2);
   if (total <= 0) return 0;
+  // A prompt append (no state) leaves V^T columns [L, ldvt) zero on every path: the one-pass attention and the P.V GEMM multiply
+  // them by P = 0, and 0 * NaN would poison the row.  (The scalar kernel does not own those columns: a memset covers them.)
   const int rows = dt == BF16 ? 64 : 32;
   if (hd == 64 && !state && (!vt || (ldvt % rows == 0 && ldvt >= cdiv(L, rows) * rows)) && ((uintptr_t)qkv & 15) == 0) {
-    dim3 g2((unsigned)cdiv(L, rows), (unsigned)(B * heads));
+    dim3 g2((unsigned)(vt ? ldvt / rows : cdiv(L, rows)), (unsigned)(B * heads));   // workgroups past L only zero their V^T columns
     if (dt == BF16)
       hipLaunchKernelGGL(rope_kv64_kernel<bf16_t>, g2, dim3(256), 0, st, (bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, (bf16_t*)vt, ldvt, cosT, sinT,
                          L, heads, Lmax, pos0);
@@ -180,6 +182,11 @@ int launch_rope_kv(void* qkv, void* kc, void* vc, void* vt, int ldvt, const floa
       hipLaunchKernelGGL(rope_kv64_kernel<float>, g2, dim3(256), 0, st, (float*)qkv, (float*)kc, (float*)vc, (float*)vt, ldvt, cosT, sinT, L,
                          heads, Lmax, pos0);
     return (int)hipGetLastError();
+  }
+  if (vt && !state && ldvt > L) {
+    const size_t es = dt == BF16 ? 2 : 4;
+    const hipError_t rc = hipMemset2DAsync((char*)vt + (size_t)L * es, (size_t)ldvt * es, 0, (size_t)(ldvt - L) * es, (size_t)B * heads * hd, st);
+    if (rc != hipSuccess) return (int)rc;
   }
   dim3 g(cdiv(total, 256));
   if (dt == BF16)

@@ -58,7 +58,8 @@ struct StepState {  // device-resident per-generate state (so one captured step 
 int launch_embed(const int64_t* ids, long id_stride, const void* E, void* x, DType dt, int B, int L, int H, int V, hipStream_t st,
                  long x_bstride = 0);
 // RoPE on q,k of qkv[M][3H] (in place) and append k,v to the cache [B][heads][Lmax][hd]; position of row (b, l) = pos0 + l
-// (pos0 from *state when state != null).  vt (optional): transposed V scratch [B][heads][hd][ldvt] for the prefill P.V GEMM.
+// (pos0 from *state when state != null).  vt (optional): transposed V scratch [B][heads][hd][ldvt] for the prefill P.V GEMM;
+// without a state its columns [L, ldvt) are zeroed.
 int launch_rope_kv(void* qkv, void* kc, void* vc, void* vt, int ldvt, const float* cosT, const float* sinT, int B, int L,
                    int heads, int hd, int Lmax, const StepState* state, int pos0, DType dt, hipStream_t st);
 // single-token step: RoPE of q / new k at position *pos, append k, v to the cache, then

@@ -465,7 +465,8 @@ def test_eval_forward_matches_reference_loss():
 
 def test_eval_forward_full_width_loss_vs_oracle():
     """12-layer small Llama, L = 751 (2 context + 14 future frames), 3 trajectories: loss / per-sample loss vs the oracle's
-    eval_forward (the row chunking of the fused cross-entropy is exercised: 2253 rows)."""
+    eval_forward.  The 2253 rows fit in ONE 4096-row lm_head chunk of the fused cross-entropy: several chunks are exercised by
+    tests/test_gpu_prefill.py test_eval_cross_entropy_across_row_chunks_vs_fp64."""
     from oracle.llama import eval_forward
     from ivideogpt_amd import weights as W
     cfg = dict(W.LLAMA_SMALL)
