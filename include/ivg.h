@@ -112,6 +112,17 @@ void ivg_reload_switches(void);
  * ivideogpt/transformer/action_model.py:61,89,104,128,143): the logits are divided by it before the top-k filter
  * (TemperatureLogitsWarper).  Engine state, default 1.0; IVG_ERR_INVALID unless strictly positive and finite (HF raises). */
 int ivg_set_temperature(ivg_engine* e, float temperature);
+/* `top_p` of HF generate (TopPLogitsWarper; the reference's callers never pass it).  Engine state, default 1.0 (no filter);
+ * IVG_ERR_INVALID outside [0, 1] or NaN (HF raises).  It covers every generate entry of the engine.  Per row, the sampler runs
+ *   1. logits / temperature (fp32);
+ *   2. the top-k kept set, ties at the threshold kept;
+ *   3. (top_p < 1) with e_i = exp(l_i - max) in fp64 over the kept set, Z = sum of e_i and S(i) = sum of e_j over the kept j with
+ *      l_j <= l_i: token i survives iff S(i) > (1 - (double)top_p) * Z.  The maximum always survives, so top_p = 0 keeps the maximum
+ *      and the tokens tied with it;
+ *   4. the inverse CDF in ascending id order with the step's uniform over the survivors (fp64).
+ * HF sums an fp32 cumsum where step 3 sums in fp64, and its unstable sort picks which tokens tied AT the nucleus boundary survive
+ * where step 3 keeps all of them: both differ only on measure-zero boundaries.  A row of NaN logits still decides token 0. */
+int ivg_set_top_p(ivg_engine* e, float top_p);
 /* ivg_config.decode_lds_kb of a live engine (0 = back to the process default); takes effect at the next generate call */
 int ivg_set_decode_lds_kb(ivg_engine* e, int kb);
 
@@ -361,6 +372,9 @@ int ivg_op_kv24_pack(const float* k32, const float* v32, void* kc, void* vc, int
 int ivg_op_decode_attn24(const float* qkv, void* kc, void* vc, float* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
                          int P, int G, int row0, ivg_stream stream);
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream);
+/* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
+int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
+                        ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
  * convolutions) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */

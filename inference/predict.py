@@ -23,7 +23,7 @@ GPU = "cuda"
 TOKENS_PER_FRAME = 4 * 4 + 1        # 16 dynamics tokens + the sdf separator
 CTX_TOKENS_PER_FRAME = 16 * 16 + 1
 
-# (flag, kwargs) -- names and defaults of the reference CLI (predict.py:76-91) + --dtype
+# (flag, kwargs) -- names and defaults of the reference CLI (predict.py:76-91) + --dtype, --top_p
 CLI = [
     ("--pretrained_model_name_or_path", dict(type=str, required=True, help="checkpoint directory (tokenizer/ + transformer/)")),
     ("--input_path", dict(type=str, required=True, help=".npz clip")),
@@ -38,6 +38,7 @@ CLI = [
     ("--repeat_times", dict(type=int, default=5, help="independent samples of the future")),
     ("--seed", dict(type=int, default=0, help="seeds python / numpy / torch")),
     ("--dtype", dict(default="bf16", choices=["bf16", "fp32"], help="arithmetic of decode + rollout (tokenize is always fp32)")),
+    ("--top_p", dict(type=float, default=None, help="nucleus filter after top-k (HF generate top_p; absent: none)")),
 ]
 
 
@@ -74,7 +75,7 @@ def predict(args, tokenizer, model, input, actions=None):
     ctx, reps = args.context_length, args.repeat_times
     clip = input.to(GPU, non_blocking=True)[None]
     prompt = tokenizer.encode_context(clip, ctx).repeat(reps, 1)          # == tokenize(...)[0][:, :257 * ctx], repeated
-    extra = {}
+    extra = {} if getattr(args, "top_p", None) is None else {"top_p": args.top_p}
     if actions is not None:
         extra["action"] = actions.to(GPU, non_blocking=True)[None].repeat(reps, 1, 1)
     n_new = TOKENS_PER_FRAME * (args.segment_length - ctx) - 1

@@ -59,6 +59,7 @@ EXPORTS = {
     "ivg_destroy": (None, [C.c_void_p]),
     "ivg_reload_switches": (None, []),
     "ivg_set_temperature": (C.c_int, [C.c_void_p, C.c_float]),
+    "ivg_set_top_p": (C.c_int, [C.c_void_p, C.c_float]),
     "ivg_set_decode_lds_kb": (C.c_int, [C.c_void_p, C.c_int]),
     "ivg_set_context_length": (C.c_int, [C.c_void_p, C.c_int]),
     "ivg_tokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -114,6 +115,7 @@ EXPORTS = {
     "ivg_op_add_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "ivg_op_conv_in": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "ivg_op_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ivg_op_sample_top_p": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_debug_counter": (C.c_int64, [C.c_char_p]),
 }
 

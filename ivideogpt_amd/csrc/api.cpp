@@ -388,6 +388,13 @@ int ivg_set_temperature(ivg_engine* e, float temperature) {
   return IVG_OK;
 }
 
+int ivg_set_top_p(ivg_engine* e, float top_p) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!(top_p >= 0.0f && top_p <= 1.0f)) return e->fail(IVG_ERR_INVALID, "top_p must be a float in [0, 1]");   // HF raises the same (NaN included)
+  e->top_p = top_p;
+  return IVG_OK;
+}
+
 int ivg_engine::effective_lds_kb() const { return decode_lds_kb > 0 ? decode_lds_kb : ivg::sw().decode_lds_kb; }
 
 int ivg_set_decode_lds_kb(ivg_engine* e, int kb) {
@@ -972,6 +979,27 @@ int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperatur
   sa.ids_out = out; sa.ids_stride = 1; sa.L0 = 0; sa.forced_period = 0; sa.forced_token = 0;
   sa.E = logits; sa.x = out; sa.H = 0; sa.act = nullptr; sa.act_T = 0; sa.ctx = 1; sa.slot0 = 0; sa.state = state;
   sa.temperature = temperature;
+  if (!rc) rc = launch_sample_embed(sa, B, F32, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(state);
+  return rc ? IVG_ERR_HIP : IVG_OK;
+}
+
+int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
+                        ivg_stream stream) {
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return IVG_ERR_INVALID;   // as ivg_set_temperature
+  if (!(top_p >= 0.0f && top_p <= 1.0f)) return IVG_ERR_INVALID;                       // as ivg_set_top_p
+  // one draw per row through the rollout's sampler kernel (token j = 1 of a prompt of length 0; no embedding: H = 0)
+  StepState* state = nullptr;
+  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_state_set(state, 0, 1, st);
+  SampleArgs sa{};
+  sa.logits = logits; sa.V = V; sa.uniforms = uniforms; sa.n_uni = 1; sa.top_k = top_k;
+  sa.ids_out = out; sa.ids_stride = 1; sa.L0 = 0; sa.forced_period = 0; sa.forced_token = 0;
+  sa.E = logits; sa.x = out; sa.H = 0; sa.act = nullptr; sa.act_T = 0; sa.ctx = 1; sa.slot0 = 0; sa.state = state;
+  sa.temperature = temperature;
+  sa.top_p = top_p;
   if (!rc) rc = launch_sample_embed(sa, B, F32, st);
   (void)hipStreamSynchronize(st);
   (void)hipFree(state);

@@ -102,6 +102,7 @@ struct ivg_engine {
   int effective_lds_kb() const;
   bool in_flight() const { return effective_lds_kb() < 160; }
   float temperature = 1.0f;   // sampling temperature of the rollout (ivg_set_temperature; HF TemperatureLogitsWarper semantics)
+  float top_p = 1.0f;         // nucleus filter of the rollout (ivg_set_top_p; HF TopPLogitsWarper up to the documented boundaries)
   ivg::ProfClass prof[IVG_K_COUNT];
   unsigned long long* attn_prof = nullptr;  // [layers][IVG_ATTN_PROF_SLOTS][2][Lmax] wall-clock stamps of the decode attention
   bool attn_prof_on = false;                // ivg_profile_enable(IVG_K_DECODE_ATTN): part of the step-graph key

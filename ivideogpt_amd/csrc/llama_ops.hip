@@ -1065,7 +1065,24 @@ __device__ __forceinline__ int block_suffix_excl(int x, int* s4, int lane, int w
   return incl - x + above;
 }
 
-template <typename T, int KPT>  // KPT logits per thread (contiguous segment): vocab <= 256 * KPT
+// order key of the nucleus filter: f2key with -0.0 folded onto +0.0, so that key order is exactly the float order l_j <= l_i
+__device__ __forceinline__ unsigned nkey(float f) { return f == 0.0f ? 0x80000000u : f2key(f); }
+
+// fp64 sum over the 256 threads of a workgroup in one fixed order (xor butterfly, then waves 0..3): every thread gets the same value
+__device__ __forceinline__ double block_sum_f64(double x, double* s_w, int lane, int wv) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if (lane == 0) s_w[wv] = x;
+  __syncthreads();
+  const double t = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  __syncthreads();
+  return t;
+}
+
+// NUCLEUS (a.top_p < 1; include/ivg.h ivg_set_top_p): after the top-k filter a kept token i survives iff
+// S(i) = sum of e_j = exp(l_j - max) over the kept j with l_j <= l_i exceeds (1 - top_p) * Z, Z the sum over every kept token (fp64),
+// or l_i is the maximum.  The instances without it are the sampler as it was: every NUCLEUS branch is `if constexpr`.
+template <typename T, int KPT, bool NUCLEUS>  // KPT logits per thread (contiguous segment): vocab <= 256 * KPT
 __global__ __launch_bounds__(256) void sample_embed_kernel(SampleArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* lg = (float*)smem;  // [V] staging: coalesced global read, then each thread takes a contiguous segment
@@ -1075,7 +1092,7 @@ __global__ __launch_bounds__(256) void sample_embed_kernel(SampleArgs a) {
   __shared__ int s_sel[2];
   __shared__ __attribute__((aligned(16))) int hist[2048];
   __shared__ int kid[SAMPLE_CAP];
-  __shared__ float cval[SAMPLE_CAP];
+  __shared__ __attribute__((aligned(16))) float cval[SAMPLE_CAP];
   __shared__ double s_w[4];
   __shared__ long s_tok;
   __shared__ double s_target;
@@ -1286,6 +1303,39 @@ __global__ __launch_bounds__(256) void sample_embed_kernel(SampleArgs a) {
             part += ex[r];
           }
         }
+        if constexpr (NUCLEUS) {
+          // S(i) by counting over the list: each listed token sums the weights of the listed tokens not above it (ascending
+          // id order, fp64).  The weights go to the staging row, free once the list is built (the launch gives it >= 8 KiB).
+          double* s_e = (double*)lg;
+#pragma unroll
+          for (int r = 0; r < SAMPLE_CAP / 256; ++r)
+            if (r < per && e0 + r < e1) s_e[e0 + r] = ex[r];
+          if (tid < 8 && n_list + tid < SAMPLE_CAP) s_e[n_list + tid] = 0.0;   // pad to a multiple of 8: weightless
+          const double cut = (1.0 - (double)a.top_p) * block_sum_f64(part, s_w, lane, wv);   // (synchronises: s_e is complete)
+          part = 0.0;
+#pragma unroll
+          for (int r = 0; r < SAMPLE_CAP / 256; ++r) {
+            if (r < per && ex[r] > 0.0) {
+              // the list padded to a multiple of 8 with weightless entries, read 16 bytes at a time, 8 independent fp64 chains combined
+              // in one fixed order: a single chain over ~150 entries waited on LDS and add latency at every step (+10 us per launch)
+              const float li = cval[e0 + r];
+              double S = 0.0;
+              const int n8 = (n_list + 7) & ~7;
+              double S0 = 0.0, S1 = 0.0, S2 = 0.0, S3 = 0.0, S4 = 0.0, S5 = 0.0, S6 = 0.0, S7 = 0.0;
+#pragma unroll 2
+              for (int jj = 0; jj < n8; jj += 8) {
+                const float4 ca = *(const float4*)&cval[jj], cb = *(const float4*)&cval[jj + 4];
+                const double2 ea = *(const double2*)&s_e[jj], eb = *(const double2*)&s_e[jj + 2];
+                const double2 ec = *(const double2*)&s_e[jj + 4], ed = *(const double2*)&s_e[jj + 6];
+                S0 += ca.x <= li ? ea.x : 0.0; S1 += ca.y <= li ? ea.y : 0.0; S2 += ca.z <= li ? eb.x : 0.0; S3 += ca.w <= li ? eb.y : 0.0;
+                S4 += cb.x <= li ? ec.x : 0.0; S5 += cb.y <= li ? ec.y : 0.0; S6 += cb.z <= li ? ed.x : 0.0; S7 += cb.w <= li ? ed.y : 0.0;
+              }
+              S = ((S0 + S1) + (S2 + S3)) + ((S4 + S5) + (S6 + S7));
+              if (!(S > cut || li == mx)) ex[r] = 0.0;
+            }
+            part += ex[r];
+          }
+        }
         double incl = part;  // inclusive scan over threads (thread order == id order)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -1315,10 +1365,34 @@ __global__ __launch_bounds__(256) void sample_embed_kernel(SampleArgs a) {
         if (tok < 0) tok = mi;  // unreachable for u in [0, 1): defensive
       } else {
         // general path (massive ties at the threshold): every thread walks its own id segment
+        unsigned tau = 0u;   // NUCLEUS: the survivors are the kept tokens with nkey >= tau
+        if constexpr (NUCLEUS) {
+          // tau = the smallest key T with G(T) = sum of the kept weights with nkey <= T above the cut (G is monotone in T):
+          // 32 rounds of bisection over the key space, each one fixed-order fp64 block sum (deterministic, no atomics)
+          double e[KPT];
+          double zp = 0.0;
+#pragma unroll
+          for (int q = 0; q < KPT; ++q) {
+            e[q] = (key[q] >= thr && v[q] > -INFINITY) ? exp((double)(v[q] - mx)) : 0.0;
+            zp += e[q];
+          }
+          const double Z = block_sum_f64(zp, s_w, lane, wv);
+          const double cut = (1.0 - (double)a.top_p) * Z;
+          unsigned lo = 0u, hi = 0xffffffffu;
+          if (!(Z > cut)) lo = hi;   // top_p = 0 (or nothing kept): the maximum alone
+          while (lo < hi) {          // uniform: every thread holds the same sums
+            const unsigned mid = lo + ((hi - lo) >> 1);
+            double m = 0.0;
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) m += nkey(v[q]) <= mid ? e[q] : 0.0;
+            if (block_sum_f64(m, s_w, lane, wv) > cut) hi = mid; else lo = mid + 1;
+          }
+          tau = min(lo, nkey(mx));   // the maximum always survives
+        }
         double part = 0.0;
 #pragma unroll
         for (int q = 0; q < KPT; ++q)
-          if (key[q] >= thr && v[q] > -INFINITY) part += exp((double)(v[q] - mx));
+          if (key[q] >= thr && v[q] > -INFINITY && (!NUCLEUS || nkey(v[q]) >= tau)) part += exp((double)(v[q] - mx));
         double incl = part;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -1341,7 +1415,7 @@ __global__ __launch_bounds__(256) void sample_embed_kernel(SampleArgs a) {
           long found = -1, last = -1;
 #pragma unroll
           for (int q = 0; q < KPT; ++q) {
-            if (key[q] >= thr && v[q] > -INFINITY) {
+            if (key[q] >= thr && v[q] > -INFINITY && (!NUCLEUS || nkey(v[q]) >= tau)) {
               run += exp((double)(v[q] - mx));
               last = i0 + q;
               if (found < 0 && run > target) found = i0 + q;
@@ -1371,19 +1445,27 @@ __global__ __launch_bounds__(256) void sample_embed_kernel(SampleArgs a) {
   }
 }
 
-template <typename T, int KPT>
+template <typename T, int KPT, bool NUCLEUS>
 static void launch_sample_t(const SampleArgs& a, int B, size_t smem, hipStream_t st) {
   static DynLdsOnce once;
-  (void)ensure_dyn_lds(once, (const void*)sample_embed_kernel<T, KPT>, 96 * 1024);
-  hipLaunchKernelGGL((sample_embed_kernel<T, KPT>), dim3(B), dim3(256), smem, st, a);
+  (void)ensure_dyn_lds(once, (const void*)sample_embed_kernel<T, KPT, NUCLEUS>, 96 * 1024);
+  hipLaunchKernelGGL((sample_embed_kernel<T, KPT, NUCLEUS>), dim3(B), dim3(256), smem, st, a);
+}
+
+template <bool NUCLEUS>
+static void launch_sample_dt(const SampleArgs& a, int B, DType dt, size_t smem, hipStream_t st) {
+  const bool small = a.V <= 256 * 36;
+  if (dt == BF16) { if (small) launch_sample_t<bf16_t, 36, NUCLEUS>(a, B, smem, st); else launch_sample_t<bf16_t, 72, NUCLEUS>(a, B, smem, st); }
+  else { if (small) launch_sample_t<float, 36, NUCLEUS>(a, B, smem, st); else launch_sample_t<float, 72, NUCLEUS>(a, B, smem, st); }
 }
 
 int launch_sample_embed(const SampleArgs& a, int B, DType dt, hipStream_t st) {
   const size_t smem = (size_t)std::max(a.V, SAMPLE_CAP) * sizeof(float);
   if (a.V > 256 * 72 || smem > 96 * 1024) return (int)hipErrorInvalidValue;
-  const bool small = a.V <= 256 * 36;
-  if (dt == BF16) { if (small) launch_sample_t<bf16_t, 36>(a, B, smem, st); else launch_sample_t<bf16_t, 72>(a, B, smem, st); }
-  else { if (small) launch_sample_t<float, 36>(a, B, smem, st); else launch_sample_t<float, 72>(a, B, smem, st); }
+  if (a.top_p < 1.0f)   // the nucleus filter keeps the list's fp64 weights in the staging row: SAMPLE_CAP doubles
+    launch_sample_dt<true>(a, B, dt, std::max(smem, (size_t)SAMPLE_CAP * sizeof(double)), st);
+  else
+    launch_sample_dt<false>(a, B, dt, smem, st);
   return (int)hipGetLastError();
 }
 

@@ -98,6 +98,7 @@ struct SampleArgs {
   int slot0;                                   // sdf slots already inside the prompt beyond the first: (L0 - 257*ctx) / 17
   StepState* state;
   float temperature;                           // logits / temperature before the top-k filter (HF TemperatureLogitsWarper); 1.0: none
+  float top_p = 1.0f;                          // nucleus filter after the top-k filter (include/ivg.h ivg_set_top_p); 1.0: none
 };
 int launch_sample_embed(const SampleArgs& a, int B, DType dt, hipStream_t st);
 int launch_state_set(StepState* state, int pos, int j, hipStream_t st);

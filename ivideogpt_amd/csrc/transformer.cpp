@@ -391,11 +391,13 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     sa.slot0 = actions ? (L0 - 257 * ctx) / 17 : 0;  // a prompt that already holds t generated frames (MBRL step-wise rollout)
     sa.state = g.state;
     sa.temperature = e->temperature;
+    sa.top_p = e->top_p;
     // step 1 eagerly (also performs every kernel's one-time attribute setup), then replay a captured step graph
-    // (everything a captured step bakes in: the temperature by its BIT PATTERN -- to_string keeps six decimals --, this engine's LDS
-    // budget and the generation of the switch table, whose kernel-selection switches a replayed graph would otherwise keep ignoring)
+    // (everything a captured step bakes in: the temperature and top_p by their BIT PATTERNS -- to_string keeps six decimals --, this
+    // engine's LDS budget and the generation of the switch table, whose kernel-selection switches a replayed graph would otherwise keep ignoring)
     uint32_t t_bits; memcpy(&t_bits, &e->temperature, 4);
-    const std::string key = std::to_string(Bc) + ":" + std::to_string(t_bits) + ":" + std::to_string(e->decode_lds_kb) + ":" + std::to_string(switches_generation()) +
+    uint32_t p_bits; memcpy(&p_bits, &e->top_p, 4);
+    const std::string key = std::to_string(Bc) + ":" + std::to_string(t_bits) + ":" + std::to_string(p_bits) + ":" + std::to_string(e->decode_lds_kb) + ":" + std::to_string(switches_generation()) +
                             ":" + (uniforms ? "s" : "g") + ":" + std::to_string(top_k) + ":" +
                             std::to_string(sa.forced_period) + ":" + std::to_string(ctx) + ":" + std::to_string(act_T) + ":" +
                             std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)

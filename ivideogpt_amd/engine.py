@@ -68,6 +68,7 @@ class Engine:
         self._caches = set()   # live detokenize caches (device memory owned here: released with the engine)
         self._clamp_out = False
         self._temperature = 1.0
+        self._top_p = 1.0
         self._run = None       # the stream of the last call (the dedicated one, or the caller's own)
 
     def close(self):
@@ -126,6 +127,14 @@ class Engine:
         if t != self._temperature:
             self.check(self.lib.ivg_set_temperature(self.h, t), "set_temperature")
             self._temperature = t
+        return self
+
+    def set_top_p(self, p):
+        """``top_p`` of HF generate (nucleus filter after the top-k filter, include/ivg.h ivg_set_top_p; 1.0: none).  Engine state."""
+        p = float(p)
+        if p != self._top_p:
+            self.check(self.lib.ivg_set_top_p(self.h, p), "set_top_p")
+            self._top_p = p
         return self
 
     def set_decode_lds_kb(self, kb):

@@ -105,6 +105,19 @@ def _from_group_major(x, t, B0):
     return x.view(B0, t, *x.shape[1:]).transpose(0, 1).reshape(x.shape).contiguous()
 
 
+def _top_p_of(top_p, do_sample):
+    """The engine's ``top_p`` for a generate call, checked before any engine work as HF does: only when sampling (HF builds its
+    TopPLogitsWarper only then, so ``do_sample=False`` ignores any value), after ``float(top_p)`` (numpy scalars, 0-d tensors and
+    numeric strings are accepted), ValueError outside [0, 1].  One difference: NaN raises too (HF's range test lets it through and
+    filters nothing).  ``None`` -> 1.0, no filter."""
+    if top_p is None or not do_sample:
+        return 1.0
+    p = float(top_p)
+    if not (0.0 <= p <= 1.0):
+        raise ValueError(f"`top_p` has to be a float >= 0 and <= 1, but is {top_p}")
+    return p
+
+
 class LlamaForCausalLM:
     supports_shared_context = True   # generate / detokenize accept shared_context= (libivg ivg_generate_shared / ivg_detokenize_shared)
     def __init__(self, config, state_dict=None, dtype="bf16", prefix="", action_dim=None, reward_prediction=False, decode_lds_kb=0):
@@ -266,8 +279,10 @@ class LlamaForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=None,
                  generator=None, uniforms=None, inputs_embeds=None, return_dict_in_generate=False, output_hidden_states=False,
-                 use_cache=True, shared_context=None, **unused):
+                 use_cache=True, shared_context=None, top_p=None, **unused):
         """``input_ids`` prompt -> int64 (B, L0 + max_new_tokens), prompt included (HF convention).
+        ``top_p``: HF's nucleus filter after the top-k filter (include/ivg.h ivg_set_top_p); ``None`` / 1.0: none, ignored without
+        ``do_sample``, ValueError outside [0, 1] or NaN (``_top_p_of``).
         ``shared_context`` (not in HF; round 6): ``t`` or ``"auto"`` when ``input_ids`` is ``prompts.repeat(t, 1)`` -- what
         inference/predict.py:65 and train_gpt.py:170-184 pass.  The prompt is then prefilled ONCE per distinct row, its K / V rows are kept
         once and shared by the t samples at every decode step (libivg ``ivg_generate_shared``); row order, uniforms and results are those
@@ -280,13 +295,14 @@ class LlamaForCausalLM:
         the embeddings of the tokens it generated), only the last row is fed -- verified on the device, never assumed."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):   # HF's TemperatureLogitsWarper raises the same way
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        top_p = _top_p_of(top_p, do_sample)
         if inputs_embeds is not None:
             emb = inputs_embeds.to(device=self.device, dtype=self.torch_dtype).contiguous()
             B, L0, _ = emb.shape
             out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=self.device)
             hidden = torch.empty(B, 1, emb.shape[-1], dtype=self.torch_dtype, device=self.device) if output_hidden_states else None
             u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
-            self.last_generate_reused_cache = self._ensure(B).set_temperature(temperature).generate_embeds(
+            self.last_generate_reused_cache = self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_embeds(
                 emb, max_new_tokens, out, hidden=hidden, uniforms=u, top_k=top_k or self._cfg["vocab_size"], allow_reuse=use_cache)
             if not return_dict_in_generate:
                 return out
@@ -297,10 +313,10 @@ class LlamaForCausalLM:
         u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
         t, B0 = shared_prompt_groups(ids, shared_context) if shared_context else (1, B)
         if t > 1 and L0 >= 2:
-            self._ensure(B).set_temperature(temperature).generate_shared(ids[:B0].contiguous(), t, max_new_tokens, out, uniforms=_to_group_major(u, t, B0),
-                                                                         top_k=top_k or self._cfg["vocab_size"])
+            self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_shared(
+                ids[:B0].contiguous(), t, max_new_tokens, out, uniforms=_to_group_major(u, t, B0), top_k=top_k or self._cfg["vocab_size"])
             return _from_group_major(out, t, B0)
-        self._ensure(B).set_temperature(temperature).generate(ids, max_new_tokens, out, uniforms=u, top_k=top_k or self._cfg["vocab_size"])
+        self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate(ids, max_new_tokens, out, uniforms=u, top_k=top_k or self._cfg["vocab_size"])
         return out
 
     @torch.no_grad()
@@ -431,7 +447,7 @@ class HeadModelWithAction:
 
     @torch.no_grad()
     def generate(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=50256,
-                 action=None, generator=None, uniforms=None, return_reward=False, reuse_cache=False, shared_context=None):
+                 action=None, generator=None, uniforms=None, return_reward=False, reuse_cache=False, shared_context=None, top_p=None):
         """action_model.py:56-121: action (B, T, D); new token j is the forced sdf when j % 17 == 0; the i-th sdf slot's
         embedding gets ``action_linear(action[:, i + context - 1])``.  -> int64 (B, L0 + max_new_tokens).
         ``shared_context``: as ``LlamaForCausalLM.generate`` -- ``inputs_token`` is ``prompts.repeat(t, 1)`` (train_gpt.py:170, VP2's
@@ -439,9 +455,11 @@ class HeadModelWithAction:
         before the first action slot).
         ``reuse_cache=True`` (step-wise rollouts, mbrl/video_predictor.py:286-317): the prompt is the previous call's full
         output plus the forced ``sdf``; the engine keeps the KV cache of that call and feeds only the last prompt token
-        instead of prefilling the grown prompt again (raises AssertionError when the cache holds something else)."""
+        instead of prefilling the grown prompt again (raises AssertionError when the cache holds something else).
+        ``top_p`` (not in the reference's signature; an extension like ``shared_context``): as ``LlamaForCausalLM.generate``."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        top_p = _top_p_of(top_p, do_sample)
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
@@ -451,30 +469,34 @@ class HeadModelWithAction:
         reward = torch.empty(B, dtype=torch.float32, device=llm.device) if return_reward else None
         t, B0 = shared_prompt_groups(ids, shared_context) if (shared_context and not reuse_cache) else (1, B)
         if t > 1 and L0 == 257 * self.context:
-            llm._ensure(B, act.shape[1]).set_temperature(temperature).generate_shared(
+            llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate_shared(
                 ids[:B0].contiguous(), t, max_new_tokens, out, actions=_to_group_major(act, t, B0), ctx=self.context, uniforms=_to_group_major(u, t, B0),
                 top_k=top_k or llm._cfg["vocab_size"], reward=reward)
             out, reward = _from_group_major(out, t, B0), _from_group_major(reward, t, B0)
             return (out, reward) if return_reward else out
-        llm._ensure(B, act.shape[1]).set_temperature(temperature).generate(ids, max_new_tokens, out, actions=act, ctx=self.context, uniforms=u,
-                                              top_k=top_k or llm._cfg["vocab_size"], reward=reward, reuse_kv=reuse_cache)
+        llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate(
+            ids, max_new_tokens, out, actions=act, ctx=self.context, uniforms=u, top_k=top_k or llm._cfg["vocab_size"], reward=reward,
+            reuse_kv=reuse_cache)
         return (out, reward) if return_reward else out
 
     @torch.no_grad()
     def generate_without_action(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, generator=None,
-                                uniforms=None):
+                                uniforms=None, top_p=None):
         """action_model.py:123-152 (no caller in the reference): per future frame 16 sampled tokens, then the forced ``sdf`` -- the
         schedule of ``generate`` without any action embedding; the last forced ``sdf`` is dropped.  -> int64 (B, L0 + max_new_tokens).
-        One prefill + cached steps instead of the reference's per-frame re-prefill (token-identical: same argument as ``generate``)."""
+        One prefill + cached steps instead of the reference's per-frame re-prefill (token-identical: same argument as ``generate``).
+        ``top_p`` (an extension, as in ``generate``): as ``LlamaForCausalLM.generate``."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        top_p = _top_p_of(top_p, do_sample)
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
         assert (max_new_tokens + 1) % (self.segment_length - self.context) == 0, "max_new_tokens must be (tokens_per_dyna + 1) * frames - 1"
         out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
         u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
-        llm._ensure(B).set_temperature(temperature).generate_forced_sdf(ids, max_new_tokens, out, ctx=self.context, uniforms=u, top_k=top_k or llm._cfg["vocab_size"])
+        llm._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_forced_sdf(ids, max_new_tokens, out, ctx=self.context, uniforms=u,
+                                                                               top_k=top_k or llm._cfg["vocab_size"])
         return out
 
     @torch.no_grad()
