@@ -72,7 +72,8 @@ typedef struct {
   int32_t hidden_size;
   int32_t intermediate_size;
   int32_t num_layers;
-  int32_t num_heads;
+  int32_t num_heads;       /* must divide hidden_size; head_dim = hidden_size / num_heads must be one the decode-attention kernel
+                            * covers (bf16: 8, 16, 32, 64, 128, 256; fp32 and IVG_F32X3: 4 and those): IVG_ERR_INVALID at create otherwise */
   int32_t vocab_size;
   int32_t max_position_embeddings;
   float rms_norm_eps;
@@ -85,7 +86,7 @@ typedef struct {
   /* ---- capacity the workspace / KV cache are sized for */
   int32_t max_batch;       /* trajectories per call */
   int32_t max_frames;      /* frames per clip (T) */
-  int32_t max_seq;         /* KV-cache length (0: max_position_embeddings) */
+  int32_t max_seq;         /* KV-cache length (0: max_position_embeddings; above it: IVG_ERR_INVALID, the RoPE tables end there) */
   /* ---- launch policy of THIS engine (no process-global state on the data path: a latency engine and a throughput engine can
    * live in one process, e.g. mbrl/video_predictor.py's step-wise rollout beside a batch evaluator) */
   int32_t decode_lds_kb;   /* LDS budget of a decode-step GEMM workgroup in KiB (16 .. 160); 0: the process default (IVG_DECODE_LDS_KB,
@@ -350,7 +351,9 @@ int ivg_op_conv_in(const void* video, int video_dtype, const float* w, const flo
 /* One decode-attention step of a shared-context rollout (ivg_generate_shared): qkv (B, 3 * heads * hd) of the tokens being fed (RoPE
  * at `pos` is applied inside, the new k / v are appended at cache position `pos` of every row), caches kc / vc
  * (rows, heads, Lmax, hd) in which group slot s = (b - row0) / G (row0 <= 0) holds the shared prompt rows [0, P) in cache row s and
- * every trajectory b its own rows [P, pos) in cache row b; out (B, heads * hd).  With G = 1 and P = 0: the plain step. */
+ * every trajectory b its own rows [P, pos) in cache row b; out (B, heads * hd).  With G = 1 and P = 0: the plain step.  A head dim
+ * the kernel does not cover (include/ivg.h ivg_config.num_heads), a dtype other than IVG_F32 / IVG_BF16 or inconsistent positions:
+ * IVG_ERR_INVALID before anything is allocated or launched. */
 int ivg_op_shared_decode_attn(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int hd, int Lmax,
                               int pos, int P, int G, int row0, int dtype, ivg_stream stream);
 /* One prefill layer's attention over a prompt at positions [0, L) (1 <= L <= Lmax; hd even; dtype IVG_F32 or IVG_BF16): qkv [B * L][3 * heads * hd]

@@ -307,6 +307,22 @@ int ivg_create(const ivg_config* cfg, const ivg_tensor* weights, int n_weights, 
   e->ctx = cfg->context_length > 0 ? cfg->context_length : 1;
   for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = weights[i];
   if (cfg->max_batch <= 0 || cfg->max_frames <= 0) { e->err = "ivg_create: max_batch / max_frames must be positive"; return bail(IVG_ERR_INVALID); }
+  if (cfg->num_layers > 0) {   // transformer shape checks, before anything is built or launched
+    if (cfg->num_heads <= 0 || cfg->hidden_size <= 0 || cfg->hidden_size % cfg->num_heads != 0) {
+      e->err = "ivg_create: hidden_size must be a positive multiple of num_heads"; return bail(IVG_ERR_INVALID);
+    }
+    const int hd = cfg->hidden_size / cfg->num_heads;
+    if (!decode_attn_covers(hd, e->llm_dt)) {
+      e->err = "ivg_create: head_dim " + std::to_string(hd) + " is not supported by the decode-attention kernel (" +
+               (e->llm_dt == BF16 ? "bf16: 8, 16, 32, 64, 128 or 256)" : "fp32: 4, 8, 16, 32, 64, 128 or 256)");
+      return bail(IVG_ERR_INVALID);
+    }
+    if (cfg->max_seq > cfg->max_position_embeddings) {   // the RoPE tables hold max_position_embeddings rows
+      e->err = "ivg_create: max_seq " + std::to_string(cfg->max_seq) + " exceeds max_position_embeddings " +
+               std::to_string(cfg->max_position_embeddings);
+      return bail(IVG_ERR_INVALID);
+    }
+  }
   if (cfg->n_levels > 0) {
     const ivg_config& c = *cfg;
     if (c.n_levels > 8 || c.vq_embed_dim != 64 || c.patch_size != 4 || (c.resolution >> (c.n_levels - 1)) != 16 || c.latent_channels % 32 != 0) {
@@ -923,7 +939,9 @@ int ivg_op_conv_in(const void* video, int video_dtype, const float* w, const flo
 int ivg_op_shared_decode_attn(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int hd, int Lmax,
                               int pos, int P, int G, int row0, int dtype, ivg_stream stream) {
   // unit-test hook of one decode-attention step of a shared-context rollout (decode_attn_kernel SHARED)
-  if (B <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
+  if (B <= 0 || heads <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
+  // a head dim the kernel has no instance for is refused here, before anything is allocated or launched
+  if ((dtype != IVG_F32 && dtype != IVG_BF16) || !decode_attn_covers(hd, (DType)dtype)) return IVG_ERR_INVALID;
   StepState* state = nullptr;
   if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
   hipStream_t st = (hipStream_t)stream;

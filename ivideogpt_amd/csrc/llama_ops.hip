@@ -761,10 +761,15 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
   }
 }
 
+bool decode_attn_covers(int hd, DType dt) {
+  const int vec = dt == BF16 ? 8 : 4;
+  return hd > 0 && hd <= 256 && hd % vec == 0 && 256 % (hd / vec) == 0;
+}
+
 int launch_decode_attn(const void* qkv, void* kc, void* vc, void* out, const float* cosT, const float* sinT, int B, int heads, int hd,
                        int Lmax, const StepState* state, unsigned long long* prof, DType dt, hipStream_t st, int sh_P, int sh_G, int sh_row0) {
+  if (!decode_attn_covers(hd, dt)) return (int)hipErrorInvalidValue;
   const int vec = dt == BF16 ? 8 : 4;
-  if (hd % vec != 0 || hd > 256 || 256 % (hd / vec) != 0 || (hd & 1)) return (int)hipErrorInvalidValue;
   const int gpb = 256 / (hd / vec);
   const size_t smem = (size_t)(3 * hd + Lmax + gpb * hd) * sizeof(float);
   dim3 g(B * heads);

@@ -74,6 +74,10 @@ bool xattn_covers(int P, int kv, int C, int nh, DType dt);   // pure predicate (
 // prof (nullable): [IVG_ATTN_PROF_SLOTS][Lmax starts | Lmax ends] wall-clock stamps (100 MHz) of the launch at each cache
 // position; workgroups spread over the slots so the atomics do not serialise on one address
 #define IVG_ATTN_PROF_SLOTS 32
+// the head dims decode_attn_kernel is instantiated for: hd / VEC lanes (VEC = 8 bf16, 4 fp32) share a key row and must divide the
+// 256 lanes of a workgroup -- bf16 {8, 16, 32, 64, 128, 256}, fp32 {4, 8, 16, 32, 64, 128, 256}.  The prompt path (RoPE kernels, score
+// and P.V GEMMs) covers every one of them; ivg_create refuses a transformer whose head dim fails this, launch_decode_attn any launch
+bool decode_attn_covers(int hd, DType dt);
 // sh_G > 1 (shared-context rollout): chunk row b belongs to group slot (b - sh_row0) / sh_G (sh_row0 <= 0); key rows t < sh_P are read
 // from cache row `slot` (where the prefill of the group's prompt wrote them), rows t >= sh_P from the trajectory's own cache row b
 int launch_decode_attn(const void* qkv, void* kc, void* vc, void* out, const float* cosT, const float* sinT, int B, int heads, int hd,

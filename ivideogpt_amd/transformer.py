@@ -120,8 +120,10 @@ def _top_p_of(top_p, do_sample):
 
 class LlamaForCausalLM:
     supports_shared_context = True   # generate / detokenize accept shared_context= (libivg ivg_generate_shared / ivg_detokenize_shared)
-    def __init__(self, config, state_dict=None, dtype="bf16", prefix="", action_dim=None, reward_prediction=False, decode_lds_kb=0):
+    def __init__(self, config, state_dict=None, dtype="bf16", prefix="", action_dim=None, reward_prediction=False, decode_lds_kb=0,
+                 max_seq=0):
         self._decode_lds_kb = int(decode_lds_kb or 0)   # launch policy of THIS model's engine (set_decode_lds_kb)
+        self._max_seq = int(max_seq or 0)               # KV-cache length (0: max_position_embeddings; never more, ivg_config.max_seq)
         self._cfg = dict(W.LLAMA_SMALL)
         self._cfg.update({k: v for k, v in dict(config).items() if k in self._cfg})
         self.config = SimpleNamespace(**self._cfg)
@@ -156,7 +158,7 @@ class LlamaForCausalLM:
         if self.device.type != "cuda":
             raise RuntimeError("replica(): call .to('cuda') first")
         r = LlamaForCausalLM(self._cfg, self._sd, dtype=self.dtype, prefix=self._prefix, action_dim=self._action_dim,
-                             reward_prediction=self._reward, decode_lds_kb=self._decode_lds_kb)
+                             reward_prediction=self._reward, decode_lds_kb=self._decode_lds_kb, max_seq=self._max_seq)
         r.device = self.device
         r._sd_version = self._sd_version
         if hasattr(self, "_wrapper_heads"):
@@ -247,7 +249,7 @@ class LlamaForCausalLM:
         self._drop_engine()
         self._engine = Engine(self.device, self._packed_weights(), llm_cfg=self._cfg, action_dim=self._action_dim or 0,
                               reward_head=self._reward, llm_dtype=self.dtype, max_batch=cap_b, max_frames=cap_t,
-                              decode_lds_kb=self._decode_lds_kb)
+                              decode_lds_kb=self._decode_lds_kb, max_seq=self._max_seq)
         return self._engine
 
     # LDS budget (KiB) of a decode-step GEMM workgroup for a model whose batch shares the GPU with other batches in flight (bench.py
