@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    (+ the last timed step's frames / metric rows as DIR/*.npy)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full                (+ every side measurement listed below: minutes, not seconds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the hot path over one batch of synthetic clips already resident in HBM:
@@ -12,8 +13,8 @@ A step = one pass of the hot path over one batch of synthetic clips already resi
 Four batches are kept in flight per GPU by default (``--lanes 4``: engine instances over one copy of the weights, each with its own KV
 cache, workspace, HIP stream and host thread, decode GEMMs planned under a 40 KiB LDS budget PER ENGINE -- ``ivg_config.decode_lds_kb``;
 the K timed steps are dealt round-robin to the lanes): the latency- and HBM-bound rollouts of the batches overlap one another.
-``value`` counts the frames of exactly K steps over the wall clock; ``single_lane`` in the line is the same pipeline with one batch in
-flight (the latency of a batch); ``roofline_in_flight`` the aggregate HBM rate of the rollout phase with all lanes running.
+``value`` counts the frames of exactly K steps over the wall clock; with ``--full``, ``single_lane`` in the line is the same pipeline with
+one batch in flight (the latency of a batch), ``roofline_in_flight`` the aggregate HBM rate of the rollout phase with all lanes running.
 Multi-GPU: independent trajectories shard by batch rows (weak scaling: 64 per GPU), no data-path collective; the
 per-sample metric rows are all-gathered over RCCL once per step (the reference's accelerator.gather, train_gpt.py:476-479).
 
@@ -22,11 +23,17 @@ per-sample metric rows are all-gathered over RCCL once per step (the reference's
 GLOBAL batch fixed and splits it over the ranks (default: weak, ``--batch`` trajectories per GPU).
 
 Prints ONE JSON line on rank 0 (see the task contract): value = predicted frames / s over all GPUs, measured over a CLEAN timed
-loop (no measurement hooks); a separate, untimed profiled pass then yields
-  "roofline"     : the kernel class with the most time per step (decode attention / decode GEMMs: HBM; conv3x3 / igemm: MFMA),
-                   the others in "roofline_other"
-  "cpu_baseline" : the oracle's restatement of the reference algorithm timed on this box's host cores (N = 1 only)
-  "fp32_mode"    : the same step with fp32 decode + fp32 rollout, i.e. the arithmetic that meets the 1e-3 parity bar (N = 1 only).
+loop (no measurement hooks).  A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print the line.
+``--full`` adds everything else, before and after the timed loop (each part can be switched off with its --no-* flag):
+  "stage_ms"     : per-stage split of one batch alone (median of 3 passes), before the timed loop
+  "single_lane"  : one batch in flight (>= 10 steps), before the timed loop (with --lanes 1 it is the headline itself, in every run)
+  "roofline"     : an untimed profiled pass: the kernel class with the most time per step (decode attention / decode GEMMs: HBM;
+                   conv3x3 / igemm: MFMA), the others in "roofline_other"; "roofline_in_flight": the decode classes with all lanes running
+  "fp32_mode", "compliant_mode" : the same step in the arithmetic that meets the 1e-3 parity bar (N = 1 only)
+  "other_configs", "shared_context" : BASELINE configs 3 / 4 / 5 and the multi-sample callers (default shapes, N = 1 only)
+  "cpu_baseline" : the oracle's restatement of the reference algorithm timed on the host cores (N = 1 only).
+The headline computes the same frames in both kinds of run: a plain run advances the sampling generator past the draws of the
+passes it skips (``skip_draws`` in main).
 """
 import argparse
 import json
@@ -499,6 +506,9 @@ def main():
     ap.add_argument("--encode-dtype", default="fp32")
     ap.add_argument("--decode-dtype", default="bf16")
     ap.add_argument("--llm-dtype", default="bf16")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-stage split, one batch in flight, "
+                                                         "rooflines, fp32 / x3 modes, configs 3-5, multi-sample callers, host-CPU baseline "
+                                                         "(the --no-* flags below switch parts of it off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp32-mode", action="store_true", help="skip the extra fp32-arithmetic measurement")
     ap.add_argument("--x3-lanes", type=int, default=4, help="batches in flight of the compliant_mode's second figure (round 6, 24-bit K / V cache: "
@@ -514,7 +524,8 @@ def main():
     ap.add_argument("--lane-lds-kb", type=int, default=LlamaForCausalLM.BATCHES_IN_FLIGHT_LDS_KB,
                     help="decode-GEMM LDS budget (KiB) of the engines of the lanes while several batches are in flight (per engine: "
                          "ivg_config.decode_lds_kb / set_decode_lds_kb); 0: the process default, i.e. a whole CU per workgroup (A/B)")
-    ap.add_argument("--only-lanes", action="store_true", help="skip the per-stage and one-batch-in-flight passes (kernel traces of the lanes mode alone)")
+    ap.add_argument("--only-lanes", action="store_true", help="--full: shorten the per-stage and one-batch-in-flight passes to one each "
+                                                               "(kernel traces of the lanes mode alone)")
     ap.add_argument("--lanes", type=int, default=4, help="batches in flight per GPU: engine instances on their own HIP streams and host threads "
                                                          "(1: one batch at a time, the per-batch latency case)")
     ap.add_argument("--conv-gate", type=int, default=0, help="1: at most one lane's convolution phase (encode / decode) on the device at a time "
@@ -594,22 +605,39 @@ def main():
         v = sorted(v)
         return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
-    # ---- per-stage split: median of 3 passes, taken BEFORE anything else runs (one warm-up pass builds the engines)
-    stage_pass()
-    n_sp = 1 if a.only_lanes else 3
-    sp = [stage_pass() for _ in range(n_sp)]
-    stage = {"encode_ms": median([p[0] for p in sp]), "rollout_ms": median([p[1] for p in sp]), "decode_ms": median([p[2] for p in sp]),
-             "passes": n_sp, "note": f"median of {n_sp} passes on one batch alone, before the timed loops"}
+    def skip_draws(n_steps):
+        """Advance sample_gen past the uniforms `n_steps` steps draw (one (B, 17 * F - 1) torch.rand per rollout), without running
+        them: the passes of a --full run that precede the headline and use lane 0's generator are skipped in a plain run, and lane 0
+        still samples what it samples in a --full run."""
+        if not a.greedy:
+            for _ in range(n_steps):
+                torch.rand(B, 17 * F - 1, device=dev, dtype=torch.float32, generator=sample_gen)
 
-    # ---- one batch in flight (the latency of a batch): >= 10 timed steps, mean and median
+    # ---- per-stage split (--full): median of 3 passes, taken BEFORE anything else runs (one warm-up pass builds the engines)
+    n_sp = 1 if a.only_lanes else 3
+    stage = None
+    if a.full:
+        stage_pass()
+        sp = [stage_pass() for _ in range(n_sp)]
+        stage = {"encode_ms": median([p[0] for p in sp]), "rollout_ms": median([p[1] for p in sp]), "decode_ms": median([p[2] for p in sp]),
+                 "passes": n_sp, "note": f"median of {n_sp} passes on one batch alone, before the timed loops"}
+    else:
+        skip_draws(1 + n_sp)
+
+    # ---- one batch in flight (the latency of a batch): >= 10 timed steps, mean and median (--full; with --lanes 1 the headline)
     n1 = a.steps if a.lanes <= 1 else (1 if a.only_lanes else max(10, min(a.steps, 12)))
-    e1, frames, rows, step, t1 = measure(tok, model, pixels, actions, ctx, F, a.greedy, sample_gen, n1, a.warmup if a.lanes <= 1 else 1, per_step=True)
-    assert torch.isfinite(frames).all() and rows.shape == (global_b, 3) and torch.isfinite(rows).all()
-    my_elapsed = e1
-    single = {"value": global_b * F * n1 / parallel.max_over_ranks(e1, dev), "unit": "predicted frames/s", "ms_per_step": e1 / n1 * 1e3,
-              "ms_per_step_median": median(t1) * 1e3, "value_at_median": B * F * world / median(t1), "steps": n1,
-              "note": "one batch in flight (lane 0 alone): the latency of a batch through encode -> rollout -> decode"}
-    steps_timed = n1
+    w1 = a.warmup if a.lanes <= 1 else 1
+    single = None
+    if a.full or a.lanes <= 1:
+        e1, frames, rows, step, t1 = measure(tok, model, pixels, actions, ctx, F, a.greedy, sample_gen, n1, w1, per_step=True)
+        assert torch.isfinite(frames).all() and rows.shape == (global_b, 3) and torch.isfinite(rows).all()
+        my_elapsed = e1
+        single = {"value": global_b * F * n1 / parallel.max_over_ranks(e1, dev), "unit": "predicted frames/s", "ms_per_step": e1 / n1 * 1e3,
+                  "ms_per_step_median": median(t1) * 1e3, "value_at_median": B * F * world / median(t1), "steps": n1,
+                  "note": "one batch in flight (lane 0 alone): the latency of a batch through encode -> rollout -> decode"}
+        steps_timed = n1
+    else:
+        skip_draws(max(1, w1) + n1)
     in_flight = None
     dumped = None
     if a.dump_outputs and a.lanes <= 1 and rank == 0:     # this loop is the headline: its last step
@@ -648,7 +676,7 @@ def main():
             last_lane = (a.steps - 1) % a.lanes
             dumped = dump_outputs(a.dump_outputs, {"frames": lane_frames[last_lane], "metrics": lane_rows[last_lane]})
         steps_timed = a.steps
-        if not a.no_profile:
+        if a.full and not a.no_profile:
             in_flight = in_flight_pass(lanes, ctx, F, a.greedy, actions is not None)
         model.set_decode_lds_kb(0)
         del lanes[1:]
@@ -690,20 +718,21 @@ def main():
 
     kstats, attn_fit = {}, (0.0, 0.0)
     llm_engine = (model.llm if a.action_dim else model)._engine
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         kstats, attn_fit = profile_classes(tok._engine, llm_engine, step)
 
     # not part of a prediction step: the eval path's full-clip tokenize (train_gpt.py:356: context encoder on the ctx frames +
     # CONDITIONAL encoder with cross-attention on all F future frames of every trajectory, SURVEY.md rows a1 / a3 at batch)
-    tok.tokenize(pixels, ctx)   # warm-up (workspace plan)
-    ev_t = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev_t[0].record()
-    tok.tokenize(pixels, ctx)
-    ev_t[1].record()
-    torch.cuda.synchronize()
-    stage["tokenize_full_ms"] = ev_t[0].elapsed_time(ev_t[1])
-    stage["tokenize_full_note"] = (f"full-clip tokenize of {B} x {T} frames (eval path, outside the timed step): "
-                                   f"{B * T / max(stage['tokenize_full_ms'], 1e-9) * 1e3:.0f} frames/s")
+    if a.full:
+        tok.tokenize(pixels, ctx)   # warm-up (workspace plan)
+        ev_t = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev_t[0].record()
+        tok.tokenize(pixels, ctx)
+        ev_t[1].record()
+        torch.cuda.synchronize()
+        stage["tokenize_full_ms"] = ev_t[0].elapsed_time(ev_t[1])
+        stage["tokenize_full_note"] = (f"full-clip tokenize of {B} x {T} frames (eval path, outside the timed step): "
+                                       f"{B * T / max(stage['tokenize_full_ms'], 1e-9) * 1e3:.0f} frames/s")
 
     # ---- the arithmetic that meets the 1e-3 parity bar, same workload, short runs (N = 1 only):
     #   fp32_mode       fp32 decode + fp32 rollout on f32-input MFMAs (1/16 of the bf16 matrix rate)
@@ -711,7 +740,7 @@ def main():
     #                   operand, fp32 accumulate; conv3x3.hip / igemm.hip / gemm256.hip X3), K / V cache at 24 bits per element in two
     #                   planes (round 6, llama_ops.hip) -- the same 1e-3 bars (tests/test_gpu_x3.py)
     alt = {}
-    if world == 1 and not a.no_fp32_mode and (a.decode_dtype, a.llm_dtype) != ("fp32", "fp32"):
+    if a.full and world == 1 and not a.no_fp32_mode and (a.decode_dtype, a.llm_dtype) != ("fp32", "fp32"):
         del model, tok
         torch.cuda.empty_cache()
         for key, dec, llm, note in (("fp32_mode", "fp32", "fp32", "pixels / logits within 1e-3 of the fp32 reference, token-identical rollouts (tests/test_gpu_models.py)"),
@@ -745,7 +774,7 @@ def main():
     # ---- the other per-GPU shapes of BASELINE.json (configs 3, 4, 5) inside the same driver-observed line: one batch in flight over
     # >= 10 steps (mean and median), then `lanes` batches in flight over 2 * lanes steps -- the two figures config 2 is reported with
     other = {}
-    if world == 1 and default_run and not a.no_other_configs:
+    if a.full and world == 1 and default_run and not a.no_other_configs:
         for k in (3, 4, 5):
             c = CONFIGS[k]
             try:
@@ -812,7 +841,7 @@ def main():
     # frames, generate_max_batchsize 100 / decode_max_batchsize 67 of vp/ivideogpt.yaml), each timed twice: the callers' own flow on
     # the plain entries (every row prefills / stores / streams / decodes its copy of the context) and with shared_context (once per clip)
     shared = {}
-    if world == 1 and default_run and not a.no_other_configs:
+    if a.full and world == 1 and default_run and not a.no_other_configs:
         for key, spec in (("config_1", dict(t=5, frames=16, action_dim=0, gmax=5, dmax=5, steps=8,
                                             what="inference/predict.py: 1 clip, --repeat_times 5, 2 context + 14 predicted frames, 64x64, small transformer")),
                           ("vp2", dict(t=200, frames=12, action_dim=5, gmax=100, dmax=67, steps=4,
@@ -873,10 +902,6 @@ def main():
 
     if rank == 0:
         units = global_b * F * a.steps
-        rl = rooflines(kstats, a)
-        for r in rl:
-            if r.get("kernel", "").startswith("ivg::decode_attn") and attn_fit[1] > 0:   # launch duration = fixed + bytes / rate over the cache lengths
-                r["fit"] = {"fixed_us_per_launch": attn_fit[0], "streaming_GBps": attn_fit[1]}
         name = f"ivideogpt-{'bair' if a.action_dim else 'oxe'}-{a.res}-{'act-cond' if a.action_dim else 'act-free'}{'-medium' if a.medium else ''}"
         default_shapes = not (a.medium or a.action_dim or a.res != 64 or T != 16 or a.ctx)
         cfg_label = a.config or (2 if default_shapes else "custom shapes")
@@ -898,9 +923,13 @@ def main():
                                          f"round-robin, a step = one batch through encode -> rollout -> decode)" if a.lanes > 1 else ""),
                        "lanes": a.lanes},
             "per_rank_frames_per_s": per_rank,
-            "roofline": rl[0], "roofline_other": rl[1:],
-            "stage_ms": stage,
         }
+        if a.full:
+            rl = rooflines(kstats, a)
+            for r in rl:
+                if r.get("kernel", "").startswith("ivg::decode_attn") and attn_fit[1] > 0:   # launch duration = fixed + bytes / rate over the cache lengths
+                    r["fit"] = {"fixed_us_per_launch": attn_fit[0], "streaming_GBps": attn_fit[1]}
+            out.update({"roofline": rl[0], "roofline_other": rl[1:], "stage_ms": stage})
         if in_flight:
             out["roofline_in_flight"] = in_flight
         if dumped:
@@ -912,7 +941,7 @@ def main():
             out["other_configs"] = other
         if shared:
             out["shared_context"] = shared
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # 32 threads: MORE threads make this port slower on the GPU box's host (4 trajectories: 4.35 frames/s on 32 threads, 2.11 on
             # 64, no result within 200 s on all 256 -- profiles/r04_cpu_baseline_threads.txt); --cpu-threads N overrides
             threads = a.cpu_threads or min(32, _cpu_threads())

@@ -191,11 +191,11 @@ def test_decode_lds_budget_is_a_property_of_the_engine(switches):
 
 
 def test_bench_lanes_small_run_with_the_in_flight_roofline():
-    """the profiled passes of bench.py at a small shape: `roofline_in_flight` (all lanes' decode bytes over the union of their rollout
-    intervals) beside `roofline` (one batch alone)"""
+    """the profiled passes of bench.py --full at a small shape: `roofline_in_flight` (all lanes' decode bytes over the union of their
+    rollout intervals) beside `roofline` (one batch alone)"""
     import json
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lanes", "2", "--batch", "4", "--frames", "6", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-fp32-mode"], capture_output=True, text=True, timeout=900,
+                        "--full", "--no-cpu-baseline", "--no-fp32-mode"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -206,11 +206,11 @@ def test_bench_lanes_small_run_with_the_in_flight_roofline():
 
 
 def test_bench_two_lanes_small_run():
-    """``bench.py --lanes 2`` end to end at a small shape: one JSON line with both figures (two batches in flight / one)."""
+    """``bench.py --lanes 2 --full`` end to end at a small shape: one JSON line with both figures (two batches in flight / one)."""
     # (custom shapes: no other_configs block; the fp32 / x3 modes are skipped explicitly)
     import json
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lanes", "2", "--batch", "4", "--frames", "6", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-fp32-mode", "--no-profile"], capture_output=True, text=True, timeout=900,
+                        "--full", "--no-cpu-baseline", "--no-fp32-mode", "--no-profile"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -239,6 +239,31 @@ def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
         assert got[0][k].dtype == np.float32 and np.isfinite(got[0][k]).all()
         assert np.array_equal(got[0][k], got[1][k]), k
     assert got[0]["frames"].min() >= 0 and got[0]["frames"].max() <= 1
+
+
+@pytest.mark.parametrize("lanes,steps", [(2, 3), (1, 2)])
+def test_bench_plain_run_computes_what_the_full_run_computes(tmp_path, lanes, steps):
+    """A plain ``bench.py`` run skips the passes a ``--full`` run makes before the timed loop (per-stage split, one batch in flight),
+    which draw from the generator lane 0 samples with; it advances that generator past their draws instead.  Both runs write the same
+    arrays for the last timed step -- here on lane 0 -- and the plain line carries none of the side figures."""
+    import json
+    import numpy as np
+    got, lines = {}, {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-fp32-mode", "--no-profile"])):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lanes", str(lanes), "--batch", "4", "--frames", "6",
+                            "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / run)] + extra,
+                           capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        lines[run] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        got[run] = {k: np.load(tmp_path / run / f"{k}.npy") for k in ("frames", "metrics")}
+    assert (steps - 1) % lanes == 0                                                   # the dumped step ran on lane 0
+    for k in ("frames", "metrics"):
+        assert np.array_equal(got["plain"][k], got["full"][k]), k
+    for k in ("stage_ms", "roofline", "roofline_in_flight", "cpu_baseline", "fp32_mode", "other_configs"):
+        assert k not in lines["plain"], k
+    assert "stage_ms" in lines["full"] and "roofline" in lines["full"] and lines["full"]["single_lane"]["steps"] == (steps if lanes == 1 else 10)
+    for d in lines.values():
+        assert d["steps"] == steps and abs(d["value"] - 4 * 4 * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-6 * d["value"]
 
 
 def test_engine_runs_on_the_callers_stream_and_orders_a_switch_of_streams():
