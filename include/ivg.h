@@ -339,6 +339,15 @@ int ivg_op_skinny(const void* X, const void* W, void* Y, int M, int N, int K, in
  * requests -- together the batches-in-flight profile, i.e. the kernel plans bench.py's lanes run (tests compare THOSE with fp64) */
 int ivg_op_skinny_policy(const void* X, const void* W, void* Y, int M, int N, int K, int ldx, int ldw, int ldy, int flags, int dtype, int lds_kb,
                          int w_shared, ivg_stream stream);
+/* dtype of both: IVG_F32, IVG_BF16, or IVG_F32X3 (fp32 tensors, split-bf16 arithmetic on the third-generation kernel; the second ignores
+ * it and runs fp32); any other dtype, or lds_kb outside {0} u [16, 160], is IVG_ERR_INVALID before anything launches.
+ * The plan the two would launch for these arguments (X / W / Y only for their alignment; nothing is read or launched), into out[0..10]:
+ * generation (3: dgemm3.hip, 2: dgemm.hip, 0: not covered or nothing to do), row tiles MF, weight tiles FN, waves, then gen 3: lines of
+ * K per wave, ring slots; gen 2: lines per burst LG, bursts, launch-bound class (4 / 8 / 16 waves); then rows of W per workgroup and
+ * the split-bf16 flag.  Test hook: it calls the very plan functions the launchers use. */
+#define IVG_SKINNY_PLAN_INTS 11
+int ivg_op_skinny_plan(int M, int N, int K, int ldx, int ldw, int ldy, int flags, int dtype, int lds_kb, const void* X, const void* W,
+                       const void* Y, int32_t* out);
 int ivg_op_groupnorm(const void* X, void* Y, void* ws /* >= N*chunks*groups*16 B */, const float* gamma, const float* beta,
                      const float* pos, int N, int P, int C, int groups, float eps, int silu, int dtype, ivg_stream stream);
 int ivg_op_softmax(const float* S, void* P, int64_t rows, int Lq, int Lk, int lds, int ldp, int causal, int dtype,

@@ -109,6 +109,7 @@ EXPORTS = {
     "ivg_op_decode_attn24": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
     "ivg_op_skinny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "ivg_op_skinny_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]),
+    "ivg_op_skinny_plan": (C.c_int, [C.c_int] * 9 + [C.c_void_p] * 3 + [C.POINTER(C.c_int32)]),
     "ivg_op_groupnorm": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "ivg_op_softmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 6 + [C.c_void_p]),
     "ivg_op_vq_argmin": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),

@@ -904,12 +904,35 @@ int ivg_op_skinny(const void* X, const void* W, void* Y, int M, int N, int K, in
   return ivg_op_skinny_policy(X, W, Y, M, N, K, ldx, ldw, ldy, flags, dtype, 0, 0, stream);
 }
 
+// dtype IVG_F32X3: fp32 tensors with SkinnyArgs::x3 (split-bf16 arithmetic where dgemm3.hip covers the shape), as Run::gemm sets it
+static bool skinny_op_args(SkinnyArgs& s, DType& dt, int M, int N, int K, int ldx, int ldw, int ldy, int flags, int dtype, int lds_kb) {
+  if (dtype != IVG_F32 && dtype != IVG_BF16 && dtype != IVG_F32X3) return false;
+  if (lds_kb != 0 && (lds_kb < 16 || lds_kb > 160)) return false;
+  s.M = M; s.N = N; s.K = K; s.ldx = ldx; s.ldw = ldw; s.ldy = ldy; s.flags = flags; s.lds_kb = lds_kb;
+  s.x3 = dtype == IVG_F32X3;
+  dt = dtype == IVG_BF16 ? BF16 : F32;
+  return true;
+}
+
 int ivg_op_skinny_policy(const void* X, const void* W, void* Y, int M, int N, int K, int ldx, int ldw, int ldy, int flags, int dtype, int lds_kb,
                          int w_shared, ivg_stream stream) {
-  if (lds_kb != 0 && (lds_kb < 16 || lds_kb > 160)) return IVG_ERR_INVALID;
-  SkinnyArgs s; s.X = X; s.W = W; s.Y = Y; s.M = M; s.N = N; s.K = K; s.ldx = ldx; s.ldw = ldw; s.ldy = ldy; s.flags = flags;
-  s.lds_kb = lds_kb; s.w_shared = w_shared != 0;
-  return launch_skinny(s, (DType)dtype, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
+  SkinnyArgs s;
+  DType dt;
+  if (!skinny_op_args(s, dt, M, N, K, ldx, ldw, ldy, flags, dtype, lds_kb)) return IVG_ERR_INVALID;
+  s.X = X; s.W = W; s.Y = Y; s.w_shared = w_shared != 0;
+  return launch_skinny(s, dt, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
+}
+
+int ivg_op_skinny_plan(int M, int N, int K, int ldx, int ldw, int ldy, int flags, int dtype, int lds_kb, const void* X, const void* W,
+                       const void* Y, int32_t* out) {
+  SkinnyArgs s;
+  DType dt;
+  if (!out || !skinny_op_args(s, dt, M, N, K, ldx, ldw, ldy, flags, dtype, lds_kb)) return IVG_ERR_INVALID;
+  s.X = X; s.W = W; s.Y = (void*)Y;
+  const SkinnyPlan p = skinny_plan(s, dt);
+  const int32_t v[IVG_SKINNY_PLAN_INTS] = {p.gen, p.mf, p.fn, p.waves, p.klw, p.ring, p.lg, p.nburst, p.wmax, p.wr, p.x3};
+  for (int i = 0; i < IVG_SKINNY_PLAN_INTS; ++i) out[i] = v[i];
+  return IVG_OK;
 }
 
 int ivg_op_groupnorm(const void* X, void* Y, void* ws, const float* gamma, const float* beta, const float* pos, int N, int P, int C, int groups,

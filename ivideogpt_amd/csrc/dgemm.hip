@@ -321,12 +321,25 @@ __global__ __launch_bounds__(WMAX * 64) void dgemm_kernel(const DgDev p) {
   if (p.bump && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) { p.bump[0] += 1; p.bump[1] += 1; }
 }
 
+// dynamic LDS of a workgroup: the staging area, or the combine area that aliases it when that is larger
+static int dg_smem(int mf, int fn, int lg, int waves) {
+  const int stage = waves * lg * (mf + fn) * 2048;
+  const int comb = waves * mf * fn * 64 * 16 + waves * mf * 16 * 4;
+  return std::max(stage, comb);
+}
+
+// launch bound = the smallest class that holds the waves (register budget: 4 waves -> 512, 8 -> 256, 16 -> 128 per lane); 0: no
+// instance of that tile holds them
+static int dg_wmax(int mf, int fn, int waves) {
+  if (waves <= 4) return 4;
+  if (mf * fn <= 8 && waves <= 8) return 8;
+  if (mf * fn <= 2 && waves <= 16) return 16;
+  return 0;
+}
+
 template <typename T, int MF, int FN, int LG, int WMAX>
 static int launch_dg(const DgDev& d, int waves, hipStream_t stream) {
-  const int nfrag = FN * MF;
-  const int stage = waves * LG * (MF + FN) * 2048;
-  const int comb = waves * nfrag * 64 * 16 + waves * MF * 16 * 4;
-  const int smem = std::max(stage, comb);
+  const int smem = dg_smem(MF, FN, LG, waves);
   if (smem > 160 * 1024 || waves > WMAX) return -1;
   static DynLdsOnce once;
   auto kfn = dgemm_kernel<T, MF, FN, LG, WMAX>;
@@ -376,12 +389,11 @@ static const DgPick kDgPicks[] = {
 };
 
 template <typename T, int LG>
-static int launch_dg_t(const DgDev& d, int MF, int FN, int waves, hipStream_t st) {
-  // launch bound = the smallest class that holds the waves (register budget: 4 waves -> 512, 8 -> 256, 16 -> 128 per lane)
+static int launch_dg_t(const DgDev& d, int MF, int FN, int waves, int wmax, hipStream_t st) {
 #define IVG_DG(mf, fn) if (MF == mf && FN == fn) { \
-    if (waves <= 4) return launch_dg<T, mf, fn, LG, 4>(d, waves, st); \
-    if constexpr (mf * fn <= 8) { if (waves <= 8) return launch_dg<T, mf, fn, LG, 8>(d, waves, st); } \
-    if constexpr (mf * fn <= 2) return launch_dg<T, mf, fn, LG, 16>(d, waves, st); \
+    if (wmax == 4) return launch_dg<T, mf, fn, LG, 4>(d, waves, st); \
+    if constexpr (mf * fn <= 8) { if (wmax == 8) return launch_dg<T, mf, fn, LG, 8>(d, waves, st); } \
+    if constexpr (mf * fn <= 2) { if (wmax == 16) return launch_dg<T, mf, fn, LG, 16>(d, waves, st); } \
     return -1; }
   IVG_DG(1, 1) IVG_DG(1, 2) IVG_DG(1, 4)
   IVG_DG(2, 1) IVG_DG(2, 2) IVG_DG(2, 4)
@@ -398,18 +410,21 @@ int dgemm_w_rows_per_block(const SkinnyArgs& a, DType dtype) {
   return 16 * ((a.flags & IG_GLU) ? 2 : 1);
 }
 
-// -1: shape not covered (launch_skinny below answers hipErrorInvalidValue); otherwise a hipError_t
-int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
+struct DgPlan { int mf, fn, waves, lg, nburst, wmax; };
+
+// shape -> launch plan; false: not covered.  The K partition (waves x lines per wave) depends on (K bytes, N) only; the batch size
+// and the LDS budget pick the tile (MF, FN), the line groups per burst (LG) and with them the register class.
+static bool dg_plan(const SkinnyArgs& a, DType dtype, DgPlan& pl) {
   const int es = dtype == BF16 ? 2 : 4;
-  if (a.M <= 0 || a.N <= 0 || a.M > 128) return -1;
-  if (((long)a.K * es) % 128 != 0 || ((long)a.ldx * es) % 16 != 0 || ((long)a.ldw * es) % 16 != 0) return -1;
-  if (((uintptr_t)a.X & 15) || ((uintptr_t)a.W & 15)) return -1;
-  if ((long)a.N * a.ldw * es >= (1L << 31) || (long)a.M * a.ldx * es >= (1L << 31)) return -1;   // 32-bit per-lane offsets
+  if (a.M <= 0 || a.N <= 0 || a.M > 128) return false;
+  if (((long)a.K * es) % 128 != 0 || ((long)a.ldx * es) % 16 != 0 || ((long)a.ldw * es) % 16 != 0) return false;
+  if (((uintptr_t)a.X & 15) || ((uintptr_t)a.W & 15)) return false;
+  if ((long)a.N * a.ldw * es >= (1L << 31) || (long)a.M * a.ldx * es >= (1L << 31)) return false;   // 32-bit per-lane offsets
   const bool glu = a.flags & IG_GLU;
-  if (glu && a.N % 32 != 0) return -1;
-  if ((a.flags & IG_RESIDUAL) && !(a.flags & IG_OUT_F32) && ((a.ldy & 3) != 0 || ((uintptr_t)a.Y & (4 * es - 1)))) return -1;
+  if (glu && a.N % 32 != 0) return false;
+  if ((a.flags & IG_RESIDUAL) && !(a.flags & IG_OUT_F32) && ((a.ldy & 3) != 0 || ((uintptr_t)a.Y & (4 * es - 1)))) return false;
   DgSplit sp;
-  if (!dg_split((long)a.K * es / 16, sp)) return -1;
+  if (!dg_split((long)a.K * es / 16, sp)) return false;
   // tile: all rows of the batch in one workgroup when that still leaves >= ~half the CUs busy, W tiles as narrow as the
   // epilogue allows -- activations are cheap now (whole lines out of L2), weight bytes per CU are what is left to balance
   const int mt = cdiv(a.M, 16);
@@ -453,6 +468,17 @@ int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
   }
   while (MF > 1 && waves * lgv * (MF + FN) * 2048 > budget) MF >>= 1;
   if (a.w_shared && sw().dg2_mf_cap > 0) MF = std::min(MF, sw().dg2_mf_cap);   // development A/B (IVG_DG2_MF_CAP)
+  const int wmax = dg_wmax(MF, FN, waves);
+  if (!wmax || dg_smem(MF, FN, lgv, waves) > 160 * 1024) return false;
+  pl = DgPlan{MF, FN, waves, lgv, nburst, wmax};
+  return true;
+}
+
+// -1: shape not covered (launch_skinny below answers hipErrorInvalidValue); otherwise a hipError_t
+int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
+  DgPlan pl;
+  if (!dg_plan(a, dtype, pl)) return -1;
+  const int MF = pl.mf, FN = pl.fn, waves = pl.waves, lgv = pl.lg, nburst = pl.nburst;
   DgDev d{a.X, a.W, a.Y, a.M, a.N, a.K, a.ldx, a.ldw, a.ldy, a.flags, a.eps, a.bump, nburst, a.pos ? a.prof : nullptr, a.pos, a.prof_ld, a.dbg,
           nullptr, 0u, 0, 0, a.w_shared ? 0 : 1};
   if (a.next_W && a.next_tile_bytes >= 1024 && a.next_tiles > 0 && sw().dg3_warm) {
@@ -464,11 +490,21 @@ int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
     d.pf_base = (const char*)a.next_W; d.pf_tile_bytes = (unsigned)a.next_tile_bytes; d.pf_tiles = a.next_tiles; d.pf_per_wave = (int)per;
   }
   int rc;
-  if (dtype == BF16) rc = lgv == 3 ? launch_dg_t<bf16_t, 3>(d, MF, FN, waves, stream) : lgv == 2 ? launch_dg_t<bf16_t, 2>(d, MF, FN, waves, stream)
-                                                                                     : launch_dg_t<bf16_t, 1>(d, MF, FN, waves, stream);
-  else rc = lgv == 3 ? launch_dg_t<float, 3>(d, MF, FN, waves, stream) : lgv == 2 ? launch_dg_t<float, 2>(d, MF, FN, waves, stream)
-                                                                                 : launch_dg_t<float, 1>(d, MF, FN, waves, stream);
+  const int wm = pl.wmax;
+  if (dtype == BF16) rc = lgv == 3 ? launch_dg_t<bf16_t, 3>(d, MF, FN, waves, wm, stream) : lgv == 2 ? launch_dg_t<bf16_t, 2>(d, MF, FN, waves, wm, stream)
+                                                                                         : launch_dg_t<bf16_t, 1>(d, MF, FN, waves, wm, stream);
+  else rc = lgv == 3 ? launch_dg_t<float, 3>(d, MF, FN, waves, wm, stream) : lgv == 2 ? launch_dg_t<float, 2>(d, MF, FN, waves, wm, stream)
+                                                                                     : launch_dg_t<float, 1>(d, MF, FN, waves, wm, stream);
   return rc;
+}
+
+bool dgemm_plan(const SkinnyArgs& a, DType dtype, SkinnyPlan& out) {
+  DgPlan pl;
+  if (!dg_plan(a, dtype, pl)) return false;
+  out = SkinnyPlan{};
+  out.gen = 2; out.mf = pl.mf; out.fn = pl.fn; out.waves = pl.waves; out.lg = pl.lg; out.nburst = pl.nburst; out.wmax = pl.wmax;
+  out.wr = 16 * pl.fn;
+  return true;
 }
 
 // Decode-step GEMM dispatcher (the name survives from the first-generation kernel, removed in round 4: no shape of a released model
@@ -477,6 +513,14 @@ int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
 // the batch.  A shape neither covers (K bytes not a multiple of 128, M > 128, unaligned operands) fails loudly.
 static std::atomic<long long> g_gen3_launches{0}, g_gen2_launches{0};
 long long decode_gemm_launches(int generation) { return (generation == 3 ? g_gen3_launches : g_gen2_launches).load(std::memory_order_relaxed); }
+
+SkinnyPlan skinny_plan(const SkinnyArgs& a, DType dtype) {
+  SkinnyPlan p;
+  if (a.M <= 0 || a.N <= 0) return p;
+  if (dgemm3_plan(a, dtype, p)) return p;
+  if (dgemm_plan(a, dtype, p)) return p;
+  return SkinnyPlan{};
+}
 
 int launch_skinny(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
   if (a.M <= 0 || a.N <= 0) return 0;

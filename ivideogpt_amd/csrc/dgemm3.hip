@@ -492,6 +492,16 @@ int dgemm3_w_rows_per_block(const SkinnyArgs& a, DType dtype) {
   return dg3_plan(a, dtype, pl) ? pl.wr : 0;
 }
 
+bool dgemm3_plan(const SkinnyArgs& a, DType dtype, SkinnyPlan& out) {
+  if (!sw().dg3) return false;
+  Dg3Plan pl;
+  if (!dg3_plan(a, dtype, pl)) return false;
+  out = SkinnyPlan{};
+  out.gen = 3; out.mf = pl.mf; out.fn = pl.fn; out.waves = pl.waves; out.klw = pl.klw; out.ring = pl.ring; out.wr = pl.wr;
+  out.x3 = (a.x3 && dtype == F32) ? 1 : 0;
+  return true;
+}
+
 // -1: shape not covered; otherwise a hipError_t
 int launch_dgemm3(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
   if (!sw().dg3) return -1;   // IVG_DG3=0: second-generation kernel (A/B runs, tests of the older generations)

@@ -102,6 +102,13 @@ struct SkinnyArgs {
 };
 #define IVG_GEMM_PROF_SLOTS 8
 int launch_skinny(const SkinnyArgs& a, DType dtype, hipStream_t stream);   // dispatcher: dgemm3.hip, else dgemm.hip (error: neither covers the shape)
+// The plan launch_skinny launches for these arguments, without launching (test hook ivg_op_skinny_plan).  gen 3: dg3_kernel<T, mf, fn,
+// waves, x3> with klw lines of K per wave through a ring of `ring` slots, wr rows of W per workgroup; gen 2: dgemm_kernel<T, mf, fn,
+// lg, wmax> with nburst bursts of lg lines per wave; gen 0: not covered (or M, N <= 0: nothing to launch).
+struct SkinnyPlan { int gen = 0, mf = 0, fn = 0, waves = 0, klw = 0, ring = 0, lg = 0, nburst = 0, wmax = 0, wr = 0, x3 = 0; };
+SkinnyPlan skinny_plan(const SkinnyArgs& a, DType dtype);
+bool dgemm3_plan(const SkinnyArgs& a, DType dtype, SkinnyPlan& out);   // the launch_dgemm3 plan (false: it answers -1)
+bool dgemm_plan(const SkinnyArgs& a, DType dtype, SkinnyPlan& out);    // the launch_dgemm plan (false: it answers -1)
 // dgemm.hip: second-generation kernel, activations staged as whole cache lines; -1 when the shape is not covered
 int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream);
 // dgemm3.hip: third generation (K over up to 16 waves, one barrier, cache warm-up of the next launch's weights); -1 when not covered
