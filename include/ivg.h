@@ -273,6 +273,27 @@ size_t ivg_frame_metrics_ws_bytes(int n_samples, int T, int H, int W);
 int ivg_frame_metrics(const void* gt, int gt_dtype, int B, int T_gt, int gt_t0, const float* pred, int n_samples, int T_pr, int pr_t0, int T, int H,
                       int W, float* rows_out, void* ws, size_t ws_bytes, ivg_stream stream);
 
+/* LPIPS (VGG-16 variant, v0.1, spatial = False) of predicted clips on the device: the fourth value of Evaluator.forward
+ * (ivideogpt/utils/video_metric.py:75-88; network ivideogpt/vq_model/lpips.py), fp32 arithmetic.  The weights are the caller's: the
+ * engine ships none.  Engine-free; a handle is bound to one device and borrows the weight tensors until ivg_lpips_destroy.
+ *   weights  31 float32 tensors under the state-dict keys of the reference's LPIPS class: net.slice{1..5}.{i}.weight / .bias for
+ *            i in (0, 2 | 5, 7 | 10, 12, 14 | 17, 19, 21 | 24, 26, 28) with the weights packed [Cout][kh][kw][Cin]
+ *            (ivideogpt_amd/packing.py pack_lpips), and lin{0..4}.model.1.weight as vectors of 64 / 128 / 256 / 512 / 512.
+ *            A missing tensor: IVG_ERR_MISSING; a wrong dtype or element count: IVG_ERR_INVALID (text in ivg_last_error(NULL)).
+ *   gt, pred, the frame windows and the sample layout: as ivg_frame_metrics.  H and W: multiples of 16, >= 16 (IVG_ERR_INVALID).
+ *   frames_out  float32 (n_samples, T) per-frame values, or NULL;  rows_out float32 (B): mean over the T frames, min over the t samples
+ *   ws       scratch; the images pass the network in chunks of as many as it holds, and the result does not depend on that number,
+ *            bit for bit.  ivg_lpips_ws_bytes(n, H, W): bytes that carry n images per chunk (a frame pair needs 2; with frames_out
+ *            NULL the per-frame values take n_samples * T * 4 + 256 bytes more).  Too small for one pair: IVG_ERR_CAPACITY.
+ * Every ground-truth frame passes the network once, every predicted frame once: B * T * (1 + t) images.  Nothing is launched and
+ * nothing is written when a status other than IVG_OK / IVG_ERR_HIP is returned. */
+typedef struct ivg_lpips ivg_lpips;
+int ivg_lpips_create(const ivg_tensor* weights, int n_weights, int device, ivg_lpips** out);
+void ivg_lpips_destroy(ivg_lpips* p);
+size_t ivg_lpips_ws_bytes(int max_images_per_chunk, int H, int W);
+int ivg_lpips_rows(ivg_lpips* p, const void* gt, int gt_dtype, int B, int T_gt, int gt_t0, const float* pred, int n_samples, int T_pr, int pr_t0, int T,
+                   int H, int W, float* frames_out, float* rows_out, void* ws, size_t ws_bytes, ivg_stream stream);
+
 /* ---- measurement hooks (bench.py): time one kernel class with HIP events on the launching stream; the decode attention
  * (which runs inside a replayed hipGraph) stamps its own launch windows with the 100 MHz wall clock instead */
 enum ivg_kernel_class { IVG_K_IGEMM_BF16 = 0, IVG_K_IGEMM_F32 = 1, IVG_K_CONV3X3_BF16 = 2, IVG_K_CONV3X3_F32 = 3, IVG_K_DECODE_ATTN = 4,
@@ -387,9 +408,21 @@ int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperatur
 /* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
                         ivg_stream stream);
+/* LPIPS pieces (csrc/lpips.hip).  ivg_op_lpips_features: n images (n, 3, H, W) in [0, 1] (IVG_F32 / IVG_BF16) through the VGG-16 trunk,
+ * taps_out[k] (n, H >> k, W >> k, 64 / 128 / 256 / 512 / 512) NHWC float32 (NULL entries are skipped); ws as ivg_lpips_rows (one image
+ * at least).  ivg_op_lpips_head: out[i] = mean over the P pixels of sum_c lin[c] (f0n - f1n)^2 with f normalised per pixel by
+ * sqrt(sum_c f^2) + 1e-10, image i of f1 (n1, P, C) against image i % n0 of f0 (n0, P, C); C in {64, 128, 256, 512};
+ * ws of at least n1 * 128 bytes.  ivg_op_lpips_conv_in: the input layer alone, (n, 3, H, W) -> relu(conv(((2 x - 1) - shift) / scale))
+ * (n, H, W, 64), w packed [64][3][3][3] as (co, kh, kw, ci).  ivg_op_maxpool2: 2 x 2 / stride 2 max-pool, NHWC float32, C % 4 == 0. */
+int ivg_op_lpips_features(ivg_lpips* p, const void* images, int dtype, int n, int H, int W, float* const* taps_out, void* ws, size_t ws_bytes,
+                          ivg_stream stream);
+int ivg_op_lpips_head(const float* f0, const float* f1, const float* lin, int n0, int n1, int P, int C, float* out, void* ws, size_t ws_bytes,
+                      ivg_stream stream);
+int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const float* bias, float* Y, int n, int H, int W, ivg_stream stream);
+int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

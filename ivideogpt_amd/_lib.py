@@ -10,6 +10,7 @@ IVG_F32, IVG_BF16, IVG_F32X3 = 0, 1, 2
 IVG_K_IGEMM_BF16, IVG_K_IGEMM_F32, IVG_K_CONV3X3_BF16, IVG_K_CONV3X3_F32, IVG_K_DECODE_ATTN, IVG_K_DECODE_GEMM = 0, 1, 2, 3, 4, 5
 # igemm epilogue flags (csrc/igemm.h)
 IG_BIAS_N, IG_BIAS_M, IG_RESIDUAL, IG_SILU, IG_GLU, IG_OUT_F32 = 1, 2, 4, 8, 16, 32
+IG_RELU = 256
 
 
 class IvgTensor(C.Structure):
@@ -92,6 +93,14 @@ EXPORTS = {
     "ivg_frame_metrics_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ivg_frame_metrics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_lpips_create": (C.c_int, [C.POINTER(IvgTensor), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ivg_lpips_destroy": (None, [C.c_void_p]),
+    "ivg_lpips_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ivg_lpips_rows": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "ivg_op_lpips_features": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_op_lpips_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_op_lpips_conv_in": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "ivg_op_maxpool2": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     "ivg_profile_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ivg_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(IvgProfileStats)]),
     "ivg_profile_attn_fit": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -673,6 +673,100 @@ int ivg_frame_metrics(const void* gt, int gt_dtype, int B, int T_gt, int gt_t0, 
                                                                                                                                                 : IVG_OK;
 }
 
+// ---- LPIPS (lpips.hip): a handle is the table of the caller's 13 + 13 + 5 weight tensors
+struct ivg_lpips {
+  int device = 0;
+  const float* cw[13];
+  const float* cb[13];
+  const float* lin[5];
+};
+
+int ivg_lpips_create(const ivg_tensor* weights, int n_weights, int device, ivg_lpips** out) {
+  if (!out) return IVG_ERR_INVALID;
+  *out = nullptr;
+  if (!weights || n_weights <= 0) { g_create_err = "no weight table"; return IVG_ERR_MISSING; }
+  static const int idx[13] = {0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28}, slice[13] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5};
+  static const int cin[13] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512}, cout[13] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+  static const int tapc[5] = {64, 128, 256, 512, 512};
+  int status = IVG_OK;
+  auto find = [&](const std::string& name, int64_t numel) -> const float* {
+    for (int i = 0; i < n_weights; ++i) {
+      if (!weights[i].name || name != weights[i].name) continue;
+      int64_t n = 1;
+      for (int d = 0; d < weights[i].ndim; ++d) n *= weights[i].shape[d];
+      if (weights[i].dtype != IVG_F32 || n != numel || !weights[i].data || ((uintptr_t)weights[i].data & 15)) {
+        if (status == IVG_OK) { status = IVG_ERR_INVALID; g_create_err = "LPIPS weight tensor '" + name + "': expected " + std::to_string(numel) + " float32 elements, 16-byte aligned"; }
+        return nullptr;
+      }
+      return (const float*)weights[i].data;
+    }
+    if (status == IVG_OK) { status = IVG_ERR_MISSING; g_create_err = "missing LPIPS weight tensor '" + name + "'"; }
+    return nullptr;
+  };
+  ivg_lpips h;
+  h.device = device;
+  for (int l = 0; l < 13; ++l) {
+    const std::string n = "net.slice" + std::to_string(slice[l]) + "." + std::to_string(idx[l]);
+    h.cw[l] = find(n + ".weight", (int64_t)cout[l] * 9 * cin[l]);
+    h.cb[l] = find(n + ".bias", cout[l]);
+  }
+  for (int k = 0; k < 5; ++k) h.lin[k] = find("lin" + std::to_string(k) + ".model.1.weight", tapc[k]);
+  if (status != IVG_OK) return status;
+  *out = new ivg_lpips(h);
+  return IVG_OK;
+}
+
+void ivg_lpips_destroy(ivg_lpips* p) { delete p; }
+
+size_t ivg_lpips_ws_bytes(int max_images_per_chunk, int H, int W) {
+  return (max_images_per_chunk <= 0 || H <= 0 || W <= 0) ? 0 : lpips_ws_bytes(max_images_per_chunk, H, W);
+}
+
+static int lpips_status(int rc) { return rc == 0 ? IVG_OK : (rc == -4 ? IVG_ERR_CAPACITY : IVG_ERR_HIP); }
+
+int ivg_lpips_rows(ivg_lpips* p, const void* gt, int gt_dtype, int B, int T_gt, int gt_t0, const float* pred, int n_samples, int T_pr, int pr_t0, int T,
+                   int H, int W, float* frames_out, float* rows_out, void* ws, size_t ws_bytes, ivg_stream stream) {
+  if (!p || !gt || !pred || !rows_out || !ws || (gt_dtype != IVG_F32 && gt_dtype != IVG_BF16)) return IVG_ERR_INVALID;
+  if (B <= 0 || n_samples <= 0 || n_samples % B != 0 || T <= 0 || gt_t0 < 0 || pr_t0 < 0 || gt_t0 + T > T_gt || pr_t0 + T > T_pr) return IVG_ERR_INVALID;
+  if (!lpips_shape_ok(H, W)) return IVG_ERR_INVALID;
+  float* frames = frames_out;
+  if (!frames) {   // the per-frame values live at the end of the workspace
+    const size_t need = ((size_t)n_samples * T * sizeof(float) + 255) & ~(size_t)255;
+    if (ws_bytes < need + 256) return IVG_ERR_CAPACITY;
+    ws_bytes -= need;
+    frames = (float*)(((uintptr_t)ws + ws_bytes) & ~(uintptr_t)255);
+    ws_bytes = (size_t)((char*)frames - (char*)ws);
+  }
+  if (lpips_ws_images(ws_bytes, H, W) < 2) return IVG_ERR_CAPACITY;
+  return lpips_status(launch_lpips_rows(p->cw, p->cb, p->lin, gt, (DType)gt_dtype, B, T_gt, gt_t0, pred, n_samples, T_pr, pr_t0, T, H, W, frames, rows_out,
+                                        ws, ws_bytes, (hipStream_t)stream));
+}
+
+int ivg_op_lpips_features(ivg_lpips* p, const void* images, int dtype, int n, int H, int W, float* const* taps_out, void* ws, size_t ws_bytes,
+                          ivg_stream stream) {
+  if (!p || !images || !taps_out || !ws || n <= 0 || (dtype != IVG_F32 && dtype != IVG_BF16) || !lpips_shape_ok(H, W)) return IVG_ERR_INVALID;
+  if (lpips_ws_images(ws_bytes, H, W) < 1) return IVG_ERR_CAPACITY;
+  return lpips_status(launch_lpips_features(p->cw, p->cb, images, (DType)dtype, n, H, W, taps_out, ws, ws_bytes, (hipStream_t)stream));
+}
+
+int ivg_op_lpips_head(const float* f0, const float* f1, const float* lin, int n0, int n1, int P, int C, float* out, void* ws, size_t ws_bytes,
+                      ivg_stream stream) {
+  if (!f0 || !f1 || !lin || !out || !ws || n0 <= 0 || n1 <= 0 || P <= 0 || (C != 64 && C != 128 && C != 256 && C != 512)) return IVG_ERR_INVALID;
+  if (((uintptr_t)f0 & 15) || ((uintptr_t)f1 & 15) || ((uintptr_t)lin & 15) || ((uintptr_t)ws & 7)) return IVG_ERR_INVALID;
+  if (ws_bytes < lpips_head_part_bytes(n1, P)) return IVG_ERR_CAPACITY;
+  return lpips_status(launch_lpips_head(f0, f1, lin, n0, n1, P, C, out, n0, 0, (double*)ws, (hipStream_t)stream));
+}
+
+int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const float* bias, float* Y, int n, int H, int W, ivg_stream stream) {
+  if (!images || !w || !bias || !Y || n <= 0 || H <= 0 || W <= 0 || (dtype != IVG_F32 && dtype != IVG_BF16) || ((uintptr_t)Y & 15)) return IVG_ERR_INVALID;
+  return lpips_status(launch_lpips_input_layer(images, (DType)dtype, w, bias, Y, n, H, W, (hipStream_t)stream));
+}
+
+int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream) {
+  if (!X || !Y || N <= 0 || H < 2 || W < 2 || H % 2 || W % 2 || C <= 0 || C % 4 || ((uintptr_t)X & 15) || ((uintptr_t)Y & 15)) return IVG_ERR_INVALID;
+  return lpips_status(launch_maxpool2(X, Y, N, H, W, C, (hipStream_t)stream));
+}
+
 int ivg_profile_attn_fit(ivg_engine* e, double* fixed_us, double* gbps) {
   if (!e || !fixed_us || !gbps) return IVG_ERR_INVALID;
   *fixed_us = e->attn_fit_fixed_us; *gbps = e->attn_fit_gbps;
@@ -897,6 +991,7 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "decode_attn24")) return decode_attn24_launches();
   if (name && !strcmp(name, "decode_gemm_gen3")) return decode_gemm_launches(3);
   if (name && !strcmp(name, "decode_gemm_gen2")) return decode_gemm_launches(2);
+  if (name && !strcmp(name, "lpips_trunk_images")) return lpips_trunk_images();
   return -1;
 }
 

@@ -133,4 +133,23 @@ size_t frame_metrics_ws_bytes(int n_samples, int T, int H, int W);
 int launch_frame_metrics(const void* gt, DType gt_dt, int B, int T_gt, int gt_t0, const float* pred, int n_samples, int T_pr, int pr_t0, int T,
                          int H, int W, float* rows, void* ws, hipStream_t st);
 
+// ---- lpips.hip (LPIPS, VGG-16 variant: the fourth frame metric)
+// cw / cb: the 13 convolutions' weights [Cout][kh][kw][Cin] fp32 and biases; lin: the 5 tap weight vectors.  Return values: 0, a
+// hipError_t, or -4 when the workspace holds less than one image (features) / one image pair (rows).
+bool lpips_shape_ok(int H, int W);                                  // H, W multiples of 16 (four 2 x 2 pools), >= 16
+size_t lpips_ws_bytes(int max_images, int H, int W);
+long lpips_ws_images(size_t ws_bytes, int H, int W);                // images of H x W a workspace of that size carries through the trunk
+long long lpips_trunk_images();                                     // images sent through the trunk since load (test hook)
+int launch_maxpool2(const float* X, float* Y, int N, int H, int W, int C, hipStream_t st);   // NHWC fp32, 2 x 2 / stride 2
+int launch_lpips_input_layer(const void* images, DType dt, const float* w, const float* bias, float* Y, int n, int H, int W, hipStream_t st);
+size_t lpips_head_part_bytes(int n1, int P);
+// out[(i / n0) * group_stride + i % n0] (+)= sum_c lin[c] (f0n - f1n)^2 averaged over the P pixels, image i of f1 against image i % n0 of f0
+int launch_lpips_head(const float* f0, const float* f1, const float* lin, int n0, int n1, int P, int C, float* out, long group_stride, int accumulate,
+                      double* part, hipStream_t st);
+int launch_lpips_features(const float* const* cw, const float* const* cb, const void* images, DType dt, int n, int H, int W, float* const* taps_out,
+                          void* ws, size_t ws_bytes, hipStream_t st);
+int launch_lpips_rows(const float* const* cw, const float* const* cb, const float* const* lin, const void* gt, DType gt_dt, int B, int T_gt, int gt_t0,
+                      const float* pred, int n_samples, int T_pr, int pr_t0, int T, int H, int W, float* frames, float* rows, void* ws, size_t ws_bytes,
+                      hipStream_t st);
+
 }  // namespace ivg

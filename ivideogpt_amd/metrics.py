@@ -1,6 +1,7 @@
 """Frame metrics of predicted clips on the MI355X (libivg ``ivg_frame_metrics``): the reference's ``Evaluator.forward``
-(/root/reference/ivideogpt/utils/video_metric.py:63-100) without LPIPS / FVD (external network weights): per-frame MSE,
-PSNR and SSIM (piqa semantics), mean over a trajectory's frames, best of the ``t`` samples drawn per trajectory."""
+(/root/reference/ivideogpt/utils/video_metric.py:63-100) without FVD: per-frame MSE, PSNR and SSIM (piqa semantics), mean over a
+trajectory's frames, best of the ``t`` samples drawn per trajectory; LPIPS the same way when the caller supplies the network
+weights (``Evaluator(lpips=...)``, ivideogpt_amd/lpips.py)."""
 import ctypes as C
 import threading
 
@@ -54,20 +55,39 @@ class Evaluator:
     """``Evaluator(video_1, video_2)`` of the reference's eval loop (train_gpt.py:469-472; ivideogpt/utils/video_metric.py:63-100):
     video_1 = ground truth (B, T, 3, H, W), video_2 = predictions (t * B, T, 3, H, W), sample k of trajectory b at row k * B + b.
     -> ``(mse, psnr, ssim, lpips)`` scalars like the reference's 4-tuple: per-frame metrics, mean over a trajectory's frames, best of
-    its t samples (min mse, max psnr / ssim), mean over trajectories -- computed by libivg ``ivg_frame_metrics``.  ``lpips`` is NaN:
-    LPIPS (and FVD) need network weights that do not ship with the reference (out of scope); a caller that
-    unpacks four values keeps working and sees an explicit not-a-number instead of a silently missing metric.
-    ``rows(video_1, video_2)`` returns the per-trajectory (B, 3) rows -- the payload of the multi-GPU all-gather."""
+    its t samples (min mse, max psnr / ssim, min lpips), mean over trajectories -- computed by libivg ``ivg_frame_metrics`` and
+    ``ivg_lpips_rows``.  LPIPS needs network weights that do not ship with the reference: ``lpips=`` takes an
+    ``ivideogpt_amd.lpips.LPIPS`` or the pair ``(vgg16_features_path, lin_path)``; ``max_batchsize`` then bounds the images per pass
+    through the network, as in the reference.  Without ``lpips=`` the fourth value is NaN: a caller that unpacks four values keeps
+    working and sees an explicit not-a-number instead of a silently missing metric (FVD stays out of scope).
+    ``rows(video_1, video_2)`` returns the per-trajectory (B, 3) rows -- the payload of the multi-GPU all-gather; ``rows4`` the
+    (B, 4) rows with LPIPS (needs ``lpips=``)."""
 
-    def __init__(self, i3d_path=None, max_batchsize=None):
-        self.i3d_path, self.max_batchsize = i3d_path, max_batchsize     # accepted for signature compatibility; FVD is out of scope
+    def __init__(self, i3d_path=None, max_batchsize=None, lpips=None):
+        self.i3d_path, self.max_batchsize = i3d_path, max_batchsize     # i3d_path: accepted for signature compatibility; FVD is out of scope
+        if lpips is not None and not hasattr(lpips, "frames_and_rows"):
+            from .lpips import LPIPS
+            vgg_path, lin_path = lpips
+            lpips = LPIPS.from_files(vgg_path, lin_path)
+        self.lpips = lpips
 
     def rows(self, video_1, video_2):
         return frame_metric_rows(video_1, video_2)
 
+    def lpips_rows(self, video_1, video_2):
+        if self.lpips is None:
+            raise RuntimeError("Evaluator was built without LPIPS weights (lpips=)")
+        cap = None if self.max_batchsize is None else max(2, 2 * int(self.max_batchsize))   # max_batchsize counts image PAIRS there
+        return self.lpips(video_1, video_2, max_images=cap)
+
+    def rows4(self, video_1, video_2):
+        return torch.cat([self.rows(video_1, video_2), self.lpips_rows(video_1, video_2)[:, None]], 1)
+
     def __call__(self, video_1, video_2):
         m = self.rows(video_1, video_2).mean(0)
-        return m[0], m[1], m[2], torch.full((), float("nan"), device=m.device)
+        if self.lpips is None:
+            return m[0], m[1], m[2], torch.full((), float("nan"), device=m.device)
+        return m[0], m[1], m[2], self.lpips_rows(video_1, video_2).mean()
 
     forward = __call__
 

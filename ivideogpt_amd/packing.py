@@ -76,6 +76,65 @@ def pack_subpixel(w):
     return torch.cat(out, 0).contiguous()
 
 
+# VGG-16 ``features`` indices of the 13 convolutions the LPIPS taps need, and the slice of the reference's wrapper that holds each
+# (ivideogpt/vq_model/lpips.py: slice1 = features[0:4], slice2 = [4:9], slice3 = [9:16], slice4 = [16:23], slice5 = [23:30])
+LPIPS_CONVS = ((1, 0, 3, 64), (1, 2, 64, 64), (2, 5, 64, 128), (2, 7, 128, 128), (3, 10, 128, 256), (3, 12, 256, 256), (3, 14, 256, 256),
+               (4, 17, 256, 512), (4, 19, 512, 512), (4, 21, 512, 512), (5, 24, 512, 512), (5, 26, 512, 512), (5, 28, 512, 512))
+LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)
+
+
+def lpips_key_map(keys):
+    """{canonical name: source key} for the 31 tensors ``ivg_lpips_create`` takes.  Canonical = the state-dict keys of the
+    reference's LPIPS class (``net.slice{s}.{i}.weight|bias``, ``lin{k}.model.1.weight``); also accepted: torchvision's
+    ``features.{i}.*`` (with or without a leading ``features.``-less prefix such as ``net.``) for the trunk.  KeyError names the
+    first tensor that cannot be found."""
+    keys = set(keys)
+    out = {}
+    for s, i, _, _ in LPIPS_CONVS:
+        for kind in ("weight", "bias"):
+            name = f"net.slice{s}.{i}.{kind}"
+            for cand in (name, f"features.{i}.{kind}", f"{i}.{kind}", f"net.features.{i}.{kind}"):
+                if cand in keys:
+                    out[name] = cand
+                    break
+            else:
+                raise KeyError(f"LPIPS: no tensor for {name} (nor features.{i}.{kind})")
+    for k in range(5):
+        name = f"lin{k}.model.1.weight"
+        for cand in (name, f"lin{k}.model.0.weight"):
+            if cand in keys:
+                out[name] = cand
+                break
+        else:
+            raise KeyError(f"LPIPS: no tensor for {name}")
+    return out
+
+
+def pack_lpips(sd):
+    """State dict (reference LPIPS keys, or torchvision ``features.N.*`` + ``lin{k}.model.1.weight``) -> {canonical name: fp32 CPU
+    tensor} in the layouts csrc/lpips.hip reads: conv weights [Cout, Cin, 3, 3] -> [Cout, 9 * Cin] with K ordered (kh, kw, c), biases
+    [Cout], lin weights [1, C, 1, 1] -> [C].  Shapes are checked here (ValueError)."""
+    km = lpips_key_map(sd.keys())
+    out = {}
+    for s, i, cin, cout in LPIPS_CONVS:
+        w, b = sd[km[f"net.slice{s}.{i}.weight"]].detach().float().cpu(), sd[km[f"net.slice{s}.{i}.bias"]].detach().float().cpu()
+        if tuple(w.shape) != (cout, cin, 3, 3) or tuple(b.shape) != (cout,):
+            raise ValueError(f"LPIPS: features.{i} has shapes {tuple(w.shape)} / {tuple(b.shape)}, expected {(cout, cin, 3, 3)} / {(cout,)}")
+        out[f"net.slice{s}.{i}.weight"] = _conv(w, torch.float32)
+        out[f"net.slice{s}.{i}.bias"] = b.contiguous()
+    for k, c in enumerate(LPIPS_TAP_CHANNELS):
+        v = sd[km[f"lin{k}.model.1.weight"]].detach().float().cpu()
+        if v.numel() != c:
+            raise ValueError(f"LPIPS: lin{k} has {v.numel()} weights, expected {c}")
+        out[f"lin{k}.model.1.weight"] = v.reshape(c).contiguous()
+    return out
+
+
+def unpack_lpips_conv(w_packed, cin):
+    """inverse of the conv packing: [Cout, 9 * Cin] (kh, kw, c) -> [Cout, Cin, 3, 3]"""
+    return w_packed.reshape(w_packed.shape[0], 3, 3, cin).permute(0, 3, 1, 2).contiguous()
+
+
 def pack_tokenizer(sd, cfg, device, enc_code, dec_code, dec_x3=False):
     """DF state dict of CompressiveVQModel -> {name: device tensor} for ivg_create.  dec_x3: the 3x3 convolutions of the two
     decoders also get their weights pre-split for the split-bf16 kernels (``<name>.x3``, beside the fp32 matrix other shapes use)."""

@@ -10,7 +10,9 @@ Same names, arguments and op sequence as the reference, so the loop reads like t
   * ``accelerator`` is any object with ``device / num_processes / is_main_process / is_local_main_process / gather / unwrap_model /
     log`` -- ``ivideogpt_amd.parallel.LocalAccelerator`` (torch.distributed over RCCL, no ``accelerate`` dependency) or HF's
     ``Accelerator`` itself;
-  * FVD and the LPIPS column need network weights that do not ship (``args.use_fvd`` raises; ``eval/lpips`` is NaN);
+  * FVD needs detector weights that do not ship (``args.use_fvd`` raises); the LPIPS column needs the VGG-16 / LPIPS weights:
+    with ``--lpips_vgg_path`` and ``--lpips_lin_path`` (``Evaluator(lpips=...)``) ``eval/lpips`` is computed on the device and
+    gathered like the other three, without them it is NaN;
   * GIF dumps (``imageio``) are not written; the ``eval/mse`` fallback of that branch is kept (:447-449).
 The only collectives are the all-gathers of per-sample loss / metric rows (train_gpt.py:376, 476-479).
 """
@@ -180,6 +182,8 @@ def main(argv=None):
     ap.add_argument("--eval_generate_times", type=int, default=2)
     ap.add_argument("--max_generate_batchsize", type=int, default=None)
     ap.add_argument("--max_decode_batchsize", type=int, default=None)
+    ap.add_argument("--lpips_vgg_path", default=None, help="torchvision vgg16 weights (features.N.* keys; .pth or .safetensors)")
+    ap.add_argument("--lpips_lin_path", default=None, help="the lpips package's vgg.pth (lin{k}.model.1.weight); both paths: eval/lpips is real")
     a = ap.parse_args(argv)
     rank, world, local = parallel.init_from_env()
     dev = torch.device("cuda", local)
@@ -198,7 +202,10 @@ def main(argv=None):
     batches = [torch.rand(a.batch, a.segment_length, 3, res, res, generator=g) for _ in range(a.iters * world)][rank::world]
     args = eval_args(context_length=a.context_length, segment_length=a.segment_length, eval_generate_times=a.eval_generate_times,
                      max_generate_batchsize=a.max_generate_batchsize, max_decode_batchsize=a.max_decode_batchsize)
-    logs = evaluate(args, parallel.LocalAccelerator(dev), tok, llm, batches, Evaluator(), 0)
+    if bool(a.lpips_vgg_path) != bool(a.lpips_lin_path):
+        ap.error("--lpips_vgg_path and --lpips_lin_path go together")
+    evaluator = Evaluator(lpips=(a.lpips_vgg_path, a.lpips_lin_path) if a.lpips_vgg_path else None)
+    logs = evaluate(args, parallel.LocalAccelerator(dev), tok, llm, batches, evaluator, 0)
     if logs is not None:
         print(json.dumps(logs))
     return logs
