@@ -349,6 +349,24 @@ int ivg_op_conv_x3(const ivg_igemm_args* a, const void* w_x3, int groups, const 
  * the shape. */
 int ivg_op_conv_subpixel(const ivg_igemm_args* a, int dtype, const void* w_sub, const void* w_x3, const void* w_sub_x3, void* gn_part, int groups,
                          ivg_stream stream);
+/* The LDS-halo 3x3 kernel (csrc/conv3x3.hip) alone, with every option of a production launch at once -- never the implicit-GEMM fall-back.
+ * gamma != NULL: GroupNorm(in_groups) + SiLU of the input inside the staging; ws as in ivg_op_gn_conv (statistics partials, then the
+ * (scale, shift) table float2 [Nimg][Cin] at byte offset Nimg * ceil(Hin*Win/1024) * in_groups * 16, which the caller may read back).
+ * in_part != NULL: the input's statistics come from a preceding convolution's epilogue (double2 [Nimg][in_chunks][in_groups]) instead of
+ * a pass over X.  gn_part / groups: output statistics as in ivg_op_conv_gn (NULL: none).  w_x3: split-bf16 arithmetic (dtype IVG_F32 or
+ * IVG_F32X3); w_sub / w_sub_x3: the sub-pixel weights of an upsampling convolution.  a->R, a->flags, c_* addressing as ivg_op_igemm.
+ * Returns the statistics chunks per image (0 without gn_part); IVG_ERR_INVALID, before anything is launched or written, when the
+ * kernel does not cover the call. */
+int ivg_op_conv3x3(const ivg_igemm_args* a, int dtype, const float* gamma, const float* beta, int in_groups, float eps, void* ws,
+                   const void* in_part, int in_chunks, void* gn_part, int groups, const void* w_x3, const void* w_sub, const void* w_sub_x3,
+                   ivg_stream stream);
+/* The instance and launch geometry launch_conv3x3 chooses for such a call, without launching (the launcher launches from the very same
+ * plan): gn_in != 0 stands for gamma, gn_groups > 0 for gn_part with that many groups; a->X, a->W, w_sub count for their alignment
+ * only.  out[0..14]: covered (1; 0: not covered; -1: invalid), kind (0 bf16, 1 fp32, 2 split-bf16), BN, TW, UPS, GNA, TPB2, SUBPIX,
+ * tiles_x, tiles_per_img, tiles_n, channel chunks, staged epilogue, statistics chunks per image, dynamic LDS bytes. */
+#define IVG_CONV3X3_PLAN_INTS 15
+int ivg_op_conv3x3_plan(const ivg_igemm_args* a, int dtype, int gn_in, int gn_groups, const void* w_x3, const void* w_sub,
+                        const void* w_sub_x3, int32_t* out);
 /* Tokenizer cross-attention in one pass (bf16 only; IVG_ERR_INVALID when the shape is not covered): q [M][P][C], Kp [M/F][kv][C],
  * VpT [M/F][C][kv] -> out [M][P][C], heads of C / nh channels, softmax(q k^T / sqrt(C / nh)) v per head
  * (ivideogpt/vq_model/conditional_vae.py:38-55). */

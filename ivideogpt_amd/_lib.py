@@ -110,6 +110,10 @@ EXPORTS = {
                                  C.c_void_p]),
     "ivg_op_gn_conv": (C.c_int, [C.POINTER(IvgIgemmArgs), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "ivg_op_conv_x3": (C.c_int, [C.POINTER(IvgIgemmArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "ivg_op_conv3x3": (C.c_int, [C.POINTER(IvgIgemmArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ivg_op_conv3x3_plan": (C.c_int, [C.POINTER(IvgIgemmArgs), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_int32)]),
     "ivg_op_xattn": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     "ivg_op_conv_subpixel": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ivg_op_shared_decode_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 9 + [C.c_void_p]),

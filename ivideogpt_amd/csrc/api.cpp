@@ -985,6 +985,63 @@ int ivg_op_conv_x3(const ivg_igemm_args* a, const void* w_x3, int groups, const 
   return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
 }
 
+static bool conv3x3_op_args(IgemmArgs& g, DType& dt, const ivg_igemm_args* a, int dtype, const void* w_x3, const void* w_sub, const void* w_sub_x3) {
+  if (!a || (dtype != IVG_F32 && dtype != IVG_BF16 && dtype != IVG_F32X3)) return false;
+  if (dtype == IVG_F32X3 && !w_x3) return false;
+  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
+  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
+  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
+  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
+  g.flags = a->flags; g.alpha = a->alpha; g.nb0 = a->nb0; g.nb1 = a->nb1; g.nb2 = a->nb2;
+  g.W_x3 = w_x3; g.W_sub = w_sub; g.W_sub_x3 = w_sub_x3;
+  dt = dtype == IVG_BF16 ? BF16 : F32;
+  return true;
+}
+
+int ivg_op_conv3x3(const ivg_igemm_args* a, int dtype, const float* gamma, const float* beta, int in_groups, float eps, void* ws,
+                   const void* in_part, int in_chunks, void* gn_part, int groups, const void* w_x3, const void* w_sub, const void* w_sub_x3,
+                   ivg_stream stream) {
+  // unit-test hook: ONE launch_conv3x3 with every option a production launch combines (Run::norm_conv / Run::resnet); no fall-back
+  IgemmArgs g;
+  DType dt;
+  if (!conv3x3_op_args(g, dt, a, dtype, w_x3, w_sub, w_sub_x3)) return IVG_ERR_INVALID;
+  g.gn_part = gn_part; g.gn_groups = groups;
+  char* coef = nullptr;
+  const int P = a->Hin * a->Win;
+  if (gamma) {
+    if (!beta || !ws || in_groups <= 0 || a->Cin % in_groups != 0 || P <= 0 || a->Nimg <= 0 || (in_part && in_chunks <= 0)) return IVG_ERR_INVALID;
+    coef = (char*)ws + (size_t)a->Nimg * gn_num_chunks(P) * in_groups * 16;
+    g.gn_in_coef = coef;
+  }
+  if (conv3x3_plan(g, dt).covered != 1) return IVG_ERR_INVALID;   // before the statistics kernels write the workspace
+  if (gamma) {
+    const void* part = in_part;
+    int nch = in_chunks;
+    if (!part) {
+      if (launch_groupnorm_partial(a->X, ws, a->Nimg, P, a->Cin, in_groups, dt, (hipStream_t)stream)) return IVG_ERR_HIP;
+      part = ws; nch = gn_num_chunks(P);
+    }
+    if (launch_gn_coef(part, nch, gamma, beta, a->Nimg, P, a->Cin, in_groups, eps, coef, (hipStream_t)stream)) return IVG_ERR_HIP;
+  }
+  const int rc = launch_conv3x3(g, dt, (hipStream_t)stream);
+  if (rc != 0) return rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID;
+  return g.gn_chunks;
+}
+
+int ivg_op_conv3x3_plan(const ivg_igemm_args* a, int dtype, int gn_in, int gn_groups, const void* w_x3, const void* w_sub,
+                        const void* w_sub_x3, int32_t* out) {
+  IgemmArgs g;
+  DType dt;
+  if (!out || !conv3x3_op_args(g, dt, a, dtype, w_x3, w_sub, w_sub_x3)) return IVG_ERR_INVALID;
+  if (gn_in) g.gn_in_coef = (const void*)out;        // (only its presence matters to the plan)
+  if (gn_groups > 0) { g.gn_part = (void*)out; g.gn_groups = gn_groups; }
+  const Conv3Plan p = conv3x3_plan(g, dt);
+  const int32_t v[IVG_CONV3X3_PLAN_INTS] = {p.covered, p.kind, p.bn, p.tw, p.ups, p.gna, p.tpb2, p.subpix, p.tiles_x, p.tiles_per_img, p.tiles_n,
+                                            p.chunks, p.staged, p.gn_chunks, p.lds_bytes};
+  for (int i = 0; i < IVG_CONV3X3_PLAN_INTS; ++i) out[i] = v[i];
+  return IVG_OK;
+}
+
 int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "conv3x3_subpixel")) return conv3x3_subpixel_launches();
   if (name && !strcmp(name, "gemm256x3")) return gemm256x3_launches();

@@ -566,31 +566,23 @@ __global__ __launch_bounds__(512, 4) void conv3x3_kernel(const Conv3Dev p) {
   }
 }
 
+// bytes of the main loop's LDS: the halo double buffer and the weight ring (four slots: sub-pixel instances and the two-step loop)
+static constexpr int c3_main_lds(int bn, bool ups, int tw, bool ring4) {
+  const int th = 256 / tw;
+  const int hrows = (ups ? th / 2 + 2 : th + 2) * (ups ? tw / 2 + 2 : tw + 2);
+  const int hb = (hrows * 4 + 511) / 512 * 8192;
+  return 2 * hb + (ring4 ? 4 : 3) * bn * 64;
+}
+
+// launches the instance a plan names: everything that varies at run time (tile counts, LDS layout and size) comes from the plan
 template <typename T, int BN, bool UPS, int TW, bool GNA, bool TPB2, bool X3 = false, bool SUBPIX = false>
-static int launch_c3(const Conv3Dev& d, int nimg, hipStream_t stream) {
-  constexpr int TH = 256 / TW;
-  constexpr int HROWS = (UPS ? TH / 2 + 2 : TH + 2) * (UPS ? TW / 2 + 2 : TW + 2);
-  constexpr int HB = (HROWS * 4 + 511) / 512 * 8192;
-  constexpr int MAIN = 2 * HB + (TPB2 || SUBPIX ? 4 : 3) * BN * 64;   // halo double buffer + weight ring
-  static_assert(MAIN <= 80 * 1024, "two workgroups per CU");
-  int smem = MAIN;
-  const int stage = 256 * (BN * (int)sizeof(T) + 16);   // LDS-staged epilogue tile
-  Conv3Dev dd = d;
-  dd.stage_ok = stage <= 80 * 1024;                      // keeps two workgroups per CU (fp32 x 128 channels stores directly)
-  if (dd.stage_ok && smem < stage) smem = stage;
-  // the statistics partials of the epilogue sit behind the staging tile (the main-loop buffers are dead by then)
-  if (d.gn_part) { dd.gn_off = dd.stage_ok ? ((stage + 15) & ~15) : 0; smem = std::max(smem, dd.gn_off + 2 * (BN == 16 ? 8 : 4) * BN * 4); }
-  if constexpr (GNA) { dd.coef_off = (smem + 15) & ~15; smem = dd.coef_off + 2 * (4 * Traits<T>::VEC) * 8; }
-  // IVG_CONV_CAP=1: ONE workgroup per CU -- the request is padded past half of a CU's 160 KiB, so a second workgroup of this grid
-  // never fits beside the first and half of the LDS, of the wave slots (8 of 16 per SIMD pair) and of the registers stay free for the
-  // short kernels of ANOTHER batch in flight (decode attention, decode GEMMs planned under IVG_DECODE_LDS_KB): MFMA-bound waves
-  // beside HBM- / latency-bound ones instead of a grid that holds every CU until it drains.
-  if (sw().conv_cap) smem = std::max(smem, 82 * 1024);
+static int launch_c3(const Conv3Plan& pl, const Conv3Dev& d, int nimg, hipStream_t stream) {
+  static_assert(c3_main_lds(BN, UPS, TW, TPB2 || SUBPIX) <= 80 * 1024, "two workgroups per CU");
   static DynLdsOnce once;
   auto kfn = conv3x3_kernel<T, BN, UPS, TW, GNA, TPB2, X3, SUBPIX>;
   if (hipError_t e = ensure_dyn_lds(once, (const void*)kfn, 160 * 1024); e != hipSuccess) return (int)e;
   const long blocks = (long)nimg * d.tiles_per_img * d.tiles_n * (SUBPIX ? 4 : 1);
-  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(512), smem, stream, dd);
+  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(512), pl.lds_bytes, stream, d);
   return (int)hipGetLastError();
 }
 
@@ -601,16 +593,19 @@ bool conv3x3_enabled() { return sw().conv3x3 != 0; }
 static std::atomic<long long> g_subpix_launches{0};
 long long conv3x3_subpixel_launches() { return g_subpix_launches.load(std::memory_order_relaxed); }
 
-// Returns -1 when the shape is not covered (caller falls back to the generic implicit GEMM).
-int launch_conv3x3(const IgemmArgs& a, DType dtype, hipStream_t stream) {
-  a.gn_chunks = 0;
-  if (!conv3x3_enabled()) return -1;
-  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1) return -1;
-  if (a.nb0 * a.nb1 * a.nb2 != 1 || a.alpha != 1.0f || (a.flags & (IG_GLU | IG_BIAS_M))) return -1;
+// The instance launch_conv3x3 launches for these arguments and its launch geometry: a pure host function (nothing is read through the
+// pointers; X, W and the sub-pixel weights count for their alignment, the optional ones for being there).  covered = 0: the caller
+// falls back to the generic implicit GEMM; -1: split-bf16 weights with bf16 tensors, an error.
+Conv3Plan conv3x3_plan(const IgemmArgs& a, DType dtype) {
+  Conv3Plan pl;
+  if (!conv3x3_enabled()) return pl;
+  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1) return pl;
+  if (a.nb0 * a.nb1 * a.nb2 != 1 || a.alpha != 1.0f || (a.flags & (IG_GLU | IG_BIAS_M))) return pl;
   const int ck = dtype == BF16 ? 32 : 16;
-  if (a.Cin % ck != 0 || a.ldx != a.Cin || a.N < 1) return -1;
+  // (Cin = 0 is refused: the kernel's prologue stages channel chunk 0 before it looks at the chunk count)
+  if (a.Cin < ck || a.Cin % ck != 0 || a.ldx != a.Cin || a.N < 1) return pl;
   const int Ho = a.Hout, Wo = a.Wout;
-  if (a.ups ? (Ho != 2 * a.Hin || Wo != 2 * a.Win) : (Ho != a.Hin || Wo != a.Win)) return -1;
+  if (a.ups ? (Ho != 2 * a.Hin || Wo != 2 * a.Win) : (Ho != a.Hin || Wo != a.Win)) return pl;
   // sub-pixel form of an upsampling convolution (pre-summed phase weights at hand, input tileable): tiles are laid over the INPUT
   const void* w_sub = a.W_x3 ? a.W_sub_x3 : a.W_sub;
   bool subpix = a.ups && w_sub && sw().subpixel && !a.gn_in_coef;
@@ -620,59 +615,86 @@ int launch_conv3x3(const IgemmArgs& a, DType dtype, hipStream_t stream) {
   }
   const int Ht = subpix ? a.Hin : Ho, Wt = subpix ? a.Win : Wo;   // the grid the 256-pixel tiles cover
   const int TW = Wt >= 32 ? 32 : Wt;   // 16x16 or 8x32 tiles: halo <= 10 x 34 pixels = 24 KiB per buffer
-  if (TW != 16 && TW != 32) return -1;
+  if (TW != 16 && TW != 32) return pl;
+  const bool gna = a.gn_in_coef != nullptr;
   // (16: the decoders' fused tail -- GroupNorm inside the staging, <= 16 output channels, bf16: one 16-channel fragment per wave)
-  const int bn = a.N > 64 ? 128 : ((a.N <= 16 && a.gn_in_coef && dtype == BF16 && !a.W_x3 && !a.ups) ? 16 : 64);
+  const int bn = a.N > 64 ? 128 : ((a.N <= 16 && gna && dtype == BF16 && !a.W_x3 && !a.ups) ? 16 : 64);
   const int TH = 256 / TW;
-  if (Wt % TW != 0 || Ht % TH != 0) return -1;
-  if (((uintptr_t)a.X & 15) || ((uintptr_t)a.W & 15)) return -1;
+  if (Wt % TW != 0 || Ht % TH != 0) return pl;
+  if (((uintptr_t)a.X & 15) || ((uintptr_t)a.W & 15)) return pl;
+  if (gna && a.ups) return pl;   // (the upsampling convs take un-normalised inputs)
+  if (a.W_x3 && dtype != F32) { pl.covered = -1; return pl; }
+  pl.covered = 1;
+  pl.kind = a.W_x3 ? 2 : (dtype == BF16 ? 0 : 1);
+  pl.bn = bn; pl.tw = TW; pl.gna = gna; pl.subpix = subpix;
+  pl.ups = a.ups && !subpix;   // (the sub-pixel instances run the plain geometry over the input)
+  // two steps per barrier (measured per shape, profiles/r02_conv3x3_tpb.txt: +2 ... +3.5 % on the plain convolutions, -0.8 % on the
+  // upsampling ones, whose 32-pixel-row instance also spills registers in the two-step form: those keep one step per barrier)
+  pl.tpb2 = pl.kind == 0 && !a.ups && !gna;
+  pl.tiles_x = Wt / TW; pl.tiles_per_img = pl.tiles_x * (Ht / TH);
+  pl.tiles_n = cdiv(a.N, bn);
+  pl.chunks = a.Cin / ck;
+  const bool stats = a.gn_part && a.gn_groups > 0 && a.gn_groups <= 64 && a.N % a.gn_groups == 0 && (a.c_grp <= 1);
+  if (stats) pl.gn_chunks = pl.tiles_per_img * pl.tiles_n * (subpix ? 4 : 1);
+  // ---- LDS: the main loop's buffers; the epilogue reuses them
+  const int esz = pl.kind == 0 ? 2 : 4;
+  int smem = c3_main_lds(bn, pl.ups, TW, pl.tpb2 || subpix);
+  const int stage = 256 * (bn * esz + 16);   // LDS-staged epilogue tile
+  pl.stage_ok = stage <= 80 * 1024;         // keeps two workgroups per CU (fp32 x 128 channels stores directly)
+  if (pl.stage_ok && smem < stage) smem = stage;
+  // the statistics partials of the epilogue sit behind the staging tile (the main-loop buffers are dead by then)
+  if (stats) { pl.gn_off = pl.stage_ok ? ((stage + 15) & ~15) : 0; smem = std::max(smem, pl.gn_off + 2 * (bn == 16 ? 8 : 4) * bn * 4); }
+  if (gna) { pl.coef_off = (smem + 15) & ~15; smem = pl.coef_off + 2 * (4 * (16 / esz)) * 8; }
+  // IVG_CONV_CAP=1: ONE workgroup per CU -- the request is padded past half of a CU's 160 KiB, so a second workgroup of this grid
+  // never fits beside the first and half of the LDS, of the wave slots (8 of 16 per SIMD pair) and of the registers stay free for the
+  // short kernels of ANOTHER batch in flight (decode attention, decode GEMMs planned under IVG_DECODE_LDS_KB): MFMA-bound waves
+  // beside HBM- / latency-bound ones instead of a grid that holds every CU until it drains.
+  if (sw().conv_cap) smem = std::max(smem, 82 * 1024);
+  pl.lds_bytes = smem;
+  // dense NHWC output of the element type: the kernel stages the tile through LDS and stores whole pixel rows (its `staged`)
+  pl.staged = !(a.flags & IG_OUT_F32) && a.c_ch == 1 && a.c_pix == a.N && (a.N % bn) == 0 && pl.stage_ok;
+  return pl;
+}
+
+// Returns -1 when the shape is not covered (caller falls back to the generic implicit GEMM).
+int launch_conv3x3(const IgemmArgs& a, DType dtype, hipStream_t stream) {
+  a.gn_chunks = 0;
+  const Conv3Plan pl = conv3x3_plan(a, dtype);
+  if (pl.covered == 0) return -1;
+  if (pl.covered < 0) return (int)hipErrorInvalidValue;
   Conv3Dev d;
   d.X = a.X; d.W = a.W; d.Y = a.Y; d.R = a.R; d.bias = a.bias;
-  d.H = a.Hin; d.Wd = a.Win; d.Cin = a.Cin; d.Ho = Ho; d.Wo = Wo;
-  d.tiles_x = Wt / TW; d.tiles_per_img = d.tiles_x * (Ht / TH);
+  d.H = a.Hin; d.Wd = a.Win; d.Cin = a.Cin; d.Ho = a.Hout; d.Wo = a.Wout;
+  d.tiles_x = pl.tiles_x; d.tiles_per_img = pl.tiles_per_img;
   d.N = a.N; d.ldw = a.ldw;
-  d.tiles_n = cdiv(a.N, bn);
+  d.tiles_n = pl.tiles_n;
   d.c_img = a.c_img; d.c_pix = a.c_pix; d.c_ch = a.c_ch; d.c_grp = a.c_grp > 0 ? a.c_grp : 1; d.c_grp_stride = a.c_grp_stride;
   if (a.c_grp <= 1 && a.c_grp_stride == 0) d.c_grp_stride = a.c_img;
-  d.flags = a.flags; d.stage_ok = 0;
-  d.gn_part = nullptr; d.gn_groups = 0; d.gn_off = 0;
-  d.in_coef = nullptr; d.coef_off = 0;
-  const bool gna = a.gn_in_coef != nullptr;
-  if (gna && a.ups) return -1;   // (the upsampling convs take un-normalised inputs)
-  d.in_coef = (const f32x2*)a.gn_in_coef;
-  if (a.gn_part && a.gn_groups > 0 && a.gn_groups <= 64 && a.N % a.gn_groups == 0 && (a.c_grp <= 1)) {
-    d.gn_part = (double2*)a.gn_part; d.gn_groups = a.gn_groups;
-    a.gn_chunks = d.tiles_per_img * d.tiles_n * (subpix ? 4 : 1);
-  }
-  if (subpix) {   // [phase][N][4 taps x Cin]: four 2x2 convolutions over the input (see the kernel's SUBPIX note)
-    d.W = w_sub; d.ldw = 4 * a.Cin;
+  d.flags = a.flags; d.stage_ok = pl.stage_ok;
+  d.gn_part = nullptr; d.gn_groups = 0; d.gn_off = pl.gn_off;
+  d.in_coef = (const f32x2*)a.gn_in_coef; d.coef_off = pl.coef_off;
+  if (pl.gn_chunks > 0) { d.gn_part = (double2*)a.gn_part; d.gn_groups = a.gn_groups; a.gn_chunks = pl.gn_chunks; }
+  const int nimg = a.Nimg;
+#define IVG_C3_TW(T, BNv, U, G, PR, X, S) \
+  (pl.tw == 16 ? launch_c3<T, BNv, U, 16, G, PR, X, S>(pl, d, nimg, stream) : launch_c3<T, BNv, U, 32, G, PR, X, S>(pl, d, nimg, stream))
+#define IVG_C3_BN(T, U, G, PR, X, S) (pl.bn == 128 ? IVG_C3_TW(T, 128, U, G, PR, X, S) : IVG_C3_TW(T, 64, U, G, PR, X, S))
+  if (pl.subpix) {   // [phase][N][4 taps x Cin]: four 2x2 convolutions over the input (see the kernel's SUBPIX note)
+    d.W = a.W_x3 ? a.W_sub_x3 : a.W_sub; d.ldw = 4 * a.Cin;
     g_subpix_launches.fetch_add(1, std::memory_order_relaxed);
-#define IVG_C3S_TW(T, BNv, X) (TW == 16 ? launch_c3<T, BNv, false, 16, false, false, X, true>(d, a.Nimg, stream) : launch_c3<T, BNv, false, 32, false, false, X, true>(d, a.Nimg, stream))
-#define IVG_C3S_BN(T, X) (bn == 128 ? IVG_C3S_TW(T, 128, X) : IVG_C3S_TW(T, 64, X))
-    if (a.W_x3) { if (dtype != F32) return (int)hipErrorInvalidValue; return IVG_C3S_BN(float, true); }
-    return dtype == BF16 ? IVG_C3S_BN(bf16_t, false) : IVG_C3S_BN(float, false);
-#undef IVG_C3S_BN
-#undef IVG_C3S_TW
+    if (pl.kind == 2) return IVG_C3_BN(float, false, false, false, true, true);
+    return pl.kind == 0 ? IVG_C3_BN(bf16_t, false, false, false, false, true) : IVG_C3_BN(float, false, false, false, false, true);
   }
-#define IVG_C3_TW(T, BNv, U, G, PR) (TW == 16 ? launch_c3<T, BNv, U, 16, G, PR>(d, a.Nimg, stream) : launch_c3<T, BNv, U, 32, G, PR>(d, a.Nimg, stream))
-#define IVG_C3_BN(T, U, G, PR) (bn == 128 ? IVG_C3_TW(T, 128, U, G, PR) : IVG_C3_TW(T, 64, U, G, PR))
-  if (a.W_x3) {   // split-bf16 arithmetic on fp32 tensors (the launcher swaps in the pre-split weights: same bytes per row)
-    if (dtype != F32) return (int)hipErrorInvalidValue;
+  if (pl.kind == 2) {   // split-bf16 arithmetic on fp32 tensors (the pre-split weights: same bytes per row)
     d.W = a.W_x3;
-#define IVG_C3X_TW(BNv, U, G) (TW == 16 ? launch_c3<float, BNv, U, 16, G, false, true>(d, a.Nimg, stream) : launch_c3<float, BNv, U, 32, G, false, true>(d, a.Nimg, stream))
-#define IVG_C3X_BN(U, G) (bn == 128 ? IVG_C3X_TW(128, U, G) : IVG_C3X_TW(64, U, G))
-    if (gna) return IVG_C3X_BN(false, true);
-    return a.ups ? IVG_C3X_BN(true, false) : IVG_C3X_BN(false, false);
-#undef IVG_C3X_BN
-#undef IVG_C3X_TW
+    if (pl.gna) return IVG_C3_BN(float, false, true, false, true, false);
+    return pl.ups ? IVG_C3_BN(float, true, false, false, true, false) : IVG_C3_BN(float, false, false, false, true, false);
   }
-  if (gna && bn == 16) return IVG_C3_TW(bf16_t, 16, false, true, false);
-  if (gna) return dtype == BF16 ? IVG_C3_BN(bf16_t, false, true, false) : IVG_C3_BN(float, false, true, false);
-  // (measured per shape, profiles/r02_conv3x3_tpb.txt: +2 ... +3.5 % on the plain convolutions, -0.8 % on the upsampling ones,
-  // whose 32-pixel-row instance also spills registers in the two-step form: those keep one step per barrier)
-  if (dtype == BF16 && !a.ups) return IVG_C3_BN(bf16_t, false, false, true);   // two steps per barrier
-  if (a.ups) return dtype == BF16 ? IVG_C3_BN(bf16_t, true, false, false) : IVG_C3_BN(float, true, false, false);
-  return dtype == BF16 ? IVG_C3_BN(bf16_t, false, false, false) : IVG_C3_BN(float, false, false, false);
+  if (pl.gna && pl.bn == 16) return IVG_C3_TW(bf16_t, 16, false, true, false, false, false);
+  if (pl.gna) return pl.kind == 0 ? IVG_C3_BN(bf16_t, false, true, false, false, false) : IVG_C3_BN(float, false, true, false, false, false);
+  if (pl.tpb2) return IVG_C3_BN(bf16_t, false, false, true, false, false);
+  if (pl.ups) return pl.kind == 0 ? IVG_C3_BN(bf16_t, true, false, false, false, false) : IVG_C3_BN(float, true, false, false, false, false);
+  // (the bf16 instances of this line are shadowed by the two-step branch: the plan never names them)
+  return pl.kind == 0 ? IVG_C3_BN(bf16_t, false, false, false, false, false) : IVG_C3_BN(float, false, false, false, false, false);
 #undef IVG_C3_BN
 #undef IVG_C3_TW
 }

@@ -67,6 +67,17 @@ int launch_igemm(const IgemmArgs& a, DType dtype, hipStream_t stream);
 int launch_gemm256(const IgemmArgs& a, DType dtype, hipStream_t stream);
 // LDS-halo 3x3 stride-1 kernel (conv3x3.hip); returns -1 when the shape is not covered (use launch_igemm then)
 int launch_conv3x3(const IgemmArgs& a, DType dtype, hipStream_t stream);
+// The plan launch_conv3x3 launches from (test hook ivg_op_conv3x3_plan calls the same function): conv3x3_kernel<T, bn, ups, tw, gna, tpb2,
+// X3, subpix> with T / X3 by kind (0 bf16, 1 fp32, 2 split-bf16 on fp32 tensors), over tiles_per_img (tiles_x per row) spatial tiles x
+// tiles_n channel tiles (x 4 phases: subpix) per image, `chunks` channel chunks of 32 (bf16) / 16 channels, the epilogue staged through LDS
+// or not, gn_chunks statistics chunks per image (0: none), lds_bytes of dynamic LDS.  covered: 1, 0 (launch_conv3x3 answers -1) or -1
+// (invalid arguments).  stage_ok / gn_off / coef_off: the LDS layout handed to the kernel.
+struct Conv3Plan {
+  int covered = 0, kind = 0, bn = 0, tw = 0, ups = 0, gna = 0, tpb2 = 0, subpix = 0;
+  int tiles_x = 0, tiles_per_img = 0, tiles_n = 0, chunks = 0, staged = 0, gn_chunks = 0, lds_bytes = 0;
+  int stage_ok = 0, gn_off = 0, coef_off = 0;
+};
+Conv3Plan conv3x3_plan(const IgemmArgs& a, DType dtype);
 long long gemm256x3_launches();         // gemm256.hip: launches of the 256 x 256-tile split-bf16 GEMM since load (test hook)
 long long conv3x3_subpixel_launches();   // conv3x3.hip: upsampling convolutions launched in sub-pixel form since load (test hook)
 long long decode_gemm_launches(int generation);   // dgemm.hip: decode GEMMs the dispatcher sent to generation 3 / 2 since load (test hook)

@@ -38,7 +38,8 @@ def rel_err(a, b):
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-12)).item()
 
 
-def igemm(dt, X, W, Y, R=None, bias=None, **kw):
+def igemm(dt, X, W, Y, R=None, bias=None, halo=None, **kw):
+    """halo: True / False -- assert through the plan hook that the LDS-halo 3x3 kernel (conv3x3.hip) resp. the fall-back serves the call"""
     L, l = lib()
     a = L.IvgIgemmArgs()
     a.X, a.W, a.Y, a.R, a.bias = X.data_ptr(), W.data_ptr(), Y.data_ptr(), (R.data_ptr() if R is not None else None), \
@@ -53,6 +54,10 @@ def igemm(dt, X, W, Y, R=None, bias=None, **kw):
     for name in ("sa", "sw", "sy"):
         for i, v in enumerate(kw.get(name, (0, 0, 0))):
             getattr(a, name)[i] = v
+    if halo is not None:
+        plan = (C.c_int32 * 15)()
+        assert l.ivg_op_conv3x3_plan(C.byref(a), code(dt), 0, 0, None, None, None, plan) == 0
+        assert (plan[0] == 1) == halo, f"conv3x3 plan covered = {plan[0]}, expected the {'halo kernel' if halo else 'fall-back'}"
     rc = l.ivg_op_igemm(C.byref(a), code(dt), stream())
     assert rc == 0, f"ivg_op_igemm rc={rc}"
     torch.cuda.synchronize()
@@ -98,8 +103,8 @@ def test_conv_modes(dt, mode):
     X = x.permute(0, 2, 3, 1).contiguous().to(DEV, tdt(dt))
     Wp = w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous().to(DEV, tdt(dt))
     Y = torch.full((Nb, Ho, Ho, Cout), float("nan"), device=DEV, dtype=tdt(dt))
-    igemm(dt, X, Wp, Y, None, b.to(DEV), Nimg=Nb, Hin=H, Win=H, Cin=Cin, ldx=Cin, Hout=Ho, Wout=Ho, KH=k, KW=k, stride=stride,
-          pad=pad, ups=ups, N=Cout, ldw=k * k * Cin, c_img=Ho * Ho * Cout, c_pix=Cout, flags=1)
+    igemm(dt, X, Wp, Y, None, b.to(DEV), halo=mode in ("s1", "ups"), Nimg=Nb, Hin=H, Win=H, Cin=Cin, ldx=Cin, Hout=Ho, Wout=Ho, KH=k, KW=k,
+          stride=stride, pad=pad, ups=ups, N=Cout, ldw=k * k * Cin, c_img=Ho * Ho * Cout, c_pix=Cout, flags=1)
     assert rel_err(Y.float().permute(0, 3, 1, 2), ref) < TOL[dt]
 
 
@@ -128,8 +133,8 @@ def test_conv3x3_halo_kernel(dt, H, Cin, Cout, ups, res):
     if res:
         Y.copy_(r.permute(0, 2, 3, 1))   # in-place residual: R == Y
     bd = b.to(DEV)
-    igemm(dt, X, Wp, Y, Y if res else None, bd, Nimg=Nb, Hin=H, Win=H, Cin=Cin, ldx=Cin, Hout=Ho, Wout=Ho, KH=3, KW=3, stride=1, pad=1,
-          ups=ups, N=Cout, ldw=9 * Cin, c_img=Ho * Ho * Cout, c_pix=Cout, flags=1 | (4 if res else 0))
+    igemm(dt, X, Wp, Y, Y if res else None, bd, halo=True, Nimg=Nb, Hin=H, Win=H, Cin=Cin, ldx=Cin, Hout=Ho, Wout=Ho, KH=3, KW=3, stride=1,
+          pad=1, ups=ups, N=Cout, ldw=9 * Cin, c_img=Ho * Ho * Cout, c_pix=Cout, flags=1 | (4 if res else 0))
     assert rel_err(Y.float().permute(0, 3, 1, 2), ref) < TOL[dt]
 
 
@@ -216,7 +221,7 @@ def test_conv_out_planar_video(dt):
     Wp = w.permute(0, 2, 3, 1).reshape(3, -1).contiguous().to(DEV, tdt(dt))
     clip = torch.full((B, T, 3, H, H), -7.0, device=DEV)
     Yv = clip.view(-1)[t0 * 3 * H * H:]
-    igemm(dt, X, Wp, Yv, None, b.to(DEV), Nimg=B * per, Hin=H, Win=H, Cin=Cin, ldx=Cin, Hout=H, Wout=H, KH=3, KW=3, stride=1, pad=1,
+    igemm(dt, X, Wp, Yv, None, b.to(DEV), halo=True, Nimg=B * per, Hin=H, Win=H, Cin=Cin, ldx=Cin, Hout=H, Wout=H, KH=3, KW=3, stride=1, pad=1,
           N=3, ldw=9 * Cin, c_img=3 * H * H, c_pix=1, c_ch=H * H, c_grp=per, c_grp_stride=T * 3 * H * H, flags=1 | 32)
     assert rel_err(clip[:, t0:t0 + per], ref) < TOL[dt]
     assert (clip[:, :t0] == -7.0).all()
