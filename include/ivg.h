@@ -127,6 +127,29 @@ int ivg_set_top_p(ivg_engine* e, float top_p);
 /* ivg_config.decode_lds_kb of a live engine (0 = back to the process default); takes effect at the next generate call */
 int ivg_set_decode_lds_kb(ivg_engine* e, int kb);
 
+/* K / V cache format of the transformer's rollouts.  IVG_KV_NATIVE (0, the default): the cache holds the engine's own element type
+ * (bf16, fp32, or the 24-bit planes of an IVG_F32X3 engine) -- nothing differs from an engine that never called this.
+ * IVG_KV_FP8_E4M3 (1): an opt-in, LOSSY one-byte cache for bf16 rollouts run for throughput.
+ *   Availability  llm_dtype = IVG_BF16 and head_dim 64 only; every other engine answers IVG_ERR_INVALID, before anything is
+ *                 allocated or launched, and keeps its format.
+ *   Layout        per (layer, k|v, trajectory, head) [Lmax][64] bytes, dense in that order from the start of the allocation the bf16
+ *                 cache occupies (the allocation does not change; its second half is unused).
+ *   Element       OCP e4m3fn (gfx950's native FP8; not fnuz): byte = e4m3_rne(clamp(x_bf16 / scale, -448, +448)), where x_bf16 is exactly
+ *                 the value the bf16 cache holds (the fp32 rotation rounded to bf16) and `scale` is k_scale for K, v_scale for V:
+ *                 per engine, a finite positive power of two in [2^-126, 2^126] (the division is exact), default 1.0.  The clamp is
+ *                 explicit: a finite value never becomes NaN (460 -> 448), NaN stores a NaN code.  Reference: torch on the CPU,
+ *                 (x / scale).clamp(-448, 448).to(torch.float8_e4m3fn).
+ *   Decode step   ropes q and the fed k as the bf16 step does; rounds the fed k and v to bf16, then to e4m3, BEFORE using them for
+ *                 this step's own score and output (a later step reads exactly what this one computed with); appends them at `pos`;
+ *                 out = softmax(q (k_scale K8)^T / 8) (v_scale V8) over rows [0, pos].  q and out are bf16, accumulation is fp32 in
+ *                 a fixed order, no atomics on data; bf16 x e4m3 products are exact in fp32.
+ *   Prompt pass   unchanged and bit-identical: it writes and reads bf16 K / V (a per-layer scratch), the rows are packed afterwards.
+ * Bad format, or a scale that is not such a power of two: IVG_ERR_INVALID.  Takes effect at the next generate call on every entry
+ * (ivg_generate, _shared, _forced_sdf, _continue, _embeds) and ALWAYS invalidates the kept cache: ivg_generate_continue and the
+ * reuse path of ivg_generate_embeds then behave as for a cache never filled.  ivg_config does not change. */
+enum ivg_kv_format { IVG_KV_NATIVE = 0, IVG_KV_FP8_E4M3 = 1 };
+int ivg_set_kv_format(ivg_engine* e, int format, float k_scale, float v_scale);
+
 /* CompressiveVQModel.set_context_length (compressive_vq_model.py:154-158): keeps the LAST k frames of kv_pos_emb. */
 int ivg_set_context_length(ivg_engine* e, int context_length);
 
@@ -422,6 +445,13 @@ int ivg_op_prefill_attn(void* qkv, void* kc, void* vc, void* vt, void* out, cons
 int ivg_op_kv24_pack(const float* k32, const float* v32, void* kc, void* vc, int BH, int L, int Lmax, ivg_stream stream);
 int ivg_op_decode_attn24(const float* qkv, void* kc, void* vc, float* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
                          int P, int G, int row0, ivg_stream stream);
+/* The FP8 K / V cache (ivg_set_kv_format has the format): per (trajectory, head) [Lmax][64] bytes.  ivg_op_kv8_pack: bf16 rows [0, L) of
+ * k16 / v16 [BH][Lmax][64] -> the byte rows of kc / vc (what the prefill does per layer; rows >= L are not touched; kc / vc must not
+ * overlap k16 / v16).  ivg_op_decode_attn8: one decode-attention step at cache position pos; qkv [B][3 * heads * 64] bf16, out
+ * [B][heads * 64] bf16; P / G / row0 as ivg_op_shared_decode_attn.  Scales as ivg_set_kv_format (IVG_ERR_INVALID otherwise). */
+int ivg_op_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, ivg_stream stream);
+int ivg_op_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
+                        int P, int G, int row0, float k_scale, float v_scale, ivg_stream stream);
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream);
 /* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
@@ -440,7 +470,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

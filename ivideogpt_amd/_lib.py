@@ -11,6 +11,7 @@ IVG_K_IGEMM_BF16, IVG_K_IGEMM_F32, IVG_K_CONV3X3_BF16, IVG_K_CONV3X3_F32, IVG_K_
 # igemm epilogue flags (csrc/igemm.h)
 IG_BIAS_N, IG_BIAS_M, IG_RESIDUAL, IG_SILU, IG_GLU, IG_OUT_F32 = 1, 2, 4, 8, 16, 32
 IG_RELU = 256
+IVG_KV_NATIVE, IVG_KV_FP8_E4M3 = 0, 1   # ivg_set_kv_format
 
 
 class IvgTensor(C.Structure):
@@ -62,6 +63,7 @@ EXPORTS = {
     "ivg_set_temperature": (C.c_int, [C.c_void_p, C.c_float]),
     "ivg_set_top_p": (C.c_int, [C.c_void_p, C.c_float]),
     "ivg_set_decode_lds_kb": (C.c_int, [C.c_void_p, C.c_int]),
+    "ivg_set_kv_format": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
     "ivg_set_context_length": (C.c_int, [C.c_void_p, C.c_int]),
     "ivg_tokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_encode_context": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -120,6 +122,8 @@ EXPORTS = {
     "ivg_op_prefill_attn": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]),
     "ivg_op_kv24_pack": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "ivg_op_decode_attn24": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
+    "ivg_op_kv8_pack": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_void_p]),
+    "ivg_op_decode_attn8": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_float, C.c_float, C.c_void_p]),
     "ivg_op_skinny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "ivg_op_skinny_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]),
     "ivg_op_skinny_plan": (C.c_int, [C.c_int] * 9 + [C.c_void_p] * 3 + [C.POINTER(C.c_int32)]),

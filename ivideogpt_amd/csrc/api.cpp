@@ -420,6 +420,19 @@ int ivg_set_decode_lds_kb(ivg_engine* e, int kb) {
   return IVG_OK;
 }
 
+int ivg_set_kv_format(ivg_engine* e, int format, float k_scale, float v_scale) {
+  if (!e) return IVG_ERR_INVALID;
+  if (format != IVG_KV_NATIVE && format != IVG_KV_FP8_E4M3) return e->fail(IVG_ERR_INVALID, "set_kv_format: format must be IVG_KV_NATIVE or IVG_KV_FP8_E4M3");
+  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale))
+    return e->fail(IVG_ERR_INVALID, "set_kv_format: k_scale and v_scale must be finite, positive powers of two (2^-126 .. 2^126)");
+  if (format == IVG_KV_FP8_E4M3 && (e->cfg.num_layers <= 0 || e->llm_x3 || e->llm_dt != BF16 || e->hd != 64))
+    return e->fail(IVG_ERR_INVALID, "set_kv_format: the FP8 K/V cache needs a transformer with llm_dtype IVG_BF16 and head_dim 64");
+  e->kv_format = format; e->k_scale = k_scale; e->v_scale = v_scale;
+  // whatever the cache holds was written in the previous format: a kept-cache caller starts over
+  e->kv_len = 0; e->kv_B = 0; e->snap_valid = false; e->ids_valid = false;
+  return IVG_OK;
+}
+
 int ivg_set_output_clamp(ivg_engine* e, int on) {
   if (!e) return IVG_ERR_INVALID;
   e->clamp_out = on != 0;
@@ -812,7 +825,7 @@ int ivg_profile_read(ivg_engine* e, int k, ivg_profile_stats* out) {
         }
         if (t == 0 || s == ~0ull || t < s) continue;
         const double ms = (double)(t - s) * 1e-5;   // 100 MHz wall clock -> ms
-        const double bytes = 2.0 * e->attn_prof_B * e->heads * (double)(p + 1) * e->hd * (double)e->kv_elem_bytes();
+        const double bytes = 2.0 * e->attn_prof_B * e->heads * (double)(p + 1) * e->hd * (double)(e->attn_prof_kvb > 0 ? (size_t)e->attn_prof_kvb : e->kv_elem_bytes());
         out->launches++;
         out->total_ms += ms;
         out->total_bytes += bytes;
@@ -1046,6 +1059,7 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "conv3x3_subpixel")) return conv3x3_subpixel_launches();
   if (name && !strcmp(name, "gemm256x3")) return gemm256x3_launches();
   if (name && !strcmp(name, "decode_attn24")) return decode_attn24_launches();
+  if (name && !strcmp(name, "decode_attn8")) return decode_attn8_launches();
   if (name && !strcmp(name, "decode_gemm_gen3")) return decode_gemm_launches(3);
   if (name && !strcmp(name, "decode_gemm_gen2")) return decode_gemm_launches(2);
   if (name && !strcmp(name, "lpips_trunk_images")) return lpips_trunk_images();
@@ -1158,6 +1172,26 @@ int ivg_op_decode_attn24(const float* qkv, void* kc, void* vc, float* out, const
   (void)hipStreamSynchronize(st);
   (void)hipFree(state);
   return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
+}
+
+int ivg_op_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, ivg_stream stream) {
+  if (BH <= 0 || L < 0 || L > Lmax || !kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return IVG_ERR_INVALID;
+  return launch_kv8_pack(k16, v16, kc, vc, BH, L, Lmax, k_scale, v_scale, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
+}
+
+int ivg_op_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
+                        int P, int G, int row0, float k_scale, float v_scale, ivg_stream stream) {
+  // unit-test hook of one decode-attention step over the FP8 K / V cache of a bf16 rollout (decode_attn8_kernel; G > 1: SHARED)
+  if (B <= 0 || heads <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
+  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return IVG_ERR_INVALID;
+  StepState* state = nullptr;
+  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_state_set(state, pos, 1, st);
+  if (!rc) rc = launch_decode_attn8(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, k_scale, v_scale, st, P, G, row0);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(state);
+  return rc == 0 ? IVG_OK : IVG_ERR_HIP;
 }
 
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream) {

@@ -75,7 +75,12 @@ struct ivg_engine {
   ivg::DType enc_dt, dec_dt, llm_dt;   // element types in HBM
   bool dec_x3 = false, llm_x3 = false;  // IVG_F32X3: fp32 tensors, split-bf16 matrix arithmetic on that path
   bool kv24 = false;         // x3 rollout, head_dim 64: the K / V cache keeps 24 of the 32 bits in two planes (llama_ops.hip: decode_attn24_kernel)
-  size_t kv_elem_bytes() const { return kv24 ? 3 : (llm_dt == ivg::BF16 ? 2 : 4); }
+  // ivg_set_kv_format: IVG_KV_FP8_E4M3 keeps a bf16 rollout's K / V as one e4m3 byte per element (llama_ops.hip: decode_attn8_kernel), dense
+  // [layers][2][Bmax][heads][Lmax][64] bytes from the start of the bf16 cache's allocation (which keeps its size)
+  int kv_format = IVG_KV_NATIVE;
+  float k_scale = 1.0f, v_scale = 1.0f;
+  bool kv8() const { return kv_format == IVG_KV_FP8_E4M3; }
+  size_t kv_elem_bytes() const { return kv8() ? 1 : (kv24 ? 3 : (llm_dt == ivg::BF16 ? 2 : 4)); }
   // tokenizer
   ivg::TrunkW enc, cenc, dec, cdec;
   ivg::ConvW quant_conv, post_quant_conv, quant_linear, post_quant_linear;
@@ -125,6 +130,7 @@ struct ivg_engine {
   int last_ctx = 0;                         // context length of the call that built the kept cache (action slot positions depend on it)
   int* h_flag = nullptr;                    // pinned host word for the verification result
   int attn_prof_B = 0;
+  int attn_prof_kvb = 0;                    // kv_elem_bytes() of the call the stamps belong to
   double attn_fit_fixed_us = 0, attn_fit_gbps = 0;   // line fit of the last ivg_profile_read(IVG_K_DECODE_ATTN)
 
   int fail(int code, const std::string& msg) { err = msg; return code; }

@@ -1041,6 +1041,248 @@ int launch_kv24_pack(const void* k32, const void* v32, void* kc, void* vc, int B
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ FP8 (e4m3) K / V cache of the bf16 rollout
+// Opt-in (ivg_set_kv_format, include/ivg.h has the contract): the bf16 rollout keeps one byte per cache element instead of two --
+// OCP e4m3fn, gfx950's native FP8 -- byte = e4m3_rne(clamp(x_bf16 / scale, -448, 448)) with x_bf16 the value the bf16 cache holds and
+// `scale` a per-engine power of two (one for K, one for V).  The clamp is explicit (the conversion's overflow mode is a register
+// state this code does not own) and lets NaN through: a finite value never becomes NaN, NaN stores a NaN code.  A key row is 64
+// bytes: FOUR lanes share it with one 16-byte load each (the same bytes per request and requests in flight as the bf16 instance of
+// decode_attn_kernel; 64 key groups per workgroup, 512 rows per round), decoded with v_cvt_pk_f32_fp8.  bf16 x e4m3 products are
+// exact in fp32.  Everything else is decode_attn_kernel's structure: first round of key rows before the step counter, scores ->
+// LDS, softmax statistics, weighted value sum in fixed order, SHARED row selection, stamps.  k_scale folds into the score scale,
+// v_scale into the final division.  As in decode_attn24_kernel the fed k / v are rounded -- to bf16, then to e4m3 -- BEFORE they
+// are used for this step's own score and output: a later step reads exactly what this one computed with.  The prompt pass keeps
+// bf16 K / V of one layer in scratch and packs the rows afterwards (kv8_pack_kernel).
+__device__ __forceinline__ float e4m3_clamp(float x) {
+  const float c = fminf(fmaxf(x, -448.f), 448.f);
+  return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u ? x : c;   // (fmin / fmax drop a NaN operand)
+}
+// a -> byte 0, b -> byte 1 of the selected half of `old` (v_cvt_pk_fp8_f32, RNE)
+template <bool HI> __device__ __forceinline__ int e4m3_pair(float a, float b, int old) {
+  return __builtin_amdgcn_cvt_pk_fp8_f32(e4m3_clamp(a), e4m3_clamp(b), old, HI);
+}
+__device__ __forceinline__ void row8_unpack(const Chunk16& r, float (&f)[16]) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[w], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[w], true);
+    f[4 * w] = lo[0]; f[4 * w + 1] = lo[1]; f[4 * w + 2] = hi[0]; f[4 * w + 3] = hi[1];
+  }
+}
+
+constexpr int KV8_LPK = 4, KV8_GPB = 256 / KV8_LPK, KV8_UNR = 8;   // lanes per key row, key groups per workgroup, rows in flight per lane
+
+template <bool SHARED>
+__global__ __launch_bounds__(256) void decode_attn8_kernel(const bf16_t* __restrict__ qkv, unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
+                                                           bf16_t* __restrict__ out, const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                                           int heads, int Lmax, const StepState* __restrict__ state, unsigned long long* prof,
+                                                           float k_scale, float v_scale, int sh_P, int sh_G, int sh_row0) {
+  constexpr int HD = 64, HALF = 32, LPK = KV8_LPK, GPB = KV8_GPB, UNR = KV8_UNR, VEC = 16;
+  const unsigned long long t_start = prof ? wall_clock64() : 0ull;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* sq = (float*)smem;          // [64] roped q (bf16 values) | [64] fed k | [64] fed v, both as decoded from their e4m3 codes
+  float* sk = sq + HD;
+  float* sv = sk + HD;
+  float* sc = sv + HD;               // [Lmax] scores
+  float* red = sc + Lmax;            // [GPB][HD] partial outputs
+  __shared__ float sred[8];
+  const int b = blockIdx.x / heads, h = blockIdx.x % heads;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int sub = tid % LPK, grp = tid / LPK;
+  const int H = heads * HD;
+  const float scale = 0.125f * k_scale;                            // 1 / sqrt(64), and the keys' scale: both powers of two
+  const float inv_ks = 1.0f / k_scale, inv_vs = 1.0f / v_scale;    // exact (kv8_scale_ok)
+  const long blk = (long)Lmax * HD;                                // bytes of one (trajectory, head)
+  unsigned char* kb = kc + ((long)b * heads + h) * blk;
+  unsigned char* vb = vc + ((long)b * heads + h) * blk;
+  long sh_delta = 0;
+  if constexpr (SHARED) sh_delta = ((long)((b - sh_row0) / sh_G) - b) * heads * blk;
+  const int step = GPB * UNR;
+  auto load_rows = [&](Chunk16 (&dst)[UNR], const unsigned char* base, int t0, int limit) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int t = t0 + u * GPB + grp;
+      const unsigned char* rb = base;
+      if constexpr (SHARED) rb = t < sh_P ? base + sh_delta : base;
+      const Chunk16* src = (const Chunk16*)(rb + ((unsigned)t * HD + (unsigned)sub * 16u));
+      dst[u] = t < limit ? (SHARED ? *src : __builtin_nontemporal_load(src)) : Chunk16{0u, 0u, 0u, 0u};
+    }
+  };
+  Chunk16 cur[UNR], nxt[UNR];
+  float rc = 0.f, rs = 0.f, q1 = 0.f, q2 = 0.f, k1 = 0.f, k2 = 0.f, va = 0.f, vb2 = 0.f;
+  if (tid < HALF) {
+    const bf16_t* row = qkv + (long)b * 3 * H + h * HD;
+    q1 = (float)row[tid]; q2 = (float)row[tid + HALF];
+    k1 = (float)row[H + tid]; k2 = (float)row[H + tid + HALF];
+    va = (float)row[2 * H + tid]; vb2 = (float)row[2 * H + tid + HALF];
+  }
+  load_rows(cur, kb, 0, Lmax);       // the first key rows are in flight while the step counter arrives and q is roped
+  const int pos = state->pos;
+  const int n_keys = pos + 1;
+  if (tid < HALF) { rc = cosT[(long)pos * HALF + tid]; rs = sinT[(long)pos * HALF + tid]; }
+  if (tid < HALF) {   // RoPE as decode_attn_kernel<bf16_t>; the fed k / v: bf16, then e4m3 -- used below as decoded from the stored codes
+    const bf16_t qa = (bf16_t)(q1 * rc - q2 * rs), qb = (bf16_t)(q2 * rc + q1 * rs);
+    const bf16_t ka = (bf16_t)(k1 * rc - k2 * rs), kb2 = (bf16_t)(k2 * rc + k1 * rs);
+    const int kp = e4m3_pair<false>((float)ka * inv_ks, (float)kb2 * inv_ks, 0);
+    const int vp = e4m3_pair<false>(va * inv_vs, vb2 * inv_vs, 0);
+    const f32x2 kd = __builtin_amdgcn_cvt_pk_f32_fp8(kp, false), vd = __builtin_amdgcn_cvt_pk_f32_fp8(vp, false);
+    sq[tid] = (float)qa; sq[tid + HALF] = (float)qb;
+    sk[tid] = kd[0]; sk[tid + HALF] = kd[1];
+    sv[tid] = vd[0]; sv[tid + HALF] = vd[1];
+    kb[(long)pos * HD + tid] = (unsigned char)(kp & 0xff); kb[(long)pos * HD + tid + HALF] = (unsigned char)((kp >> 8) & 0xff);
+    vb[(long)pos * HD + tid] = (unsigned char)(vp & 0xff); vb[(long)pos * HD + tid + HALF] = (unsigned char)((vp >> 8) & 0xff);
+  }
+  __syncthreads();
+  float qf[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) qf[j] = sq[sub * VEC + j];
+  auto scores = [&](Chunk16 (&rows)[UNR], int t0) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int t = t0 + u * GPB + grp;
+      float kf[VEC];
+      row8_unpack(rows[u], kf);
+      float d = 0.f;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) d = fmaf(qf[j], kf[j], d);
+      d = group_sum(d, LPK);
+      if (t < pos && sub == 0) sc[t] = d * scale;
+    }
+  };
+  {
+    int t0 = 0;
+    bool in_nxt = false;
+    while (t0 < pos) {
+      if (t0 + step < pos) load_rows(nxt, kb, t0 + step, pos); else load_rows(nxt, vb, 0, pos);
+      scores(cur, t0);
+      t0 += step;
+      in_nxt = true;
+      if (t0 >= pos) break;
+      if (t0 + step < pos) load_rows(cur, kb, t0 + step, pos); else load_rows(cur, vb, 0, pos);
+      scores(nxt, t0);
+      t0 += step;
+      in_nxt = false;
+    }
+    if (in_nxt) {
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) cur[u] = nxt[u];
+    }
+  }
+  if (grp == 0) {
+    float d = 0.f;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) d = fmaf(qf[j], sk[sub * VEC + j], d);
+    d = group_sum(d, LPK);
+    if (sub == 0) sc[pos] = d * scale;
+  }
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int t = tid; t < n_keys; t += 256) mx = fmaxf(mx, sc[t]);
+  mx = wave_max(mx);
+  if (lane == 0) sred[wv] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
+  float sum = 0.f;
+  for (int t = tid; t < n_keys; t += 256) { const float e = expf(sc[t] - mx); sc[t] = e; sum += e; }
+  sum = wave_sum(sum);
+  if (lane == 0) sred[4 + wv] = sum;
+  __syncthreads();
+  sum = (sred[4] + sred[5]) + (sred[6] + sred[7]);
+  float of[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) of[j] = 0.f;
+  auto weighted = [&](Chunk16 (&rows)[UNR], int t0) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int t = t0 + u * GPB + grp;
+      if (t < pos) {
+        float vf[VEC];
+        row8_unpack(rows[u], vf);
+        const float pw = sc[t];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) of[j] = fmaf(pw, vf[j], of[j]);
+      }
+    }
+  };
+  for (int t0 = 0; t0 < pos; t0 += 2 * step) {
+    if (t0 + step < pos) load_rows(nxt, vb, t0 + step, pos);
+    weighted(cur, t0);
+    if (t0 + step >= pos) break;
+    if (t0 + 2 * step < pos) load_rows(cur, vb, t0 + 2 * step, pos);
+    weighted(nxt, t0 + step);
+  }
+  if (grp == 0) {
+    const float pw = sc[pos];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) of[j] = fmaf(pw, sv[sub * VEC + j], of[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) red[grp * HD + sub * VEC + j] = of[j];
+  __syncthreads();
+  if (tid < HD) {
+    float a = 0.f;
+    for (int g = 0; g < GPB; ++g) a += red[g * HD + tid];
+    out[(long)b * H + h * HD + tid] = (bf16_t)(a / sum * v_scale);   // (the product with a power of two is exact)
+  }
+  if (prof && tid == 0) {
+    unsigned long long* slot = prof + (size_t)((blockIdx.x * 7 + blockIdx.y) % IVG_ATTN_PROF_SLOTS) * 2 * Lmax;
+    atomicMax(slot + pos, ~t_start);
+    atomicMax(slot + Lmax + pos, (unsigned long long)wall_clock64());
+  }
+}
+
+bool kv8_scale_ok(float s) {
+  int ex = 0;
+  return std::isnormal(s) && s > 0.f && frexpf(s, &ex) == 0.5f && std::isnormal(1.0f / s);
+}
+
+static std::atomic<long long> g_attn8_launches{0};
+long long decode_attn8_launches() { return g_attn8_launches.load(); }
+
+int launch_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cosT, const float* sinT, int B, int heads, int Lmax,
+                        const StepState* state, unsigned long long* prof, float k_scale, float v_scale, hipStream_t st, int sh_P, int sh_G,
+                        int sh_row0) {
+  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return (int)hipErrorInvalidValue;
+  const size_t smem = (size_t)(3 * 64 + Lmax + KV8_GPB * 64) * sizeof(float);
+  dim3 g(B * heads);
+  if (sh_G > 1) {
+    if (sh_P < 0 || sh_row0 > 0) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_attn8_kernel<true>, g, dim3(256), smem, st, (const bf16_t*)qkv, (unsigned char*)kc, (unsigned char*)vc, (bf16_t*)out, cosT,
+                       sinT, heads, Lmax, state, prof, k_scale, v_scale, sh_P, sh_G, sh_row0);
+  } else {
+    hipLaunchKernelGGL(decode_attn8_kernel<false>, g, dim3(256), smem, st, (const bf16_t*)qkv, (unsigned char*)kc, (unsigned char*)vc, (bf16_t*)out, cosT,
+                       sinT, heads, Lmax, state, prof, k_scale, v_scale, 0, 1, 0);
+  }
+  g_attn8_launches.fetch_add(1, std::memory_order_relaxed);
+  return (int)hipGetLastError();
+}
+
+// bf16 rows [0, L) of K / V ([B * heads][Lmax][64], what rope_kv wrote for the prompt into scratch) -> the byte rows of the cache.
+// Never in place: byte row t overlaps bf16 row t / 2 of the same block.
+__global__ __launch_bounds__(256) void kv8_pack_kernel(const bf16_t* __restrict__ k16, const bf16_t* __restrict__ v16, unsigned char* __restrict__ kc,
+                                                       unsigned char* __restrict__ vc, int L, int Lmax, float inv_ks, float inv_vs) {
+  const int bh = blockIdx.y, tid = threadIdx.x;
+  const int row = blockIdx.x * 32 + (tid >> 3), sub = tid & 7;
+  if (row >= L) return;
+  const long off = ((long)bh * Lmax + row) * 64 + sub * 8;
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    const bf16x8 x = *(const bf16x8*)((which ? v16 : k16) + off);
+    const float inv = which ? inv_vs : inv_ks;
+    int lo = e4m3_pair<false>((float)x[0] * inv, (float)x[1] * inv, 0), hi = e4m3_pair<false>((float)x[4] * inv, (float)x[5] * inv, 0);
+    lo = e4m3_pair<true>((float)x[2] * inv, (float)x[3] * inv, lo);
+    hi = e4m3_pair<true>((float)x[6] * inv, (float)x[7] * inv, hi);
+    *(uint2*)((which ? vc : kc) + off) = uint2{(unsigned)lo, (unsigned)hi};
+  }
+}
+
+int launch_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, hipStream_t st) {
+  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return (int)hipErrorInvalidValue;
+  if (L <= 0) return 0;
+  hipLaunchKernelGGL(kv8_pack_kernel, dim3((unsigned)cdiv(L, 32), (unsigned)BH), dim3(256), 0, st, (const bf16_t*)k16, (const bf16_t*)v16,
+                     (unsigned char*)kc, (unsigned char*)vc, L, Lmax, 1.0f / k_scale, 1.0f / v_scale);
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ sampling
 // One workgroup per trajectory.  Restates HF TopKLogitsWarper(top_k) + softmax + one draw as an
 // explicit-uniform inverse CDF over the kept tokens in ascending id order (oracle/llama.py

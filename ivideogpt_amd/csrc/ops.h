@@ -89,6 +89,15 @@ int launch_decode_attn24(const void* qkv, void* kc, void* vc, void* out, const f
                          const StepState* state, unsigned long long* prof, hipStream_t st, int sh_P = 0, int sh_G = 1, int sh_row0 = 0);
 long long decode_attn24_launches();   // launches over the 24-bit cache since load (test hook: which cache format an x3 engine really ran)
 int launch_kv24_pack(const void* k32, const void* v32, void* kc, void* vc, int BH, int L, int Lmax, hipStream_t st);
+// FP8 (OCP e4m3fn) K / V cache of a bf16 rollout, opt-in (ivg_set_kv_format; llama_ops.hip): per (trajectory, head) [Lmax][64] bytes,
+// byte = e4m3_rne(clamp(x_bf16 / scale, -448, 448)); head_dim 64, bf16 q / output.  launch_kv8_pack: bf16 rows [0, L) of [BH][Lmax][64]
+// K and V (the prefill's scratch; must not overlap the byte rows) -> the cache
+int launch_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cosT, const float* sinT, int B, int heads, int Lmax,
+                        const StepState* state, unsigned long long* prof, float k_scale, float v_scale, hipStream_t st, int sh_P = 0, int sh_G = 1,
+                        int sh_row0 = 0);
+long long decode_attn8_launches();    // launches over the FP8 cache since load (test hook)
+int launch_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, hipStream_t st);
+bool kv8_scale_ok(float s);           // a finite, positive power of two whose reciprocal is a normal float (2^-126 .. 2^126)
 int launch_expand_prompt_rows(const int64_t* prompts, long pstride, int64_t* ids, long ids_ld, int rows, int L, int G, int b0, hipStream_t st);
 // token decision + embedding of the decided token (+ action embedding on forced sdf slots) + state advance
 struct SampleArgs {

@@ -99,6 +99,11 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
   const bool kv24 = e->kv24;
   char* k32 = kv24 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 4) : nullptr;
   char* v32 = kv24 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 4) : nullptr;
+  // FP8 cache (ivg_set_kv_format): the prompt pass itself is untouched -- it writes and reads one layer's bf16 K / V here instead of
+  // the cache (never packed in place: byte row t overlaps bf16 row t / 2), kv8_pack_kernel then stores the rows as e4m3
+  const bool kv8 = e->kv8();
+  char* k16 = kv8 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 2) : nullptr;
+  char* v16 = kv8 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 2) : nullptr;
   char* Pm = flash ? nullptr : (char*)e->ws.alloc((size_t)B * heads * L * Lp * esz(dt));
   if (!planning) {
     e->kv_len = 0; e->kv_B = 0;   // the cache rows are about to be overwritten (ivg_generate re-validates them at its end)
@@ -119,10 +124,11 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
     if (!planning) CK(launch_add_rmsnorm(x, H, e->ones, xn, (int)M, H, c.rms_norm_eps, dt, st));
     ConvW wq; wq.w = w.wqkv; wq.cin = H; wq.cout = 3 * H;
     IVG_TRY(linear(dt, xn, M, wq, qkv, nullptr, 0, 0));
-    char* kl = kv24 ? k32 : kc_ptr(e, l, 0);
+    char* kl = kv24 ? k32 : (kv8 ? k16 : kc_ptr(e, l, 0));
     if (!planning) {
-      CK(launch_rope_kv(qkv, kl, kv24 ? v32 : kc_ptr(e, l, 1), e->vt, Lp, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, 0, dt, st));
+      CK(launch_rope_kv(qkv, kl, kv24 ? v32 : (kv8 ? v16 : kc_ptr(e, l, 1)), e->vt, Lp, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, 0, dt, st));
       if (kv24) CK(launch_kv24_pack(k32, v32, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, st));
+      if (kv8) CK(launch_kv8_pack(k16, v16, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, e->k_scale, e->v_scale, st));
     }
     if (flash) {
       if (!planning) CK(launch_flash_prefill(qkv, kl, e->vt, attn, B, L, Lp, heads, hd, Lmax, dt, st));
@@ -288,7 +294,10 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
     gprof(cur[0], 4 * l + 0);
     CK(launch_skinny(cur[0], dt, st));
     unsigned long long* aprof = e->attn_prof_on ? e->attn_prof + (size_t)l * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax : nullptr;
-    if (e->kv24)
+    if (e->kv8())
+      CK(launch_decode_attn8(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->Lmax, state,
+                             aprof, e->k_scale, e->v_scale, st, g.sh_P, g.sh_G, g.sh_row0));
+    else if (e->kv24)
       CK(launch_decode_attn24(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->Lmax, state,
                               aprof, st, g.sh_P, g.sh_G, g.sh_row0));
     else
@@ -347,7 +356,7 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     }
     if (e->attn_prof_on) {  // fresh launch windows for this call: every stamp slot back to 0 (= not stamped)
       CK((int)hipMemsetAsync(e->attn_prof, 0, (size_t)c.num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8, st));
-      e->attn_prof_B = Bc;
+      e->attn_prof_B = Bc; e->attn_prof_kvb = (int)e->kv_elem_bytes();
     }
     if (shared) {   // every trajectory starts from a copy of its group's prompt; groups g_lo .. g_hi have rows in this chunk
       const int g_lo = b0 / group, g_hi = (b0 + Bc - 1) / group;
@@ -397,11 +406,14 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     // engine's LDS budget and the generation of the switch table, whose kernel-selection switches a replayed graph would otherwise keep ignoring)
     uint32_t t_bits; memcpy(&t_bits, &e->temperature, 4);
     uint32_t p_bits; memcpy(&p_bits, &e->top_p, 4);
+    uint32_t ks_bits; memcpy(&ks_bits, &e->k_scale, 4);
+    uint32_t vs_bits; memcpy(&vs_bits, &e->v_scale, 4);
     const std::string key = std::to_string(Bc) + ":" + std::to_string(t_bits) + ":" + std::to_string(p_bits) + ":" + std::to_string(e->decode_lds_kb) + ":" + std::to_string(switches_generation()) +
                             ":" + (uniforms ? "s" : "g") + ":" + std::to_string(top_k) + ":" +
                             std::to_string(sa.forced_period) + ":" + std::to_string(ctx) + ":" + std::to_string(act_T) + ":" +
                             std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)
-                            (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "");
+                            (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "") +
+                            (e->kv8() ? ":kv8:" + std::to_string(ks_bits) + ":" + std::to_string(vs_bits) : "");   // (the cache format and its scales: kernel and arguments)
     // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
     // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
     auto reward = [&]() -> int {

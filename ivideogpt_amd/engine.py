@@ -142,6 +142,12 @@ class Engine:
         self.check(self.lib.ivg_set_decode_lds_kb(self.h, int(kb or 0)), "set_decode_lds_kb")
         return self
 
+    def set_kv_format(self, fmt, k_scale=1.0, v_scale=1.0):
+        """``ivg_set_kv_format``: K / V cache format of the rollouts (``_lib.IVG_KV_NATIVE`` / ``IVG_KV_FP8_E4M3``) and its scales; takes
+        effect at the next generate call and invalidates the kept cache."""
+        self.check(self.lib.ivg_set_kv_format(self.h, int(fmt), float(k_scale), float(v_scale)), "set_kv_format")
+        return self
+
     def set_context_length(self, k):
         self.check(self.lib.ivg_set_context_length(self.h, int(k)), "set_context_length")
 

@@ -12,13 +12,15 @@ engine draws by inverse CDF from explicit uniforms (``torch.rand`` on the model'
 supplied generator) over the top-k kept tokens in ascending id order; ``do_sample=False`` is greedy argmax.
 All compute is in libivg (HIP); this file is tensor plumbing and checkpoint I/O.
 """
+import math
 from types import SimpleNamespace
 
 import torch
 
+from . import _lib
 from . import weights as W
 from .engine import Engine
-from .packing import dtype_code, pack_llama, torch_dtype
+from .packing import dtype_code, is_x3, pack_llama, torch_dtype
 
 
 class _Embedding:
@@ -118,10 +120,35 @@ def _top_p_of(top_p, do_sample):
     return p
 
 
+KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
+
+
+def _kv_cache_setting(name, k_scale, v_scale, dtype, cfg):
+    """The (name, k_scale, v_scale) of ``kv_cache_dtype`` / ``set_kv_cache_dtype``, checked before any engine work (include/ivg.h
+    ivg_set_kv_format): ValueError for an unknown name, a scale that is not a finite positive power of two in [2^-126, 2^126], or
+    ``"fp8_e4m3"`` on a model that is not bf16 with head_dim 64."""
+    if name not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, not {name!r}")
+    scales = []
+    for what, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        try:
+            f = float(s)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not (math.isfinite(f) and f > 0.0 and math.frexp(f)[0] == 0.5 and 2.0 ** -126 <= f <= 2.0 ** 126):
+            raise ValueError(f"{what} must be a finite, positive power of two in [2^-126, 2^126], not {s!r}")
+        scales.append(f)
+    if name == "fp8_e4m3":
+        hd = cfg["hidden_size"] // max(1, cfg["num_attention_heads"])
+        if is_x3(dtype) or dtype_code(dtype) != _lib.IVG_BF16 or hd != 64:
+            raise ValueError(f"kv_cache_dtype='fp8_e4m3' needs a bf16 model with head_dim 64 (this one: dtype {dtype!r}, head_dim {hd})")
+    return name, scales[0], scales[1]
+
+
 class LlamaForCausalLM:
     supports_shared_context = True   # generate / detokenize accept shared_context= (libivg ivg_generate_shared / ivg_detokenize_shared)
     def __init__(self, config, state_dict=None, dtype="bf16", prefix="", action_dim=None, reward_prediction=False, decode_lds_kb=0,
-                 max_seq=0):
+                 max_seq=0, kv_cache_dtype="auto"):
         self._decode_lds_kb = int(decode_lds_kb or 0)   # launch policy of THIS model's engine (set_decode_lds_kb)
         self._max_seq = int(max_seq or 0)               # KV-cache length (0: max_position_embeddings; never more, ivg_config.max_seq)
         self._cfg = dict(W.LLAMA_SMALL)
@@ -134,6 +161,7 @@ class LlamaForCausalLM:
         self.torch_dtype = torch_dtype(dtype_code(dtype))
         self.device = torch.device("cpu")
         self._engine = None
+        self._kv = _kv_cache_setting(kv_cache_dtype, 1.0, 1.0, dtype, self._cfg)   # K / V cache format of this model's engines (set_kv_cache_dtype)
         # the packed weights in HBM, kept across engine rebuilds and shared by replicas.  Validity is an explicit version counter
         # bumped by every load_state_dict (never id(dict): a reloaded or in-place mutated dict keeps its id, a collected one's is reused)
         self._packed, self._packed_key, self._sd_version = None, None, 0
@@ -159,6 +187,7 @@ class LlamaForCausalLM:
             raise RuntimeError("replica(): call .to('cuda') first")
         r = LlamaForCausalLM(self._cfg, self._sd, dtype=self.dtype, prefix=self._prefix, action_dim=self._action_dim,
                              reward_prediction=self._reward, decode_lds_kb=self._decode_lds_kb, max_seq=self._max_seq)
+        r._kv = self._kv
         r.device = self.device
         r._sd_version = self._sd_version
         if hasattr(self, "_wrapper_heads"):
@@ -173,13 +202,15 @@ class LlamaForCausalLM:
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder="transformer", low_cpu_mem_usage=False, dtype="bf16",
-                        **unused):
+                        kv_cache_dtype="auto", **unused):
+        if kv_cache_dtype not in KV_CACHE_DTYPES:   # (before the checkpoint is read; the dtype / head_dim checks follow in __init__)
+            raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, not {kv_cache_dtype!r}")
         cfg, sd = W.load_transformer_checkpoint(pretrained_model_name_or_path, subfolder)
         W.validate_state_dict(sd, W.llama_param_shapes(cfg), "transformer")
-        return cls(cfg, sd, dtype=dtype)
+        return cls(cfg, sd, dtype=dtype, kv_cache_dtype=kv_cache_dtype)
 
     @classmethod
-    def from_config(cls, config, seed=None, dtype="bf16", **hf_kwargs):
+    def from_config(cls, config, seed=None, dtype="bf16", kv_cache_dtype="auto", **hf_kwargs):
         """``AutoModelForCausalLM.from_config(config)`` (mbrl/video_predictor.py:72, train_gpt.py:593): ``config`` = a dict, an object
         with the HF field names, or a path to a ``config.json`` / its directory (what ``AutoConfig.from_pretrained`` takes).
         seed = None: no weights yet (load_state_dict follows); otherwise seeded random weights in the checkpoint schema.
@@ -191,8 +222,9 @@ class LlamaForCausalLM:
             config = W.load_llama_config(config)
         cfg = dict(W.LLAMA_SMALL)
         cfg.update({k: v for k, v in (vars(config) if not isinstance(config, dict) else config).items() if k in cfg})
+        _kv_cache_setting(kv_cache_dtype, 1.0, 1.0, dtype, cfg)   # (a bad setting raises before any weights are drawn)
         sd = W.random_llama_state_dict(cfg, seed) if seed is not None else None
-        return cls(cfg, sd, dtype=dtype)
+        return cls(cfg, sd, dtype=dtype, kv_cache_dtype=kv_cache_dtype)
 
     def state_dict(self):
         return self._sd
@@ -250,7 +282,22 @@ class LlamaForCausalLM:
         self._engine = Engine(self.device, self._packed_weights(), llm_cfg=self._cfg, action_dim=self._action_dim or 0,
                               reward_head=self._reward, llm_dtype=self.dtype, max_batch=cap_b, max_frames=cap_t,
                               decode_lds_kb=self._decode_lds_kb, max_seq=self._max_seq)
+        if self._kv[0] != "auto":
+            self._engine.set_kv_format(_lib.IVG_KV_FP8_E4M3, self._kv[1], self._kv[2])
         return self._engine
+
+    def set_kv_cache_dtype(self, name, k_scale=1.0, v_scale=1.0):
+        """K / V cache format of this model's rollouts (include/ivg.h ivg_set_kv_format).  ``"auto"``: the model's own element type, the
+        default.  ``"fp8_e4m3"`` (bf16 models with head_dim 64): an opt-in, lossy one-byte cache, element = e4m3(clamp(x / scale, +-448))
+        with ``k_scale`` / ``v_scale`` powers of two.  ValueError, before any engine work, for a wrong name, model dtype or scale.  Applies
+        to the live engine from its next generate call on -- whose kept KV cache it invalidates (``reuse_cache`` / ``use_cache`` callers
+        start over) -- and to every engine this model builds later."""
+        kv = _kv_cache_setting(name, k_scale, v_scale, self.dtype, self._cfg)
+        if kv != self._kv:
+            self._kv = kv
+            if self._engine is not None:
+                self._engine.set_kv_format(_lib.IVG_KV_NATIVE if kv[0] == "auto" else _lib.IVG_KV_FP8_E4M3, kv[1], kv[2])
+        return self
 
     # LDS budget (KiB) of a decode-step GEMM workgroup for a model whose batch shares the GPU with other batches in flight (bench.py
     # --lanes, INTEGRATION.md "streams"): with a whole CU's LDS per workgroup (the default, fastest for one batch alone) the decode
@@ -420,6 +467,10 @@ class HeadModelWithAction:
 
     def set_decode_lds_kb(self, kb):
         self.llm.set_decode_lds_kb(kb)
+        return self
+
+    def set_kv_cache_dtype(self, name, k_scale=1.0, v_scale=1.0):
+        self.llm.set_kv_cache_dtype(name, k_scale, v_scale)
         return self
 
     def replica(self):
