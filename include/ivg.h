@@ -150,6 +150,37 @@ int ivg_set_decode_lds_kb(ivg_engine* e, int kb);
 enum ivg_kv_format { IVG_KV_NATIVE = 0, IVG_KV_FP8_E4M3 = 1 };
 int ivg_set_kv_format(ivg_engine* e, int format, float k_scale, float v_scale);
 
+/* Per-layer, per-head scales of the FP8 K / V cache, and their calibration on the device.
+ * ivg_set_kv_scales   `scales` (host) is [num_layers][2 (k, v)][heads]: the element rule of ivg_set_kv_format with `scale` = the entry of the
+ *     element's (layer, tensor, head), everything else unchanged (a decode step's output is softmax(q (ks[h] K8)^T / 8) (vs[h] V8)).
+ *     Every entry must be such a power of two, and the engine one the FP8 format is available on; otherwise IVG_ERR_INVALID and
+ *     nothing changes.  The format itself does not change: the table is in force while the format is IVG_KV_FP8_E4M3, until the next
+ *     ivg_set_kv_format (any format: it sets uniform scales and drops the table).  Takes effect at the next generate call and ALWAYS
+ *     invalidates the kept cache, as ivg_set_kv_format does.  SYNCHRONISES the device (launches still running may read the table it
+ *     rewrites).  Step graphs are keyed by a counter every call of either setter bumps: none is replayed across a change.
+ *     Shared-context rollouts use the table like the plain ones; every engine (lane, replica) owns its table.
+ * ivg_get_kv_scales   the [num_layers][2][heads] scales in force (host), expanded from k_scale / v_scale when no table is set.
+ * ivg_kv_calibrate    observes K and V.  Runs the teacher-forced prompt pass (the one behind ivg_logits; actions added on every sdf slot;
+ *     no lm_head, no sampling) over ids (B, L), B in chunks of the KV cache's batch, and after each layer's RoPE folds max |x| over
+ *     trajectories, positions [0, L) and elements of that layer's bf16 K and V into an engine-owned table amax[layer][k|v][head].
+ *     The maximum is taken on integer bit patterns (order-independent; NaN ranks above Inf above every finite value, so a non-finite
+ *     K / V is never hidden).  Feed whole ground-truth token rows: the pass then sees the positions a rollout appends, not only the
+ *     context.  Calls accumulate until ivg_kv_calibration_reset (which synchronises the device and zeroes the table).  Enqueued on
+ *     `stream`, no synchronisation; overwrites cache rows, so the kept cache is invalidated.  Works in either cache format and changes
+ *     neither format nor scales.  Engines the FP8 format is not available on: IVG_ERR_INVALID.
+ * ivg_kv_calibration_finish   SYNCHRONISES the stream of the last ivg_kv_calibrate call (as ivg_profile_read synchronises), reads amax,
+ *     derives scale = 2^(p + headroom_log2) clamped to [2^-126, 2^126], where amax = m 2^e with m in [0.5, 1) and p = e - 9 if
+ *     m <= 0.875, else e - 8 (2^p is the smallest power of two s with amax / s <= 448; integer arithmetic, no logarithm; amax = 0
+ *     gives 1.0), and installs the table as ivg_set_kv_scales would.  amax_out / scales_out (host, [num_layers][2][heads], or NULL)
+ *     receive what was observed / installed.  A NaN or Inf amax (ivg_last_error names layer, tensor and head) or headroom_log2
+ *     outside [0, 8]: IVG_ERR_INVALID, nothing installed.  One bit of headroom (the Python default) costs a floating-point format no
+ *     mantissa, only range at the subnormal end, and covers rows a rollout appends that the calibration set did not contain. */
+int ivg_set_kv_scales(ivg_engine* e, const float* scales);
+int ivg_get_kv_scales(ivg_engine* e, float* scales_out);
+int ivg_kv_calibrate(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, const float* actions, int act_T, int ctx, ivg_stream stream);
+int ivg_kv_calibration_reset(ivg_engine* e);
+int ivg_kv_calibration_finish(ivg_engine* e, int headroom_log2, float* amax_out, float* scales_out);
+
 /* CompressiveVQModel.set_context_length (compressive_vq_model.py:154-158): keeps the LAST k frames of kv_pos_emb. */
 int ivg_set_context_length(ivg_engine* e, int context_length);
 
@@ -452,6 +483,14 @@ int ivg_op_decode_attn24(const float* qkv, void* kc, void* vc, float* out, const
 int ivg_op_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, ivg_stream stream);
 int ivg_op_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
                         int P, int G, int row0, float k_scale, float v_scale, ivg_stream stream);
+/* the same two with per-head scales (ivg_set_kv_scales): k_scales / v_scales are DEVICE arrays [heads] of one layer, BH = B * heads;
+ * ivg_op_kv_absmax: the calibration's observation -- out [2][heads] (device, fp32 bit patterns, k then v) = max(out, max |x| per head over
+ * rows [0, L) of bf16 k16 / v16 [B * heads][Lmax][64]); rows >= L are never read; the caller zeroes `out` to start over */
+int ivg_op_kv8_pack_heads(const void* k16, const void* v16, void* kc, void* vc, int B, int heads, int L, int Lmax, const float* k_scales,
+                          const float* v_scales, ivg_stream stream);
+int ivg_op_decode_attn8_heads(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
+                              int P, int G, int row0, const float* k_scales, const float* v_scales, ivg_stream stream);
+int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, uint32_t* out, ivg_stream stream);
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream);
 /* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,

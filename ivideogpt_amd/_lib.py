@@ -64,6 +64,11 @@ EXPORTS = {
     "ivg_set_top_p": (C.c_int, [C.c_void_p, C.c_float]),
     "ivg_set_decode_lds_kb": (C.c_int, [C.c_void_p, C.c_int]),
     "ivg_set_kv_format": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "ivg_set_kv_scales": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ivg_get_kv_scales": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ivg_kv_calibrate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ivg_kv_calibration_reset": (C.c_int, [C.c_void_p]),
+    "ivg_kv_calibration_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ivg_set_context_length": (C.c_int, [C.c_void_p, C.c_int]),
     "ivg_tokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_encode_context": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -124,6 +129,9 @@ EXPORTS = {
     "ivg_op_decode_attn24": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
     "ivg_op_kv8_pack": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_void_p]),
     "ivg_op_decode_attn8": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_float, C.c_float, C.c_void_p]),
+    "ivg_op_kv8_pack_heads": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 3),
+    "ivg_op_decode_attn8_heads": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p] * 3),
+    "ivg_op_kv_absmax": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 2),
     "ivg_op_skinny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "ivg_op_skinny_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]),
     "ivg_op_skinny_plan": (C.c_int, [C.c_int] * 9 + [C.c_void_p] * 3 + [C.POINTER(C.c_int32)]),

@@ -280,6 +280,8 @@ void ivg_destroy(ivg_engine* e) {
   if (e->gen_buf) (void)hipFree(e->gen_buf);
   if (e->ones) (void)hipFree(e->ones);
   if (e->attn_prof) (void)hipFree(e->attn_prof);
+  if (e->kv_scales_dev) (void)hipFree(e->kv_scales_dev);
+  if (e->kv_amax) (void)hipFree(e->kv_amax);
   if (e->emb_snap) (void)hipFree(e->emb_snap);
   if (e->gemm_prof) (void)hipFree(e->gemm_prof);
   if (e->h_flag) (void)hipHostFree(e->h_flag);
@@ -354,6 +356,12 @@ int ivg_create(const ivg_config* cfg, const ivg_tensor* weights, int n_weights, 
     }
     if (hipMalloc((void**)&e->attn_prof, (size_t)cfg->num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8) != hipSuccess) { e->err = "hipMalloc failed"; return bail(IVG_ERR_HIP); }
     (void)hipMemset(e->attn_prof, 0, (size_t)cfg->num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8);
+    if (!e->llm_x3 && e->llm_dt == BF16 && e->hd == 64) {   // engines the FP8 cache is for: its scale table and the calibration's observations
+      const size_t tb = (size_t)cfg->num_layers * 2 * e->heads * 4;
+      if (hipMalloc((void**)&e->kv_scales_dev, tb) != hipSuccess || hipMalloc((void**)&e->kv_amax, tb) != hipSuccess) { e->err = "hipMalloc failed"; return bail(IVG_ERR_HIP); }
+      (void)hipMemset(e->kv_scales_dev, 0, tb);
+      (void)hipMemset(e->kv_amax, 0, tb);
+    }
     (void)hipMemset(e->vt, 0, vtb);
     (void)hipMemset(e->gen_buf, 0, e->gen_bytes);
   }
@@ -428,8 +436,114 @@ int ivg_set_kv_format(ivg_engine* e, int format, float k_scale, float v_scale) {
   if (format == IVG_KV_FP8_E4M3 && (e->cfg.num_layers <= 0 || e->llm_x3 || e->llm_dt != BF16 || e->hd != 64))
     return e->fail(IVG_ERR_INVALID, "set_kv_format: the FP8 K/V cache needs a transformer with llm_dtype IVG_BF16 and head_dim 64");
   e->kv_format = format; e->k_scale = k_scale; e->v_scale = v_scale;
+  e->kv_table = false; ++e->kv_gen;   // uniform scales: a table of ivg_set_kv_scales is dropped
   // whatever the cache holds was written in the previous format: a kept-cache caller starts over
   e->kv_len = 0; e->kv_B = 0; e->snap_valid = false; e->ids_valid = false;
+  return IVG_OK;
+}
+
+static bool kv8_engine(const ivg_engine* e) { return e->cfg.num_layers > 0 && !e->llm_x3 && e->llm_dt == BF16 && e->hd == 64 && e->kv_scales_dev && e->kv_amax; }
+static const char* const kKv8Needs = "the FP8 K/V cache needs a transformer with llm_dtype IVG_BF16 and head_dim 64";
+
+int ivg_set_kv_scales(ivg_engine* e, const float* scales) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("set_kv_scales: ") + kKv8Needs);
+  if (!scales) return e->fail(IVG_ERR_INVALID, "set_kv_scales: null argument");
+  const int heads = e->heads;
+  const size_t n = (size_t)e->cfg.num_layers * 2 * heads;
+  for (size_t i = 0; i < n; ++i)
+    if (!kv8_scale_ok(scales[i]))
+      return e->fail(IVG_ERR_INVALID, "set_kv_scales: layer " + std::to_string(i / (2 * heads)) + ", " + ((i / heads) % 2 ? "v" : "k") + ", head " +
+                                          std::to_string(i % heads) + ": every scale must be a finite, positive power of two (2^-126 .. 2^126)");
+  // launches of an earlier call may still read the table: the device is idle before it is rewritten (this call synchronises)
+  API_CK(hipDeviceSynchronize());
+  API_CK(hipMemcpy(e->kv_scales_dev, scales, n * 4, hipMemcpyHostToDevice));
+  e->kv_scales.assign(scales, scales + n);
+  e->kv_table = true; ++e->kv_gen;
+  e->kv_len = 0; e->kv_B = 0; e->snap_valid = false; e->ids_valid = false;   // as ivg_set_kv_format: the kept cache was written with other scales
+  return IVG_OK;
+}
+
+int ivg_get_kv_scales(ivg_engine* e, float* scales_out) {
+  if (!e) return IVG_ERR_INVALID;
+  if (e->cfg.num_layers <= 0 || !scales_out) return e->fail(IVG_ERR_INVALID, "get_kv_scales: engine without a transformer, or null argument");
+  const int heads = e->heads;
+  const size_t n = (size_t)e->cfg.num_layers * 2 * heads;
+  for (size_t i = 0; i < n; ++i) scales_out[i] = e->kv_table ? e->kv_scales[i] : ((i / heads) % 2 ? e->v_scale : e->k_scale);
+  return IVG_OK;
+}
+
+int ivg_kv_calibration_reset(ivg_engine* e) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("kv_calibration_reset: ") + kKv8Needs);
+  API_CK(hipDeviceSynchronize());   // (a calibration pass still running would race with the memset)
+  API_CK(hipMemset(e->kv_amax, 0, (size_t)e->cfg.num_layers * 2 * e->heads * 4));
+  API_CK(hipDeviceSynchronize());
+  e->calib_pending = false;
+  return IVG_OK;
+}
+
+int ivg_kv_calibrate(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, const float* actions, int act_T, int ctx, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("kv_calibrate: ") + kKv8Needs);
+  if (!ids || ids_stride < L) return e->fail(IVG_ERR_INVALID, "kv_calibrate: null ids, or ids_stride below L");
+  if (B <= 0 || L < 1 || L > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "kv_calibrate: batch or length exceeds capacity");
+  if (actions && (e->cfg.action_dim <= 0 || !e->act_w)) return e->fail(IVG_ERR_INVALID, "kv_calibrate: actions given but the model is action-free");
+  if (actions && (ctx < 1 || act_T < 1 || act_T > e->cfg.max_frames)) return e->fail(IVG_ERR_INVALID, "kv_calibrate: bad ctx / act_T");
+  const int Bc = std::min(e->cfg.max_batch, 128);   // the prompt pass's chunk: the cache (and its scratch) holds that many trajectories
+  const size_t es = dtype_size(e->llm_dt);
+  const int H = e->cfg.hidden_size, A = e->cfg.action_dim;
+  e->snap_valid = false; e->ids_valid = false;   // (the pass overwrites cache rows; Run::prefill zeroes kv_len / kv_B)
+  int rc = plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
+    r.kv_amax = e->kv_amax;
+    for (int b0 = 0; b0 < B; b0 += Bc) {
+      const int Bn = std::min(Bc, B - b0);
+      const size_t m = e->ws.mark();
+      const void* act_emb = nullptr;
+      if (actions) {
+        char* buf = (char*)e->ws.alloc((size_t)Bn * act_T * H * es);
+        if (!r.planning && launch_action_embed(actions + (size_t)b0 * act_T * A, e->act_w, e->act_b, buf, e->llm_dt, Bn * act_T, A, H, r.st))
+          return e->fail(IVG_ERR_HIP, "action_embed launch failed");
+        act_emb = buf;
+      }
+      // the teacher-forced prompt pass (actions on every sdf slot, as ivg_logits), no lm_head: kv_absmax_kernel follows each layer's rope_kv
+      int rc2 = r.prefill(r.planning ? nullptr : ids + (long)b0 * ids_stride, ids_stride, Bn, L, act_emb, act_T, ctx, true, nullptr, nullptr, nullptr);
+      if (rc2) return rc2;
+      e->ws.reset(m);
+    }
+    return 0;
+  });
+  if (rc == 0) { e->calib_stream = (hipStream_t)stream; e->calib_pending = true; }
+  return rc;
+}
+
+int ivg_kv_calibration_finish(ivg_engine* e, int headroom_log2, float* amax_out, float* scales_out) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("kv_calibration_finish: ") + kKv8Needs);
+  if (headroom_log2 < 0 || headroom_log2 > 8) return e->fail(IVG_ERR_INVALID, "kv_calibration_finish: headroom_log2 must be in [0, 8]");
+  const int heads = e->heads;
+  const size_t n = (size_t)e->cfg.num_layers * 2 * heads;
+  if (e->calib_pending) { API_CK(hipStreamSynchronize(e->calib_stream)); e->calib_pending = false; }
+  std::vector<uint32_t> bits(n);
+  API_CK(hipMemcpy(bits.data(), e->kv_amax, n * 4, hipMemcpyDeviceToHost));
+  std::vector<float> sc(n);
+  for (size_t i = 0; i < n; ++i) {
+    float a; memcpy(&a, &bits[i], 4);
+    if (amax_out) amax_out[i] = a;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    float a; memcpy(&a, &bits[i], 4);
+    if (bits[i] >= 0x7f800000u)
+      return e->fail(IVG_ERR_INVALID, "kv_calibration_finish: layer " + std::to_string(i / (2 * heads)) + ", " + ((i / heads) % 2 ? "v" : "k") + ", head " +
+                                          std::to_string(i % heads) + " saw " + (bits[i] > 0x7f800000u ? "NaN" : "Inf") + ": no scales installed");
+    // the smallest power of two s with amax / s <= 448 (= 0.875 * 2^9), times 2^headroom; exact, in integers
+    int ex = 0, p = 0;
+    if (a > 0.f) { const float mant = frexpf(a, &ex); p = (mant <= 0.875f ? ex - 9 : ex - 8) + headroom_log2; }
+    sc[i] = ldexpf(1.0f, std::min(126, std::max(-126, p)));
+  }
+  const int rc = ivg_set_kv_scales(e, sc.data());
+  if (rc) return rc;
+  if (scales_out) memcpy(scales_out, sc.data(), n * 4);
   return IVG_OK;
 }
 
@@ -1192,6 +1306,41 @@ int ivg_op_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const fl
   (void)hipStreamSynchronize(st);
   (void)hipFree(state);
   return rc == 0 ? IVG_OK : IVG_ERR_HIP;
+}
+
+// the [heads] tables of a test hook are device memory: read back (after the stream's earlier work) and checked as ivg_set_kv_scales checks
+static bool op_scales_ok(const float* k_scales, const float* v_scales, int heads, hipStream_t st) {
+  if (!k_scales || !v_scales || heads <= 0) return false;
+  std::vector<float> h(2 * (size_t)heads);
+  if (hipStreamSynchronize(st) != hipSuccess) return false;
+  if (hipMemcpy(h.data(), k_scales, heads * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(h.data() + heads, v_scales, heads * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+  for (float f : h) if (!kv8_scale_ok(f)) return false;
+  return true;
+}
+
+int ivg_op_kv8_pack_heads(const void* k16, const void* v16, void* kc, void* vc, int B, int heads, int L, int Lmax, const float* k_scales, const float* v_scales,
+                          ivg_stream stream) {
+  if (B <= 0 || heads <= 0 || L < 0 || L > Lmax || !op_scales_ok(k_scales, v_scales, heads, (hipStream_t)stream)) return IVG_ERR_INVALID;
+  return launch_kv8_pack(k16, v16, kc, vc, B * heads, L, Lmax, 1.0f, 1.0f, (hipStream_t)stream, heads, k_scales, v_scales) ? IVG_ERR_HIP : IVG_OK;
+}
+
+int ivg_op_decode_attn8_heads(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
+                              int P, int G, int row0, const float* k_scales, const float* v_scales, ivg_stream stream) {
+  if (B <= 0 || heads <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (!op_scales_ok(k_scales, v_scales, heads, st)) return IVG_ERR_INVALID;
+  StepState* state = nullptr;
+  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
+  int rc = launch_state_set(state, pos, 1, st);
+  if (!rc) rc = launch_decode_attn8(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, 1.0f, 1.0f, st, P, G, row0, k_scales, v_scales);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(state);
+  return rc == 0 ? IVG_OK : IVG_ERR_HIP;
+}
+
+int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, uint32_t* out, ivg_stream stream) {
+  if (!k16 || !v16 || !out || B <= 0 || heads <= 0 || L < 0 || L > Lmax) return IVG_ERR_INVALID;
+  return launch_kv_absmax(k16, v16, B, heads, L, Lmax, out, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
 }
 
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream) {

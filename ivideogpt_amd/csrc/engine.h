@@ -79,6 +79,17 @@ struct ivg_engine {
   // [layers][2][Bmax][heads][Lmax][64] bytes from the start of the bf16 cache's allocation (which keeps its size)
   int kv_format = IVG_KV_NATIVE;
   float k_scale = 1.0f, v_scale = 1.0f;
+  // ivg_set_kv_scales: per (layer, k|v, head) scales [layers][2][heads] used instead of the two scalars while kv_table is set (the
+  // device buffer is owned by the engine and rewritten only after a device synchronisation); kv_gen counts every ivg_set_kv_scales /
+  // ivg_set_kv_format and is part of the step-graph key.  kv_amax: what ivg_kv_calibrate observed, [layers][2][heads] fp32 bit patterns
+  float* kv_scales_dev = nullptr;
+  std::vector<float> kv_scales;
+  bool kv_table = false;
+  unsigned kv_gen = 0;
+  unsigned int* kv_amax = nullptr;
+  hipStream_t calib_stream = nullptr;       // stream of the last ivg_kv_calibrate (ivg_kv_calibration_finish synchronises it)
+  bool calib_pending = false;
+  const float* kv_tab(int layer, int which) const { return kv_table ? kv_scales_dev + ((size_t)layer * 2 + which) * heads : nullptr; }
   bool kv8() const { return kv_format == IVG_KV_FP8_E4M3; }
   size_t kv_elem_bytes() const { return kv8() ? 1 : (kv24 ? 3 : (llm_dt == ivg::BF16 ? 2 : 4)); }
   // tokenizer

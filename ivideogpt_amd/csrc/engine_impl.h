@@ -19,6 +19,7 @@ struct Run {
   hipStream_t st;
   bool planning;  // true: only walk the allocation plan (no launches) to size the workspace
   bool x3 = false;   // the entry point running now computes its fp32 matrix products in split-bf16 arithmetic (IVG_F32X3 path)
+  unsigned int* kv_amax = nullptr;   // prefill: after each layer's rope_kv, fold max |K|, |V| per head into kv_amax[layer][2][heads] (ivg_kv_calibrate)
   int kv_group = 1;  // decoder_trunk: trajectories per shared context (cross-attention K / V projected once per group; detokenize sets it)
 
   // ---- primitives (tokenizer.cpp)

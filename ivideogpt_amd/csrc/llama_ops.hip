@@ -1053,6 +1053,10 @@ int launch_kv24_pack(const void* k32, const void* v32, void* kc, void* vc, int B
 // v_scale into the final division.  As in decode_attn24_kernel the fed k / v are rounded -- to bf16, then to e4m3 -- BEFORE they
 // are used for this step's own score and output: a later step reads exactly what this one computed with.  The prompt pass keeps
 // bf16 K / V of one layer in scratch and packs the rows afterwards (kv8_pack_kernel).
+// Per-head scales (ivg_set_kv_scales): ks_tab / vs_tab are this layer's [heads] tables; a workgroup serves one (b, h) and reads its
+// two scales once, uniformly, where the scalars are used -- null pointers mean the scalar arguments, and that path computes what it
+// computed before the tables existed.  Resources with the two pointer arguments (-Rpass-analysis=kernel-resource-usage, gfx950):
+// 123 VGPRs plain / 133 SHARED, occupancy 4 / 3, scratch 0 -- the figures of the kernel without them.
 __device__ __forceinline__ float e4m3_clamp(float x) {
   const float c = fminf(fmaxf(x, -448.f), 448.f);
   return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u ? x : c;   // (fmin / fmax drop a NaN operand)
@@ -1075,7 +1079,8 @@ template <bool SHARED>
 __global__ __launch_bounds__(256) void decode_attn8_kernel(const bf16_t* __restrict__ qkv, unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
                                                            bf16_t* __restrict__ out, const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                            int heads, int Lmax, const StepState* __restrict__ state, unsigned long long* prof,
-                                                           float k_scale, float v_scale, int sh_P, int sh_G, int sh_row0) {
+                                                           float k_scale, float v_scale, int sh_P, int sh_G, int sh_row0,
+                                                           const float* __restrict__ ks_tab, const float* __restrict__ vs_tab) {
   constexpr int HD = 64, HALF = 32, LPK = KV8_LPK, GPB = KV8_GPB, UNR = KV8_UNR, VEC = 16;
   const unsigned long long t_start = prof ? wall_clock64() : 0ull;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1089,6 +1094,8 @@ __global__ __launch_bounds__(256) void decode_attn8_kernel(const bf16_t* __restr
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int sub = tid % LPK, grp = tid / LPK;
   const int H = heads * HD;
+  // per-head scales (ivg_set_kv_scales): one uniform read per workgroup from this layer's [heads] tables; null: the scalar arguments
+  if (ks_tab) { k_scale = ks_tab[h]; v_scale = vs_tab[h]; }
   const float scale = 0.125f * k_scale;                            // 1 / sqrt(64), and the keys' scale: both powers of two
   const float inv_ks = 1.0f / k_scale, inv_vs = 1.0f / v_scale;    // exact (kv8_scale_ok)
   const long blk = (long)Lmax * HD;                                // bytes of one (trajectory, head)
@@ -1240,17 +1247,17 @@ long long decode_attn8_launches() { return g_attn8_launches.load(); }
 
 int launch_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cosT, const float* sinT, int B, int heads, int Lmax,
                         const StepState* state, unsigned long long* prof, float k_scale, float v_scale, hipStream_t st, int sh_P, int sh_G,
-                        int sh_row0) {
-  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return (int)hipErrorInvalidValue;
+                        int sh_row0, const float* k_scales, const float* v_scales) {
+  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale) || (k_scales == nullptr) != (v_scales == nullptr)) return (int)hipErrorInvalidValue;
   const size_t smem = (size_t)(3 * 64 + Lmax + KV8_GPB * 64) * sizeof(float);
   dim3 g(B * heads);
   if (sh_G > 1) {
     if (sh_P < 0 || sh_row0 > 0) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(decode_attn8_kernel<true>, g, dim3(256), smem, st, (const bf16_t*)qkv, (unsigned char*)kc, (unsigned char*)vc, (bf16_t*)out, cosT,
-                       sinT, heads, Lmax, state, prof, k_scale, v_scale, sh_P, sh_G, sh_row0);
+                       sinT, heads, Lmax, state, prof, k_scale, v_scale, sh_P, sh_G, sh_row0, k_scales, v_scales);
   } else {
     hipLaunchKernelGGL(decode_attn8_kernel<false>, g, dim3(256), smem, st, (const bf16_t*)qkv, (unsigned char*)kc, (unsigned char*)vc, (bf16_t*)out, cosT,
-                       sinT, heads, Lmax, state, prof, k_scale, v_scale, 0, 1, 0);
+                       sinT, heads, Lmax, state, prof, k_scale, v_scale, 0, 1, 0, k_scales, v_scales);
   }
   g_attn8_launches.fetch_add(1, std::memory_order_relaxed);
   return (int)hipGetLastError();
@@ -1259,8 +1266,10 @@ int launch_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const fl
 // bf16 rows [0, L) of K / V ([B * heads][Lmax][64], what rope_kv wrote for the prompt into scratch) -> the byte rows of the cache.
 // Never in place: byte row t overlaps bf16 row t / 2 of the same block.
 __global__ __launch_bounds__(256) void kv8_pack_kernel(const bf16_t* __restrict__ k16, const bf16_t* __restrict__ v16, unsigned char* __restrict__ kc,
-                                                       unsigned char* __restrict__ vc, int L, int Lmax, float inv_ks, float inv_vs) {
+                                                       unsigned char* __restrict__ vc, int L, int Lmax, float inv_ks, float inv_vs, int heads,
+                                                       const float* __restrict__ ks_tab, const float* __restrict__ vs_tab) {
   const int bh = blockIdx.y, tid = threadIdx.x;
+  if (ks_tab) { inv_ks = 1.0f / ks_tab[bh % heads]; inv_vs = 1.0f / vs_tab[bh % heads]; }   // per-head scales: exact reciprocals of powers of two
   const int row = blockIdx.x * 32 + (tid >> 3), sub = tid & 7;
   if (row >= L) return;
   const long off = ((long)bh * Lmax + row) * 64 + sub * 8;
@@ -1275,11 +1284,54 @@ __global__ __launch_bounds__(256) void kv8_pack_kernel(const bf16_t* __restrict_
   }
 }
 
-int launch_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, hipStream_t st) {
-  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return (int)hipErrorInvalidValue;
+int launch_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, hipStream_t st,
+                    int heads, const float* k_scales, const float* v_scales) {
+  if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale) || heads <= 0 || (k_scales == nullptr) != (v_scales == nullptr)) return (int)hipErrorInvalidValue;
   if (L <= 0) return 0;
   hipLaunchKernelGGL(kv8_pack_kernel, dim3((unsigned)cdiv(L, 32), (unsigned)BH), dim3(256), 0, st, (const bf16_t*)k16, (const bf16_t*)v16,
-                     (unsigned char*)kc, (unsigned char*)vc, L, Lmax, 1.0f / k_scale, 1.0f / v_scale);
+                     (unsigned char*)kc, (unsigned char*)vc, L, Lmax, 1.0f / k_scale, 1.0f / v_scale, heads, k_scales, v_scales);
+  return (int)hipGetLastError();
+}
+
+// Observation for the calibration of the FP8 cache (ivg_kv_calibrate): per head, the maximum of |x| over trajectories, rows [0, L) and
+// elements of one layer's bf16 K and V ([B * heads][Lmax][64], what rope_kv just wrote), accumulated into amax [2][heads] (k | v) as
+// the fp32 bit pattern of that maximum.  The maximum is taken on the INTEGER pattern of |x| (bits & 0x7fff, widened to fp32 by << 16):
+// for non-negative floats the integer order is the value order, NaN patterns rank above Inf above every finite value (a non-finite
+// K / V is never hidden), and an integer maximum is associative and commutative -- the result does not depend on any order.  That is
+// why the atomicMax across workgroups below is within the rule "no atomics on data": the rule is about results that depend on the
+// order of arrival, and this one cannot.  One workgroup per (32 rows, b * heads + h) as kv8_pack_kernel, 16-byte loads, rows >= L
+// never read, wave reduction by shuffles, one atomic per wave and tensor.
+__global__ __launch_bounds__(256) void kv_absmax_kernel(const bf16_t* __restrict__ k16, const bf16_t* __restrict__ v16, int L, int Lmax, int heads,
+                                                        unsigned int* __restrict__ amax) {
+  const int bh = blockIdx.y, tid = threadIdx.x;
+  const int row = blockIdx.x * 32 + (tid >> 3), sub = tid & 7;
+  unsigned int mk = 0u, mv = 0u;
+  if (row < L) {
+    const long off = ((long)bh * Lmax + row) * 64 + sub * 8;
+    const Chunk16 a = *(const Chunk16*)(k16 + off), c = *(const Chunk16*)(v16 + off);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      mk = max(mk, max(a[w] & 0x7fffu, (a[w] >> 16) & 0x7fffu));
+      mv = max(mv, max(c[w] & 0x7fffu, (c[w] >> 16) & 0x7fffu));
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    mk = max(mk, (unsigned int)__shfl_xor((int)mk, d, 64));
+    mv = max(mv, (unsigned int)__shfl_xor((int)mv, d, 64));
+  }
+  if ((tid & 63) == 0) {
+    const int h = bh % heads;
+    if (mk) atomicMax(amax + h, mk << 16);
+    if (mv) atomicMax(amax + heads + h, mv << 16);
+  }
+}
+
+int launch_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, unsigned int* amax, hipStream_t st) {
+  if (B <= 0 || heads <= 0 || L < 0 || L > Lmax || !amax) return (int)hipErrorInvalidValue;
+  if (L == 0) return 0;
+  hipLaunchKernelGGL(kv_absmax_kernel, dim3((unsigned)cdiv(L, 32), (unsigned)(B * heads)), dim3(256), 0, st, (const bf16_t*)k16, (const bf16_t*)v16, L,
+                     Lmax, heads, amax);
   return (int)hipGetLastError();
 }
 

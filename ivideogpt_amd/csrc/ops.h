@@ -94,9 +94,14 @@ int launch_kv24_pack(const void* k32, const void* v32, void* kc, void* vc, int B
 // K and V (the prefill's scratch; must not overlap the byte rows) -> the cache
 int launch_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const float* cosT, const float* sinT, int B, int heads, int Lmax,
                         const StepState* state, unsigned long long* prof, float k_scale, float v_scale, hipStream_t st, int sh_P = 0, int sh_G = 1,
-                        int sh_row0 = 0);
+                        int sh_row0 = 0, const float* k_scales = nullptr, const float* v_scales = nullptr);
 long long decode_attn8_launches();    // launches over the FP8 cache since load (test hook)
-int launch_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, hipStream_t st);
+int launch_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, hipStream_t st,
+                    int heads = 1, const float* k_scales = nullptr, const float* v_scales = nullptr);
+// k_scales / v_scales (device, [heads], both or neither): per-head scales of one layer (ivg_set_kv_scales) used instead of the scalars;
+// head = (b * heads + h) % heads.  launch_kv_absmax: amax [2][heads] (device, fp32 bit patterns) = max(amax, max |x|) per head over
+// rows [0, L) of bf16 k16 / v16 [B * heads][Lmax][64] (kv_absmax_kernel: the calibration's observation; rows >= L are never read)
+int launch_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, unsigned int* amax, hipStream_t st);
 bool kv8_scale_ok(float s);           // a finite, positive power of two whose reciprocal is a normal float (2^-126 .. 2^126)
 int launch_expand_prompt_rows(const int64_t* prompts, long pstride, int64_t* ids, long ids_ld, int rows, int L, int G, int b0, hipStream_t st);
 // token decision + embedding of the decided token (+ action embedding on forced sdf slots) + state advance

@@ -128,7 +128,8 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
     if (!planning) {
       CK(launch_rope_kv(qkv, kl, kv24 ? v32 : (kv8 ? v16 : kc_ptr(e, l, 1)), e->vt, Lp, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, 0, dt, st));
       if (kv24) CK(launch_kv24_pack(k32, v32, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, st));
-      if (kv8) CK(launch_kv8_pack(k16, v16, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, e->k_scale, e->v_scale, st));
+      if (kv_amax) CK(launch_kv_absmax(kl, kv8 ? v16 : kc_ptr(e, l, 1), B, heads, L, Lmax, kv_amax + (size_t)l * 2 * heads, st));
+      if (kv8) CK(launch_kv8_pack(k16, v16, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, e->k_scale, e->v_scale, st, heads, e->kv_tab(l, 0), e->kv_tab(l, 1)));
     }
     if (flash) {
       if (!planning) CK(launch_flash_prefill(qkv, kl, e->vt, attn, B, L, Lp, heads, hd, Lmax, dt, st));
@@ -296,7 +297,7 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
     unsigned long long* aprof = e->attn_prof_on ? e->attn_prof + (size_t)l * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax : nullptr;
     if (e->kv8())
       CK(launch_decode_attn8(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->Lmax, state,
-                             aprof, e->k_scale, e->v_scale, st, g.sh_P, g.sh_G, g.sh_row0));
+                             aprof, e->k_scale, e->v_scale, st, g.sh_P, g.sh_G, g.sh_row0, e->kv_tab(l, 0), e->kv_tab(l, 1)));
     else if (e->kv24)
       CK(launch_decode_attn24(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->Lmax, state,
                               aprof, st, g.sh_P, g.sh_G, g.sh_row0));
@@ -413,7 +414,7 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
                             std::to_string(sa.forced_period) + ":" + std::to_string(ctx) + ":" + std::to_string(act_T) + ":" +
                             std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)
                             (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "") +
-                            (e->kv8() ? ":kv8:" + std::to_string(ks_bits) + ":" + std::to_string(vs_bits) : "");   // (the cache format and its scales: kernel and arguments)
+                            (e->kv8() ? ":kv8:" + std::to_string(ks_bits) + ":" + std::to_string(vs_bits) + ":" + std::to_string(e->kv_gen) : "");   // (the cache format and its scales: kernel and arguments; kv_gen: scalars or which table)
     // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
     // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
     auto reward = [&]() -> int {

@@ -148,6 +148,44 @@ class Engine:
         self.check(self.lib.ivg_set_kv_format(self.h, int(fmt), float(k_scale), float(v_scale)), "set_kv_format")
         return self
 
+    def _kv_table_shape(self):
+        return (int(self.cfg.num_layers), 2, int(self.cfg.num_heads))
+
+    def set_kv_scales(self, scales):
+        """``ivg_set_kv_scales``: per (layer, k|v, head) scales of the FP8 K / V cache, a ``(layers, 2, heads)`` tensor or nested list of
+        powers of two; in force while the format is FP8, until the next ``set_kv_format``.  Invalidates the kept cache; synchronises."""
+        t = torch.as_tensor(scales, dtype=torch.float32).cpu().contiguous()
+        if tuple(t.shape) != self._kv_table_shape():
+            raise ValueError(f"set_kv_scales: scales must have shape {self._kv_table_shape()}, not {tuple(t.shape)}")
+        self.check(self.lib.ivg_set_kv_scales(self.h, _ptr(t)), "set_kv_scales")
+        return self
+
+    def get_kv_scales(self):
+        """``ivg_get_kv_scales``: the scales in force as a ``(layers, 2, heads)`` float32 CPU tensor (the two scalars expanded when no table is set)."""
+        t = torch.empty(self._kv_table_shape(), dtype=torch.float32)
+        self.check(self.lib.ivg_get_kv_scales(self.h, _ptr(t)), "get_kv_scales")
+        return t
+
+    def kv_calibrate(self, ids, actions=None, ctx=1, reset=False):
+        """``ivg_kv_calibrate``: the teacher-forced prompt pass over ``ids (B, L)`` that folds max |K|, max |V| per (layer, head) into the
+        engine's table (calls accumulate; ``reset``: ``ivg_kv_calibration_reset`` first).  Enqueued, no synchronisation."""
+        if reset:
+            self.check(self.lib.ivg_kv_calibration_reset(self.h), "kv_calibration_reset")
+        B, L = ids.shape
+        act_T = actions.shape[1] if actions is not None else 0
+        with self.stream() as s:
+            self.check(self.lib.ivg_kv_calibrate(self.h, _ptr(ids), ids.stride(0), B, L, _ptr(actions), act_T, int(ctx), s), "kv_calibrate")
+            for t in (ids, actions):
+                if t is not None:
+                    t.record_stream(self._run)
+        return self
+
+    def kv_calibration_finish(self, headroom=1):
+        """``ivg_kv_calibration_finish`` (synchronises): -> (amax, scales), ``(layers, 2, heads)`` float32 CPU tensors; the scales are installed."""
+        amax, scales = torch.empty(self._kv_table_shape(), dtype=torch.float32), torch.empty(self._kv_table_shape(), dtype=torch.float32)
+        self.check(self.lib.ivg_kv_calibration_finish(self.h, int(headroom), _ptr(amax), _ptr(scales)), "kv_calibration_finish")
+        return amax, scales
+
     def set_context_length(self, k):
         self.check(self.lib.ivg_set_context_length(self.h, int(k)), "set_context_length")
 

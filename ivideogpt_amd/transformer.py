@@ -123,26 +123,45 @@ def _top_p_of(top_p, do_sample):
 KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
 
 
-def _kv_cache_setting(name, k_scale, v_scale, dtype, cfg):
+def _kv_scale_checked(what, s):
+    try:
+        f = float(s)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if not (math.isfinite(f) and f > 0.0 and math.frexp(f)[0] == 0.5 and 2.0 ** -126 <= f <= 2.0 ** 126):
+        raise ValueError(f"{what} must be a finite, positive power of two in [2^-126, 2^126], not {s!r}")
+    return f
+
+
+def _kv_cache_setting(name, k_scale, v_scale, dtype, cfg, scales=None):
     """The (name, k_scale, v_scale) of ``kv_cache_dtype`` / ``set_kv_cache_dtype``, checked before any engine work (include/ivg.h
     ivg_set_kv_format): ValueError for an unknown name, a scale that is not a finite positive power of two in [2^-126, 2^126], or
-    ``"fp8_e4m3"`` on a model that is not bf16 with head_dim 64."""
+    ``"fp8_e4m3"`` on a model that is not bf16 with head_dim 64.  With ``scales`` -- a (layers, 2, heads) tensor or nested list, every
+    entry such a power of two (ivg_set_kv_scales) -- the result has a fourth element, the table as nested tuples; ValueError for a
+    wrong shape or entry, for ``scales`` together with a non-default ``k_scale`` / ``v_scale``, or on a model the FP8 cache is not for."""
     if name not in KV_CACHE_DTYPES:
         raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, not {name!r}")
-    scales = []
-    for what, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-        try:
-            f = float(s)
-        except (TypeError, ValueError):
-            f = float("nan")
-        if not (math.isfinite(f) and f > 0.0 and math.frexp(f)[0] == 0.5 and 2.0 ** -126 <= f <= 2.0 ** 126):
-            raise ValueError(f"{what} must be a finite, positive power of two in [2^-126, 2^126], not {s!r}")
-        scales.append(f)
-    if name == "fp8_e4m3":
-        hd = cfg["hidden_size"] // max(1, cfg["num_attention_heads"])
-        if is_x3(dtype) or dtype_code(dtype) != _lib.IVG_BF16 or hd != 64:
-            raise ValueError(f"kv_cache_dtype='fp8_e4m3' needs a bf16 model with head_dim 64 (this one: dtype {dtype!r}, head_dim {hd})")
-    return name, scales[0], scales[1]
+    ks, vs = _kv_scale_checked("k_scale", k_scale), _kv_scale_checked("v_scale", v_scale)
+    hd = cfg["hidden_size"] // max(1, cfg["num_attention_heads"])
+    fp8_model = not is_x3(dtype) and dtype_code(dtype) == _lib.IVG_BF16 and hd == 64
+    if name == "fp8_e4m3" and not fp8_model:
+        raise ValueError(f"kv_cache_dtype='fp8_e4m3' needs a bf16 model with head_dim 64 (this one: dtype {dtype!r}, head_dim {hd})")
+    if scales is None:
+        return name, ks, vs
+    if (ks, vs) != (1.0, 1.0):
+        raise ValueError("pass either scales (per layer and head) or k_scale / v_scale, not both")
+    if not fp8_model:
+        raise ValueError(f"K / V scales need a bf16 model with head_dim 64 (this one: dtype {dtype!r}, head_dim {hd})")
+    shape = (cfg["num_hidden_layers"], 2, cfg["num_attention_heads"])
+    try:
+        t = torch.as_tensor(scales, dtype=torch.float32).cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"scales must be a tensor or nested list of shape {shape}") from None
+    if tuple(t.shape) != shape:
+        raise ValueError(f"scales must have shape {shape} (layers, k|v, heads), not {tuple(t.shape)}")
+    table = tuple(tuple(tuple(_kv_scale_checked(f"scales[{l}][{w}][{h}]", x) for h, x in enumerate(row)) for w, row in enumerate(lay))
+                  for l, lay in enumerate(t.tolist()))
+    return name, ks, vs, table
 
 
 class LlamaForCausalLM:
@@ -282,22 +301,62 @@ class LlamaForCausalLM:
         self._engine = Engine(self.device, self._packed_weights(), llm_cfg=self._cfg, action_dim=self._action_dim or 0,
                               reward_head=self._reward, llm_dtype=self.dtype, max_batch=cap_b, max_frames=cap_t,
                               decode_lds_kb=self._decode_lds_kb, max_seq=self._max_seq)
-        if self._kv[0] != "auto":
-            self._engine.set_kv_format(_lib.IVG_KV_FP8_E4M3, self._kv[1], self._kv[2])
+        self._apply_kv(self._engine, fresh=True)
         return self._engine
 
-    def set_kv_cache_dtype(self, name, k_scale=1.0, v_scale=1.0):
+    def _apply_kv(self, eng, fresh=False):
+        """``self._kv`` -> the engine: the format with its uniform scales, then the table when there is one (set_kv_format drops a table)."""
+        kv = self._kv
+        if not fresh or kv[0] != "auto":
+            eng.set_kv_format(_lib.IVG_KV_NATIVE if kv[0] == "auto" else _lib.IVG_KV_FP8_E4M3, kv[1], kv[2])
+        if len(kv) > 3:
+            eng.set_kv_scales(kv[3])
+
+    def set_kv_cache_dtype(self, name, k_scale=1.0, v_scale=1.0, scales=None):
         """K / V cache format of this model's rollouts (include/ivg.h ivg_set_kv_format).  ``"auto"``: the model's own element type, the
         default.  ``"fp8_e4m3"`` (bf16 models with head_dim 64): an opt-in, lossy one-byte cache, element = e4m3(clamp(x / scale, +-448))
-        with ``k_scale`` / ``v_scale`` powers of two.  ValueError, before any engine work, for a wrong name, model dtype or scale.  Applies
-        to the live engine from its next generate call on -- whose kept KV cache it invalidates (``reuse_cache`` / ``use_cache`` callers
-        start over) -- and to every engine this model builds later."""
-        kv = _kv_cache_setting(name, k_scale, v_scale, self.dtype, self._cfg)
+        with ``k_scale`` / ``v_scale`` powers of two, or with ``scales``: one power of two per (layer, k|v, head), a (layers, 2, heads)
+        tensor or nested list -- what ``calibrate_kv_cache`` returns and ``kv_scales`` reads (ivg_set_kv_scales).  Without ``scales`` the
+        scales are uniform and a table set earlier is dropped.  ValueError, before any engine work, for a wrong name, model dtype, scale
+        or table, or for ``scales`` together with ``k_scale`` / ``v_scale``.  Applies to the live engine from its next generate call on
+        -- whose kept KV cache it invalidates (``reuse_cache`` / ``use_cache`` callers start over) -- and to every engine this model
+        builds later."""
+        kv = _kv_cache_setting(name, k_scale, v_scale, self.dtype, self._cfg, scales)
         if kv != self._kv:
             self._kv = kv
             if self._engine is not None:
-                self._engine.set_kv_format(_lib.IVG_KV_NATIVE if kv[0] == "auto" else _lib.IVG_KV_FP8_E4M3, kv[1], kv[2])
+                self._apply_kv(self._engine)
         return self
+
+    @property
+    def kv_scales(self):
+        """The K / V scales of this model's FP8 cache as a (layers, 2, heads) float32 CPU tensor: the table when one is set (``scales=``,
+        ``calibrate_kv_cache``), else ``k_scale`` / ``v_scale`` expanded.  Read-only."""
+        L, H = self._cfg["num_hidden_layers"], self._cfg["num_attention_heads"]
+        if len(self._kv) > 3:
+            return torch.tensor(self._kv[3], dtype=torch.float32)
+        return torch.tensor([self._kv[1], self._kv[2]], dtype=torch.float32).view(1, 2, 1).expand(L, 2, H).contiguous()
+
+    @torch.no_grad()
+    def calibrate_kv_cache(self, input_ids, headroom=1, reset=True, _actions=None, _ctx=1):
+        """Calibrates the FP8 cache's scales on the device (ivg_kv_calibrate / ivg_kv_calibration_finish): runs the teacher-forced prompt
+        pass over ``input_ids (B, L)`` -- whole ground-truth token rows, so that it sees the positions a rollout appends --, takes
+        max |K| and max |V| per (layer, head), and installs per (layer, k|v, head) the smallest power of two that keeps the maximum
+        within +-448, times 2^``headroom`` (0 .. 8; the default leaves one bit for rows the calibration set did not contain: it costs no
+        mantissa).  ``reset=False`` accumulates over several calls.  -> the scales, a (layers, 2, heads) float32 CPU tensor, also kept
+        for rebuilt engines and ``replica()``; the observed maxima are in ``last_kv_amax``.  Does NOT switch the format on, and a later
+        ``set_kv_cache_dtype`` without ``scales`` drops the table: turn the format on first, or pass ``scales=model.kv_scales``.
+        Synchronises.  ValueError on a model the FP8 cache is not for; AssertionError (ivg_last_error names layer, tensor and head) when
+        K or V held a NaN or Inf."""
+        if not (isinstance(headroom, int) and 0 <= headroom <= 8):
+            raise ValueError(f"headroom must be an integer in [0, 8], not {headroom!r}")
+        _kv_cache_setting("fp8_e4m3", 1.0, 1.0, self.dtype, self._cfg)   # (the model check, before any engine work)
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        eng = self._ensure(ids.shape[0], _actions.shape[1] if _actions is not None else 32)
+        eng.kv_calibrate(ids, actions=_actions, ctx=_ctx, reset=reset)
+        self.last_kv_amax, scales = eng.kv_calibration_finish(headroom)
+        self._kv = self._kv[:3] + (_kv_cache_setting("auto", 1.0, 1.0, self.dtype, self._cfg, scales)[3],)   # (the engine has it installed)
+        return scales
 
     # LDS budget (KiB) of a decode-step GEMM workgroup for a model whose batch shares the GPU with other batches in flight (bench.py
     # --lanes, INTEGRATION.md "streams"): with a whole CU's LDS per workgroup (the default, fastest for one batch alone) the decode
@@ -469,9 +528,19 @@ class HeadModelWithAction:
         self.llm.set_decode_lds_kb(kb)
         return self
 
-    def set_kv_cache_dtype(self, name, k_scale=1.0, v_scale=1.0):
-        self.llm.set_kv_cache_dtype(name, k_scale, v_scale)
+    def set_kv_cache_dtype(self, name, k_scale=1.0, v_scale=1.0, scales=None):
+        self.llm.set_kv_cache_dtype(name, k_scale, v_scale, scales)
         return self
+
+    @property
+    def kv_scales(self):
+        return self.llm.kv_scales
+
+    def calibrate_kv_cache(self, input_ids, action=None, headroom=1, reset=True):
+        """``LlamaForCausalLM.calibrate_kv_cache`` with the action embeddings added on every sdf slot (as ``logits``) at this wrapper's
+        context length."""
+        act = action.to(device=self.llm.device, dtype=torch.float32).contiguous() if action is not None else None
+        return self.llm.calibrate_kv_cache(input_ids, headroom=headroom, reset=reset, _actions=act, _ctx=self.context)
 
     def replica(self):
         """As LlamaForCausalLM.replica: a second wrapper (own engine) over the same weights in HBM."""

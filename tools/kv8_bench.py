@@ -16,6 +16,10 @@ does not know the format).  BASELINE config 2's transformer: Llama-small at rele
               * pixels after detokenize of both rollouts.
             Seeded weights give near-uniform attention and bounded activations: they understate what outliers in trained K / V do
             to an 8-bit format.  No pass bar: the op-level contract (tests/test_gpu_decode_attn8.py) is the bar.
+  --calibrate  one more accuracy column (profiles/kv8_scales.txt): the same prefix + one decode step on a RESCALED twin of the model
+            (per layer q_proj rows of head 0 x 2^-10, k_proj rows of head 0 x 2^10, v_proj rows of head 1 x 2^-12, o_proj columns of
+            head 1 x 2^12: the same function, as tests/test_gpu_kv_scales.py checks) with the FP8 cache at scale 1 against the per-layer,
+            per-head scales calibrate_kv_cache finds on the prefix, and the original model beside it.
 """
 import argparse
 import os
@@ -178,12 +182,55 @@ def accuracy(m, cfg, sd, dev, out, n_new):
     m.set_kv_cache_dtype("auto")
 
 
+def rescaled_twin(sd, layers):
+    tw = {k: v.clone() for k, v in sd.items()}
+    for l in range(layers):
+        pre = f"model.layers.{l}.self_attn."
+        tw[pre + "q_proj.weight"][0:64] *= 2.0 ** -10
+        tw[pre + "k_proj.weight"][0:64] *= 2.0 ** 10
+        tw[pre + "v_proj.weight"][64:128] *= 2.0 ** -12
+        tw[pre + "o_proj.weight"][:, 64:128] *= 2.0 ** 12
+    return tw
+
+
+def calibrate_column(m, cfg, sd, dev, out):
+    from oracle.llama import LlamaRef
+    clip = torch.from_numpy(np.load(os.path.join(ROOT, "tests", "golden", "fractal_clip_seed0.npz"))["clip"])[None]
+    tcfg = W.tokenizer_config(**W.CTX_VAE64)
+    tok = CompressiveVQModel(tcfg, W.random_tokenizer_state_dict(tcfg, 0, 0.4), encode_dtype="fp32", decode_dtype="bf16").to(dev)
+    ctx = tcfg["context_length"]
+    ids = tok.tokenize(clip.to(dev), ctx)[0].cpu()
+    L = 257 * ctx + 16
+    seq = torch.cat([ids[:, :L], torch.full((1, 1), cfg["vocab_size"] - 1, dtype=torch.int64)], 1)
+    ora = LlamaRef(sd, cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["rms_norm_eps"], cfg["rope_theta"], cfg["max_position_embeddings"])
+    ref = ora.forward_embeds(ora.embed(seq), return_hidden=True)[2][:, -1].double()
+    twin = LlamaForCausalLM(cfg, rescaled_twin(sd, cfg["num_hidden_layers"]), dtype="bf16").to(dev)
+    out.append(f"--calibrate: teacher-forced prefix of {L} golden-clip tokens + one decode step, hidden state against the fp32 CPU oracle of the original "
+               f"model; scales calibrated on the {L + 1} tokens (headroom 1):")
+    for name, model in (("original", m), ("rescaled twin", twin)):
+        emb = model.get_input_embeddings()(seq.to(dev))
+        model.set_kv_cache_dtype("auto")
+        tab = model.calibrate_kv_cache(seq.to(dev))
+        lg = torch.log2(tab)
+        for what, kw in (("bf16 cache", dict(name="auto")), ("fp8, scale 1", dict(name="fp8_e4m3")), ("fp8, calibrated", dict(name="fp8_e4m3", scales=tab))):
+            model.set_kv_cache_dtype(**kw)
+            model.generate(inputs_embeds=emb[:, :L], do_sample=False, max_new_tokens=1)
+            r = model.generate(inputs_embeds=emb, do_sample=False, max_new_tokens=1, return_dict_in_generate=True, output_hidden_states=True)
+            assert model.last_generate_reused_cache, "the decode step did not run over the kept cache"
+            d = (r.hidden_states[-1][-1][:, 0].double().cpu() - ref).abs()
+            out.append(f"  {name:13s} {what:15s} max abs deviation {d.max():.4e}   rms {d.pow(2).mean().sqrt():.4e}")
+        out.append(f"  {name:13s} log2 of the calibrated scales: K min {int(lg[:, 0].min())} max {int(lg[:, 0].max())} (head 0: {int(lg[:, 0, 0].min())} .. {int(lg[:, 0, 0].max())});  "
+                   f"V min {int(lg[:, 1].min())} max {int(lg[:, 1].max())} (head 1: {int(lg[:, 1, 1].min())} .. {int(lg[:, 1, 1].max())})")
+        model.set_kv_cache_dtype("auto")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--lanes", type=int, default=4)
     ap.add_argument("--skip", default="", help="comma list of speed1, speed4, accuracy")
+    ap.add_argument("--calibrate", action="store_true", help="add the calibrated-scales accuracy column (rescaled twin of the model)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert a.rounds >= 1
@@ -206,6 +253,8 @@ def main():
         speed_lanes(m, prompt, u, n_new, a.rounds, a.lanes, out)
     if "accuracy" not in skip:
         accuracy(m, cfg, sd, dev, out, n_new)
+    if a.calibrate:
+        calibrate_column(m, cfg, sd, dev, out)
     text = "\n".join(out)
     print(text)
     if a.out:
