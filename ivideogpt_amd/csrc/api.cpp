@@ -249,12 +249,35 @@ static int plan_and_allocate(ivg_engine* e) {
   }
   if (c.num_layers > 0) {
     const int Lpre = std::min(e->Lmax - 1, 514);  // typical prompt (2 context frames); larger calls grow the arena on demand
-    int rc = r.generate(nullptr, 0, B, Lpre, 1, nullptr, 0, 1, nullptr, 0, nullptr, nullptr); if (rc) return rc;
+    GenerateReq q; q.B = B; q.L0 = Lpre; q.n_new = 1;
+    int rc = r.generate(q); if (rc) return rc;
   }
   e->ws.cap = e->ws.high + (1 << 20);
   API_CK(hipMalloc((void**)&e->ws.base, e->ws.cap));
   e->ws.planning = false; e->ws.off = 0;
   return 0;
+}
+
+// the fields every GEMM / convolution hook takes over from the caller's struct as they are
+static void igemm_op_args(IgemmArgs& g, const ivg_igemm_args* a) {
+  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
+  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
+  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
+  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
+  g.flags = a->flags; g.alpha = a->alpha;
+}
+
+// Unit-test hooks of one decode step: a device StepState at position pos (step j = 1) for the launch f(state, st) makes; waits for it
+template <typename F>
+static int one_step(int pos, ivg_stream stream, F&& f) {
+  StepState* state = nullptr;
+  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_state_set(state, pos, 1, st);
+  if (!rc) rc = f(state, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(state);
+  return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
 }
 
 extern "C" {
@@ -275,13 +298,11 @@ void ivg_destroy(ivg_engine* e) {
   if (e->ws.base) (void)hipFree(e->ws.base);
   if (e->ee_c) (void)hipFree(e->ee_c);
   if (e->ee_d) (void)hipFree(e->ee_d);
-  if (e->kv) (void)hipFree(e->kv);
+  e->kvc.destroy();
   if (e->vt) (void)hipFree(e->vt);
   if (e->gen_buf) (void)hipFree(e->gen_buf);
   if (e->ones) (void)hipFree(e->ones);
   if (e->attn_prof) (void)hipFree(e->attn_prof);
-  if (e->kv_scales_dev) (void)hipFree(e->kv_scales_dev);
-  if (e->kv_amax) (void)hipFree(e->kv_amax);
   if (e->emb_snap) (void)hipFree(e->emb_snap);
   if (e->gemm_prof) (void)hipFree(e->gemm_prof);
   if (e->h_flag) (void)hipHostFree(e->h_flag);
@@ -340,12 +361,11 @@ int ivg_create(const ivg_config* cfg, const ivg_tensor* weights, int n_weights, 
   }
   if (cfg->num_layers > 0) {
     int rc = build_transformer(e); if (rc) return bail(rc);
-    const int kb = std::min(cfg->max_batch, 128);
-    e->kv24 = e->llm_x3 && e->hd == 64 && sw().x3 && sw().kv24;   // (IVG_X3=0: an x3 engine IS the fp32 engine)
-    const size_t kvb = (size_t)cfg->num_layers * 2 * kb * e->heads * e->Lmax * e->hd * e->kv_elem_bytes();
-    const size_t vtb = (size_t)kb * e->heads * e->hd * ((e->Lmax + 63) / 64 * 64) * dtype_size(e->llm_dt);
+    const bool planes24 = e->llm_x3 && e->hd == 64 && sw().x3 && sw().kv24;   // (IVG_X3=0: an x3 engine IS the fp32 engine)
+    if (!e->kvc.create(cfg->num_layers, e->heads, e->hd, e->Lmax, cfg->max_batch, e->llm_dt, e->llm_x3, planes24)) { e->err = "hipMalloc of the KV cache failed"; return bail(IVG_ERR_HIP); }
+    const size_t vtb = (size_t)e->kvc.chunk * e->heads * e->hd * ((e->Lmax + 63) / 64 * 64) * dtype_size(e->llm_dt);
     e->gen_bytes = gen_buffer_bytes(e);
-    if (hipMalloc((void**)&e->kv, kvb) != hipSuccess || hipMalloc((void**)&e->vt, vtb) != hipSuccess || hipMalloc((void**)&e->gen_buf, e->gen_bytes) != hipSuccess) {
+    if (hipMalloc((void**)&e->vt, vtb) != hipSuccess || hipMalloc((void**)&e->gen_buf, e->gen_bytes) != hipSuccess) {
       e->err = "hipMalloc of the KV cache failed"; return bail(IVG_ERR_HIP);
     }
     {
@@ -356,12 +376,6 @@ int ivg_create(const ivg_config* cfg, const ivg_tensor* weights, int n_weights, 
     }
     if (hipMalloc((void**)&e->attn_prof, (size_t)cfg->num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8) != hipSuccess) { e->err = "hipMalloc failed"; return bail(IVG_ERR_HIP); }
     (void)hipMemset(e->attn_prof, 0, (size_t)cfg->num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8);
-    if (!e->llm_x3 && e->llm_dt == BF16 && e->hd == 64) {   // engines the FP8 cache is for: its scale table and the calibration's observations
-      const size_t tb = (size_t)cfg->num_layers * 2 * e->heads * 4;
-      if (hipMalloc((void**)&e->kv_scales_dev, tb) != hipSuccess || hipMalloc((void**)&e->kv_amax, tb) != hipSuccess) { e->err = "hipMalloc failed"; return bail(IVG_ERR_HIP); }
-      (void)hipMemset(e->kv_scales_dev, 0, tb);
-      (void)hipMemset(e->kv_amax, 0, tb);
-    }
     (void)hipMemset(e->vt, 0, vtb);
     (void)hipMemset(e->gen_buf, 0, e->gen_bytes);
   }
@@ -428,122 +442,91 @@ int ivg_set_decode_lds_kb(ivg_engine* e, int kb) {
   return IVG_OK;
 }
 
+// the FP8 cache's entries: engines it is not for are refused in the same words
+static int need_fp8(ivg_engine* e, const char* who) { return e->kvc.fp8_eligible() ? 0 : e->fail(IVG_ERR_INVALID, std::string(who) + ": " + KvCache::kFp8Needs); }
+
 int ivg_set_kv_format(ivg_engine* e, int format, float k_scale, float v_scale) {
   if (!e) return IVG_ERR_INVALID;
   if (format != IVG_KV_NATIVE && format != IVG_KV_FP8_E4M3) return e->fail(IVG_ERR_INVALID, "set_kv_format: format must be IVG_KV_NATIVE or IVG_KV_FP8_E4M3");
   if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale))
     return e->fail(IVG_ERR_INVALID, "set_kv_format: k_scale and v_scale must be finite, positive powers of two (2^-126 .. 2^126)");
-  if (format == IVG_KV_FP8_E4M3 && (e->cfg.num_layers <= 0 || e->llm_x3 || e->llm_dt != BF16 || e->hd != 64))
-    return e->fail(IVG_ERR_INVALID, "set_kv_format: the FP8 K/V cache needs a transformer with llm_dtype IVG_BF16 and head_dim 64");
-  e->kv_format = format; e->k_scale = k_scale; e->v_scale = v_scale;
-  e->kv_table = false; ++e->kv_gen;   // uniform scales: a table of ivg_set_kv_scales is dropped
-  // whatever the cache holds was written in the previous format: a kept-cache caller starts over
-  e->kv_len = 0; e->kv_B = 0; e->snap_valid = false; e->ids_valid = false;
+  if (format == IVG_KV_FP8_E4M3) IVG_TRY(need_fp8(e, "set_kv_format"));
+  e->kvc.set_format(format == IVG_KV_FP8_E4M3, k_scale, v_scale);
   return IVG_OK;
 }
 
-static bool kv8_engine(const ivg_engine* e) { return e->cfg.num_layers > 0 && !e->llm_x3 && e->llm_dt == BF16 && e->hd == 64 && e->kv_scales_dev && e->kv_amax; }
-static const char* const kKv8Needs = "the FP8 K/V cache needs a transformer with llm_dtype IVG_BF16 and head_dim 64";
-
 int ivg_set_kv_scales(ivg_engine* e, const float* scales) {
   if (!e) return IVG_ERR_INVALID;
-  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("set_kv_scales: ") + kKv8Needs);
+  IVG_TRY(need_fp8(e, "set_kv_scales"));
   if (!scales) return e->fail(IVG_ERR_INVALID, "set_kv_scales: null argument");
-  const int heads = e->heads;
-  const size_t n = (size_t)e->cfg.num_layers * 2 * heads;
-  for (size_t i = 0; i < n; ++i)
-    if (!kv8_scale_ok(scales[i]))
-      return e->fail(IVG_ERR_INVALID, "set_kv_scales: layer " + std::to_string(i / (2 * heads)) + ", " + ((i / heads) % 2 ? "v" : "k") + ", head " +
-                                          std::to_string(i % heads) + ": every scale must be a finite, positive power of two (2^-126 .. 2^126)");
-  // launches of an earlier call may still read the table: the device is idle before it is rewritten (this call synchronises)
-  API_CK(hipDeviceSynchronize());
-  API_CK(hipMemcpy(e->kv_scales_dev, scales, n * 4, hipMemcpyHostToDevice));
-  e->kv_scales.assign(scales, scales + n);
-  e->kv_table = true; ++e->kv_gen;
-  e->kv_len = 0; e->kv_B = 0; e->snap_valid = false; e->ids_valid = false;   // as ivg_set_kv_format: the kept cache was written with other scales
-  return IVG_OK;
+  for (size_t i = 0; i < e->kvc.table_n(); ++i)
+    if (!kv8_scale_ok(scales[i])) return e->fail(IVG_ERR_INVALID, "set_kv_scales: " + e->kvc.name(i) + ": every scale must be a finite, positive power of two (2^-126 .. 2^126)");
+  return e->kvc.set_scales(scales, e->err);
 }
 
 int ivg_get_kv_scales(ivg_engine* e, float* scales_out) {
   if (!e) return IVG_ERR_INVALID;
   if (e->cfg.num_layers <= 0 || !scales_out) return e->fail(IVG_ERR_INVALID, "get_kv_scales: engine without a transformer, or null argument");
-  const int heads = e->heads;
-  const size_t n = (size_t)e->cfg.num_layers * 2 * heads;
-  for (size_t i = 0; i < n; ++i) scales_out[i] = e->kv_table ? e->kv_scales[i] : ((i / heads) % 2 ? e->v_scale : e->k_scale);
+  e->kvc.get_scales(scales_out);
   return IVG_OK;
 }
 
 int ivg_kv_calibration_reset(ivg_engine* e) {
   if (!e) return IVG_ERR_INVALID;
-  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("kv_calibration_reset: ") + kKv8Needs);
-  API_CK(hipDeviceSynchronize());   // (a calibration pass still running would race with the memset)
-  API_CK(hipMemset(e->kv_amax, 0, (size_t)e->cfg.num_layers * 2 * e->heads * 4));
-  API_CK(hipDeviceSynchronize());
-  e->calib_pending = false;
-  return IVG_OK;
+  IVG_TRY(need_fp8(e, "kv_calibration_reset"));
+  return e->kvc.reset_amax(e->err);
+}
+
+// the action table (rows x action_dim, or null) embedded into workspace memory of the running pass: *out [rows][H] llm dtype, or null
+static int embed_actions(Run& r, const float* actions, int rows, const void** out) {
+  ivg_engine* e = r.e;
+  *out = nullptr;
+  if (!actions) return 0;
+  char* buf = (char*)e->ws.alloc((size_t)rows * e->cfg.hidden_size * dtype_size(e->llm_dt));
+  if (!r.planning && launch_action_embed(actions, e->act_w, e->act_b, buf, e->llm_dt, rows, e->cfg.action_dim, e->cfg.hidden_size, r.st))
+    return e->fail(IVG_ERR_HIP, "action_embed launch failed");
+  *out = buf;
+  return 0;
 }
 
 int ivg_kv_calibrate(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, const float* actions, int act_T, int ctx, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("kv_calibrate: ") + kKv8Needs);
+  IVG_TRY(need_fp8(e, "kv_calibrate"));
   if (!ids || ids_stride < L) return e->fail(IVG_ERR_INVALID, "kv_calibrate: null ids, or ids_stride below L");
   if (B <= 0 || L < 1 || L > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "kv_calibrate: batch or length exceeds capacity");
   if (actions && (e->cfg.action_dim <= 0 || !e->act_w)) return e->fail(IVG_ERR_INVALID, "kv_calibrate: actions given but the model is action-free");
   if (actions && (ctx < 1 || act_T < 1 || act_T > e->cfg.max_frames)) return e->fail(IVG_ERR_INVALID, "kv_calibrate: bad ctx / act_T");
-  const int Bc = std::min(e->cfg.max_batch, 128);   // the prompt pass's chunk: the cache (and its scratch) holds that many trajectories
-  const size_t es = dtype_size(e->llm_dt);
-  const int H = e->cfg.hidden_size, A = e->cfg.action_dim;
-  e->snap_valid = false; e->ids_valid = false;   // (the pass overwrites cache rows; Run::prefill zeroes kv_len / kv_B)
+  const int Bc = e->kvc.chunk;   // the prompt pass's chunk: the cache (and its scratch) holds that many trajectories
+  e->kvc.forget_kept();          // the pass overwrites cache rows
   int rc = plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    r.kv_amax = e->kv_amax;
+    r.kv_amax = e->kvc.amax;
     for (int b0 = 0; b0 < B; b0 += Bc) {
-      const int Bn = std::min(Bc, B - b0);
       const size_t m = e->ws.mark();
-      const void* act_emb = nullptr;
-      if (actions) {
-        char* buf = (char*)e->ws.alloc((size_t)Bn * act_T * H * es);
-        if (!r.planning && launch_action_embed(actions + (size_t)b0 * act_T * A, e->act_w, e->act_b, buf, e->llm_dt, Bn * act_T, A, H, r.st))
-          return e->fail(IVG_ERR_HIP, "action_embed launch failed");
-        act_emb = buf;
-      }
       // the teacher-forced prompt pass (actions on every sdf slot, as ivg_logits), no lm_head: kv_absmax_kernel follows each layer's rope_kv
-      int rc2 = r.prefill(r.planning ? nullptr : ids + (long)b0 * ids_stride, ids_stride, Bn, L, act_emb, act_T, ctx, true, nullptr, nullptr, nullptr);
-      if (rc2) return rc2;
+      PrefillReq q; q.ids = r.planning ? nullptr : ids + (long)b0 * ids_stride; q.ids_stride = ids_stride; q.B = std::min(Bc, B - b0); q.L = L;
+      q.act_T = act_T; q.ctx = ctx; q.all_slots = true;
+      IVG_TRY(embed_actions(r, actions ? actions + (size_t)b0 * act_T * e->cfg.action_dim : nullptr, q.B * act_T, &q.act_emb));
+      IVG_TRY(r.prefill(q));
       e->ws.reset(m);
     }
     return 0;
   });
-  if (rc == 0) { e->calib_stream = (hipStream_t)stream; e->calib_pending = true; }
+  if (rc == 0) { e->kvc.calib_stream = (hipStream_t)stream; e->kvc.calib_pending = true; }
   return rc;
 }
 
 int ivg_kv_calibration_finish(ivg_engine* e, int headroom_log2, float* amax_out, float* scales_out) {
   if (!e) return IVG_ERR_INVALID;
-  if (!kv8_engine(e)) return e->fail(IVG_ERR_INVALID, std::string("kv_calibration_finish: ") + kKv8Needs);
+  IVG_TRY(need_fp8(e, "kv_calibration_finish"));
   if (headroom_log2 < 0 || headroom_log2 > 8) return e->fail(IVG_ERR_INVALID, "kv_calibration_finish: headroom_log2 must be in [0, 8]");
-  const int heads = e->heads;
-  const size_t n = (size_t)e->cfg.num_layers * 2 * heads;
-  if (e->calib_pending) { API_CK(hipStreamSynchronize(e->calib_stream)); e->calib_pending = false; }
-  std::vector<uint32_t> bits(n);
-  API_CK(hipMemcpy(bits.data(), e->kv_amax, n * 4, hipMemcpyDeviceToHost));
-  std::vector<float> sc(n);
-  for (size_t i = 0; i < n; ++i) {
-    float a; memcpy(&a, &bits[i], 4);
-    if (amax_out) amax_out[i] = a;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    float a; memcpy(&a, &bits[i], 4);
-    if (bits[i] >= 0x7f800000u)
-      return e->fail(IVG_ERR_INVALID, "kv_calibration_finish: layer " + std::to_string(i / (2 * heads)) + ", " + ((i / heads) % 2 ? "v" : "k") + ", head " +
-                                          std::to_string(i % heads) + " saw " + (bits[i] > 0x7f800000u ? "NaN" : "Inf") + ": no scales installed");
-    // the smallest power of two s with amax / s <= 448 (= 0.875 * 2^9), times 2^headroom; exact, in integers
-    int ex = 0, p = 0;
-    if (a > 0.f) { const float mant = frexpf(a, &ex); p = (mant <= 0.875f ? ex - 9 : ex - 8) + headroom_log2; }
-    sc[i] = ldexpf(1.0f, std::min(126, std::max(-126, p)));
-  }
-  const int rc = ivg_set_kv_scales(e, sc.data());
-  if (rc) return rc;
-  if (scales_out) memcpy(scales_out, sc.data(), n * 4);
+  std::vector<uint32_t> bits; std::vector<float> sc;
+  long bad = -1;
+  IVG_TRY(e->kvc.calibrated_scales(headroom_log2, bits, sc, &bad, e->err));
+  if (amax_out) memcpy(amax_out, bits.data(), bits.size() * 4);
+  if (bad >= 0)
+    return e->fail(IVG_ERR_INVALID, "kv_calibration_finish: " + e->kvc.name(bad) + " saw " + (bits[bad] > 0x7f800000u ? "NaN" : "Inf") + ": no scales installed");
+  IVG_TRY(ivg_set_kv_scales(e, sc.data()));
+  if (scales_out) memcpy(scales_out, sc.data(), sc.size() * 4);
   return IVG_OK;
 }
 
@@ -613,70 +596,67 @@ void ivg_cache_destroy(ivg_engine* e, ivg_cache* c) {
   delete c;
 }
 
+// The opening checks of the ivg_generate* entries, in the order and the words each entry has always used (callers match on both).
+// own_err: the outcome of the entry's own argument check, which comes right after the transformer check (null: passed)
+enum GenEntry { GEN_PLAIN, GEN_SHARED, GEN_CONTINUE, GEN_EMBEDS };
+static int check_generate(ivg_engine* e, GenEntry entry, const char* own_err, int B, int L0, int n_new, const float* actions, int act_T, int ctx) {
+  const bool shared = entry == GEN_SHARED, cont = entry == GEN_CONTINUE, emb = entry == GEN_EMBEDS;
+  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "generate: engine was created without a transformer");
+  if (own_err) return e->fail(IVG_ERR_INVALID, own_err);
+  const int Bmax = emb ? e->kvc.chunk : B;   // an embeds call is one chunk of the cache
+  if (B <= 0 || B > Bmax || n_new < 1 || L0 < (shared || cont ? 2 : 1) || L0 + n_new > e->Lmax)
+    return e->fail(IVG_ERR_CAPACITY, emb ? "generate_embeds: batch " + std::to_string(B) + " / sequence of " + std::to_string(L0 + n_new) + " tokens exceeds the capacity (" +
+                                               std::to_string(Bmax) + " x " + std::to_string(e->Lmax) + ")"
+                                         : "generate: sequence of " + std::to_string(L0 + n_new) + " tokens exceeds the KV cache (" + std::to_string(e->Lmax) + ")");
+  if (!actions) return 0;
+  if (e->cfg.action_dim <= 0 || !e->act_w) return e->fail(IVG_ERR_INVALID, "generate: actions given but the model is action-free");
+  // a shared prefix is [0, L0 - 1): it may not contain an action slot (those carry per-trajectory actions), so the prompt is the
+  // context alone -- its last token, the first sdf slot, is fed per trajectory
+  if (shared && L0 != 257 * ctx) return e->fail(IVG_ERR_INVALID, "generate_shared: an action-conditioned shared prompt must hold exactly 257*ctx tokens");
+  if (L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0) return e->fail(IVG_ERR_INVALID, "generate: action-conditioned prompt must hold 257*ctx + 17*t tokens");
+  const int last = (L0 - 257 * ctx) / 17 + n_new / 17 + ctx - 1;  // highest action row read (prompt slots + forced sdf slots)
+  if (last >= act_T || act_T > e->cfg.max_frames) return e->fail(IVG_ERR_INVALID, "generate: action tensor too short (or longer than max_frames)");
+  return 0;
+}
+
 int ivg_generate(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
                  int ctx, const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "generate: engine was created without a transformer");
-  if (B <= 0 || n_new < 1 || L0 < 1 || L0 + n_new > e->Lmax)
-    return e->fail(IVG_ERR_CAPACITY, "generate: sequence of " + std::to_string(L0 + n_new) + " tokens exceeds the KV cache (" + std::to_string(e->Lmax) + ")");
-  if (actions && (e->cfg.action_dim <= 0 || !e->act_w)) return e->fail(IVG_ERR_INVALID, "generate: actions given but the model is action-free");
-  if (actions) {
-    if (L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0) return e->fail(IVG_ERR_INVALID, "generate: action-conditioned prompt must hold 257*ctx + 17*t tokens");
-    const int last = (L0 - 257 * ctx) / 17 + n_new / 17 + ctx - 1;  // highest action row read (prompt slots + forced sdf slots)
-    if (last >= act_T || act_T > e->cfg.max_frames) return e->fail(IVG_ERR_INVALID, "generate: action tensor too short (or longer than max_frames)");
-  }
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    return r.generate(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out, reward_out); });
+  IVG_TRY(check_generate(e, GEN_PLAIN, nullptr, B, L0, n_new, actions, act_T, ctx));
+  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out;
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
 int ivg_generate_shared(ivg_engine* e, const int64_t* prompts, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
                         const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out, float* reward_out,
                         ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "generate: engine was created without a transformer");
-  if (n_groups <= 0 || group_size <= 0) return e->fail(IVG_ERR_INVALID, "generate_shared: n_groups and group_size must be positive");
-  if (n_new < 1 || L0 < 2 || L0 + n_new > e->Lmax)
-    return e->fail(IVG_ERR_CAPACITY, "generate: sequence of " + std::to_string(L0 + n_new) + " tokens exceeds the KV cache (" + std::to_string(e->Lmax) + ")");
-  if (actions && (e->cfg.action_dim <= 0 || !e->act_w)) return e->fail(IVG_ERR_INVALID, "generate: actions given but the model is action-free");
-  if (actions) {
-    // the shared prefix is [0, L0 - 1): it may not contain an action slot (those carry per-trajectory actions), so the prompt is the
-    // context alone -- its last token, the first sdf slot, is fed per trajectory
-    if (L0 != 257 * ctx) return e->fail(IVG_ERR_INVALID, "generate_shared: an action-conditioned shared prompt must hold exactly 257*ctx tokens");
-    const int last = n_new / 17 + ctx - 1;
-    if (last >= act_T || act_T > e->cfg.max_frames) return e->fail(IVG_ERR_INVALID, "generate: action tensor too short (or longer than max_frames)");
-  }
-  const int B = n_groups * group_size;
-  if (group_size == 1)   // nothing to share: the plain entry (one prefill over all rows)
-    return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-      return r.generate(prompts, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out, reward_out, false, nullptr, nullptr, nullptr,
-                        force_sdf != 0); });
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    return r.generate(prompts, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out, reward_out, false, nullptr, nullptr, nullptr,
-                      force_sdf != 0, group_size); });
+  const bool sized = n_groups > 0 && group_size > 0;
+  const int B = sized ? n_groups * group_size : 1;
+  IVG_TRY(check_generate(e, GEN_SHARED, sized ? nullptr : "generate_shared: n_groups and group_size must be positive", B, L0, n_new, actions, act_T, ctx));
+  GenerateReq q; q.prompt = prompts; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out; q.force_sdf = force_sdf != 0;
+  q.group = group_size;   // 1: nothing to share -- the plain entry (one prefill over all rows)
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
 int ivg_generate_forced_sdf(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, int ctx, const float* uniforms,
                             int top_k, int64_t* ids_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "generate: engine was created without a transformer");
-  if (B <= 0 || n_new < 1 || L0 < 1 || L0 + n_new > e->Lmax)
-    return e->fail(IVG_ERR_CAPACITY, "generate: sequence of " + std::to_string(L0 + n_new) + " tokens exceeds the KV cache (" + std::to_string(e->Lmax) + ")");
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    return r.generate(prompt, prompt_stride, B, L0, n_new, nullptr, 0, ctx, uniforms, top_k, ids_out, nullptr, false, nullptr, nullptr, nullptr, true); });
+  IVG_TRY(check_generate(e, GEN_PLAIN, nullptr, B, L0, n_new, nullptr, 0, ctx));
+  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.ctx = ctx;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = true;
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
 int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions,
                           int act_T, int ctx, const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "generate: engine was created without a transformer");
-  if (!actions || e->cfg.action_dim <= 0 || !e->act_w) return e->fail(IVG_ERR_INVALID, "generate_continue: action-conditioned models only");
-  if (B <= 0 || n_new < 1 || L0 < 2 || L0 + n_new > e->Lmax)
-    return e->fail(IVG_ERR_CAPACITY, "generate: sequence of " + std::to_string(L0 + n_new) + " tokens exceeds the KV cache (" + std::to_string(e->Lmax) + ")");
-  if (L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0) return e->fail(IVG_ERR_INVALID, "generate: action-conditioned prompt must hold 257*ctx + 17*t tokens");
-  const int last = (L0 - 257 * ctx) / 17 + n_new / 17 + ctx - 1;
-  if (last >= act_T || act_T > e->cfg.max_frames) return e->fail(IVG_ERR_INVALID, "generate: action tensor too short (or longer than max_frames)");
-  if (e->kv_B != B || e->kv_len != L0 - 1)
-    return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kv_len) + " positions of " + std::to_string(e->kv_B) +
+  const bool act_ok = actions && e->cfg.action_dim > 0 && e->act_w;
+  IVG_TRY(check_generate(e, GEN_CONTINUE, act_ok ? nullptr : "generate_continue: action-conditioned models only", B, L0, n_new, actions, act_T, ctx));
+  if (!e->kvc.holds(B, L0 - 1))
+    return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
                                         " trajectories, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(B));
   {  // same (batch, length) is not enough: another caller may have used the model in between.  Compare the cached prefix
      // (token ids + the action rows baked into its sdf slots) with the prompt on the device (one stream synchronisation).
@@ -684,24 +664,22 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
     IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0, actions, act_T, ctx, (hipStream_t)stream, &same));
     if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
   }
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    return r.generate(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out, reward_out, true); });
+  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out; q.reuse_kv = true;
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                         void* hidden_out, int allow_reuse, int* reused_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   if (reused_out) *reused_out = 0;
-  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "generate: engine was created without a transformer");
-  if (!embeds || !new_ids_out) return e->fail(IVG_ERR_INVALID, "generate_embeds: null argument");
-  if (B <= 0 || B > std::min(e->cfg.max_batch, 128) || n_new < 1 || L0 < 1 || L0 + n_new > e->Lmax)
-    return e->fail(IVG_ERR_CAPACITY, "generate_embeds: batch " + std::to_string(B) + " / sequence of " + std::to_string(L0 + n_new) +
-                                         " tokens exceeds the capacity (" + std::to_string(std::min(e->cfg.max_batch, 128)) + " x " + std::to_string(e->Lmax) + ")");
+  IVG_TRY(check_generate(e, GEN_EMBEDS, embeds && new_ids_out ? nullptr : "generate_embeds: null argument", B, L0, n_new, nullptr, 0, 1));
   bool reuse = false;
   if (allow_reuse && L0 >= 2) IVG_TRY(kv_prefix_matches_embeds(e, embeds, B, L0, (hipStream_t)stream, &reuse));
   if (reused_out) *reused_out = reuse ? 1 : 0;
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    return r.generate(nullptr, 0, B, L0, n_new, nullptr, 0, 1, uniforms, top_k, nullptr, nullptr, reuse, embeds, new_ids_out, hidden_out); });
+  GenerateReq q; q.B = B; q.L0 = L0; q.n_new = n_new; q.uniforms = uniforms; q.top_k = top_k;
+  q.reuse_kv = reuse; q.embeds = embeds; q.new_ids_out = new_ids_out; q.hidden_out = hidden_out;
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
 int ivg_embed_tokens(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, void* out, ivg_stream stream) {
@@ -732,19 +710,12 @@ int ivg_reward_linear(ivg_engine* e, const void* hidden, int rows, float* out, i
 int ivg_logits(ivg_engine* e, const int64_t* ids, int B, int L, const float* actions, int act_T, int ctx, float* logits_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "logits: engine was created without a transformer");
-  if (B <= 0 || B > std::min(e->cfg.max_batch, 128) || L > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "logits: batch or length exceeds capacity");
+  if (B <= 0 || B > e->kvc.chunk || L > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "logits: batch or length exceeds capacity");
   if (actions && (e->cfg.action_dim <= 0 || !e->act_w)) return e->fail(IVG_ERR_INVALID, "logits: actions given but the model is action-free");
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    const void* act_emb = nullptr;
-    if (actions) {
-      char* buf = (char*)e->ws.alloc((size_t)B * act_T * e->cfg.hidden_size * dtype_size(e->llm_dt));
-      if (!r.planning) {
-        int rc = launch_action_embed(actions, e->act_w, e->act_b, buf, e->llm_dt, B * act_T, e->cfg.action_dim, e->cfg.hidden_size, r.st);
-        if (rc) return e->fail(IVG_ERR_HIP, "action_embed launch failed");
-      }
-      act_emb = buf;
-    }
-    return r.prefill(ids, L, B, L, act_emb, act_T, ctx, true, logits_out, nullptr, nullptr);
+    PrefillReq q; q.ids = ids; q.ids_stride = L; q.B = B; q.L = L; q.act_T = act_T; q.ctx = ctx; q.all_slots = true; q.logits_all = logits_out;
+    IVG_TRY(embed_actions(r, actions, B * act_T, &q.act_emb));
+    return r.prefill(q);
   });
 }
 
@@ -753,18 +724,13 @@ int ivg_eval_forward(ivg_engine* e, const int64_t* ids, const int64_t* labels, i
   if (!e) return IVG_ERR_INVALID;
   if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "eval_forward: engine was created without a transformer");
   if (!ids || !labels || !token_nll_out || !loss_rows_out) return e->fail(IVG_ERR_INVALID, "eval_forward: null argument");
-  if (B <= 0 || B > std::min(e->cfg.max_batch, 128) || L < 2 || L > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "eval_forward: batch or length exceeds capacity");
+  if (B <= 0 || B > e->kvc.chunk || L < 2 || L > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "eval_forward: batch or length exceeds capacity");
   if (actions && (e->cfg.action_dim <= 0 || !e->act_w)) return e->fail(IVG_ERR_INVALID, "eval_forward: actions given but the model is action-free");
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
-    const void* act_emb = nullptr;
-    if (actions) {
-      char* buf = (char*)e->ws.alloc((size_t)B * act_T * e->cfg.hidden_size * dtype_size(e->llm_dt));
-      if (!r.planning && launch_action_embed(actions, e->act_w, e->act_b, buf, e->llm_dt, B * act_T, e->cfg.action_dim, e->cfg.hidden_size, r.st))
-        return e->fail(IVG_ERR_HIP, "action_embed launch failed");
-      act_emb = buf;
-    }
-    int rc = r.prefill(ids, L, B, L, act_emb, act_T, ctx, true, nullptr, nullptr, nullptr, nullptr, hidden_out, labels, token_nll_out);
-    if (rc) return rc;
+    PrefillReq q; q.ids = ids; q.ids_stride = L; q.B = B; q.L = L; q.act_T = act_T; q.ctx = ctx; q.all_slots = true;
+    q.hidden_all = hidden_out; q.labels = labels; q.token_nll = token_nll_out;
+    IVG_TRY(embed_actions(r, actions, B * act_T, &q.act_emb));
+    IVG_TRY(r.prefill(q));
     if (!r.planning && launch_ce_reduce(token_nll_out, labels, B, L, e->cfg.vocab_size, loss_rows_out, r.st)) return e->fail(IVG_ERR_HIP, "ce_reduce launch failed");
     return 0;
   });
@@ -919,10 +885,10 @@ int ivg_profile_enable(ivg_engine* e, int k, int enable) {
 int ivg_profile_read(ivg_engine* e, int k, ivg_profile_stats* out) {
   if (!e || !out || k < 0 || k >= IVG_K_COUNT) return IVG_ERR_INVALID;
   API_CK(hipDeviceSynchronize());
+  out->launches = 0; out->total_ms = 0; out->total_flops = 0; out->total_bytes = 0;
   if (k == IVG_K_DECODE_ATTN) {
     // launch windows stamped by the kernel itself (it runs inside a replayed hipGraph, where HIP events cannot bracket
     // single launches): last ivg_generate call only; bytes = K and V rows read per launch
-    out->launches = 0; out->total_ms = 0; out->total_flops = 0; out->total_bytes = 0;
     if (!e->attn_prof) return IVG_OK;
     const int L = e->Lmax, nl = e->cfg.num_layers, NS = IVG_ATTN_PROF_SLOTS;
     std::vector<unsigned long long> h((size_t)nl * NS * 2 * L);
@@ -939,7 +905,7 @@ int ivg_profile_read(ivg_engine* e, int k, ivg_profile_stats* out) {
         }
         if (t == 0 || s == ~0ull || t < s) continue;
         const double ms = (double)(t - s) * 1e-5;   // 100 MHz wall clock -> ms
-        const double bytes = 2.0 * e->attn_prof_B * e->heads * (double)(p + 1) * e->hd * (double)(e->attn_prof_kvb > 0 ? (size_t)e->attn_prof_kvb : e->kv_elem_bytes());
+        const double bytes = 2.0 * e->attn_prof_B * e->heads * (double)(p + 1) * e->hd * (double)e->kvc.profiled_elem_bytes();
         out->launches++;
         out->total_ms += ms;
         out->total_bytes += bytes;
@@ -957,7 +923,6 @@ int ivg_profile_read(ivg_engine* e, int k, ivg_profile_stats* out) {
   }
   if (k == IVG_K_DECODE_GEMM) {
     // launch windows stamped by the GEMM kernels of the last ivg_generate call; bytes = the weight matrix a launch streams
-    out->launches = 0; out->total_ms = 0; out->total_flops = 0; out->total_bytes = 0;
     if (!e->gemm_prof) return IVG_OK;
     const int L = e->Lmax, nl = e->cfg.num_layers, NS = IVG_GEMM_PROF_SLOTS, ng = 4 * nl + 1;
     const double H = e->cfg.hidden_size, I = e->cfg.intermediate_size, V = e->cfg.vocab_size, es = (double)dtype_size(e->llm_dt);
@@ -985,7 +950,6 @@ int ivg_profile_read(ivg_engine* e, int k, ivg_profile_stats* out) {
     return IVG_OK;
   }
   ProfClass& pc = e->prof[k];
-  out->launches = 0; out->total_ms = 0; out->total_flops = 0; out->total_bytes = 0;
   for (auto& s : pc.used) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { out->launches++; out->total_ms += ms; out->total_flops += s.flops; out->total_bytes += s.bytes; }
@@ -1004,11 +968,8 @@ int ivg_profile_gemm_kinds(ivg_engine* e, double* mean_us, int64_t* launches) {
 // ---------------------------------------------------------------------------------------------- op-level hooks
 int ivg_op_igemm(const ivg_igemm_args* a, int dtype, ivg_stream stream) {
   IgemmArgs g;
-  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
-  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
-  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
-  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
-  g.flags = a->flags; g.alpha = a->alpha; g.nb0 = a->nb0; g.nb1 = a->nb1; g.nb2 = a->nb2;
+  igemm_op_args(g, a);
+  g.nb0 = a->nb0; g.nb1 = a->nb1; g.nb2 = a->nb2;
   for (int i = 0; i < 3; ++i) { g.sa[i] = a->sa[i]; g.sw[i] = a->sw[i]; g.sy[i] = a->sy[i]; }
   if (dtype == IVG_F32X3) { g.x3 = true; dtype = IVG_F32; }   // fp32 tensors, split-bf16 arithmetic: what Run::gemm sets for an x3 engine
   if (g.KH == 3 && g.KW == 3 && g.stride == 1 && !g.x3) {  // same dispatch as the engine: LDS-halo kernel first
@@ -1029,11 +990,7 @@ int ivg_op_conv_gn(const ivg_igemm_args* a, int dtype, void* gn_part, int groups
   // unit-test hook of the fused path: 3x3 convolution whose epilogue reduces the GroupNorm statistics of its output, followed by
   // the apply-only GroupNorm that consumes them.  Returns the number of statistics chunks per image (> 0) or a negative status.
   IgemmArgs g;
-  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
-  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
-  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
-  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
-  g.flags = a->flags; g.alpha = a->alpha;
+  igemm_op_args(g, a);
   g.gn_part = gn_part; g.gn_groups = groups;
   const int rc = launch_conv3x3(g, (DType)dtype, (hipStream_t)stream);
   if (rc != 0 || g.gn_chunks <= 0) return rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID;
@@ -1050,11 +1007,7 @@ int ivg_op_conv_subpixel(const ivg_igemm_args* a, int dtype, const void* w_sub, 
   // statistics from the epilogue; returns the chunks per image then (0 without), IVG_ERR_INVALID when the sub-pixel kernel did not run.
   if (!a->ups || !w_sub) return IVG_ERR_INVALID;
   IgemmArgs g;
-  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
-  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
-  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
-  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
-  g.flags = a->flags; g.alpha = a->alpha;
+  igemm_op_args(g, a);
   g.W_sub = w_sub; g.W_x3 = w_x3; g.W_sub_x3 = w_sub_x3;
   g.gn_part = gn_part; g.gn_groups = groups;
   const long long before = conv3x3_subpixel_launches();
@@ -1074,11 +1027,7 @@ int ivg_op_gn_conv(const ivg_igemm_args* a, int dtype, int groups, const float* 
   // ws: scratch of at least Nimg * (ceil(H*W/1024) * groups * 16 + Cin * 8) bytes.  Returns IVG_ERR_INVALID when the fused kernel
   // does not cover the shape.
   IgemmArgs g;
-  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
-  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
-  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
-  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
-  g.flags = a->flags; g.alpha = a->alpha;
+  igemm_op_args(g, a);
   const int P = a->Hin * a->Win, nch = gn_num_chunks(P);
   char* part = (char*)ws;
   char* coef = part + (size_t)a->Nimg * nch * groups * 16;
@@ -1093,11 +1042,7 @@ int ivg_op_conv_x3(const ivg_igemm_args* a, const void* w_x3, int groups, const 
   // unit-test hook of the split-bf16 3x3 convolution (fp32 tensors, weights pre-split by packing.py pack_x3); gamma != NULL: with
   // GroupNorm + SiLU of the input applied (and the result split) inside the staging, ws as in ivg_op_gn_conv
   IgemmArgs g;
-  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
-  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
-  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
-  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
-  g.flags = a->flags; g.alpha = a->alpha;
+  igemm_op_args(g, a);
   g.W_x3 = w_x3;
   if (!w_x3) return IVG_ERR_INVALID;
   if (gamma) {
@@ -1115,11 +1060,8 @@ int ivg_op_conv_x3(const ivg_igemm_args* a, const void* w_x3, int groups, const 
 static bool conv3x3_op_args(IgemmArgs& g, DType& dt, const ivg_igemm_args* a, int dtype, const void* w_x3, const void* w_sub, const void* w_sub_x3) {
   if (!a || (dtype != IVG_F32 && dtype != IVG_BF16 && dtype != IVG_F32X3)) return false;
   if (dtype == IVG_F32X3 && !w_x3) return false;
-  g.X = a->X; g.W = a->W; g.Y = a->Y; g.R = a->R; g.bias = a->bias;
-  g.Nimg = a->Nimg; g.Hin = a->Hin; g.Win = a->Win; g.Cin = a->Cin; g.ldx = a->ldx; g.Hout = a->Hout; g.Wout = a->Wout;
-  g.KH = a->KH; g.KW = a->KW; g.stride = a->stride; g.pad = a->pad; g.ups = a->ups; g.N = a->N; g.ldw = a->ldw;
-  g.c_img = a->c_img; g.c_pix = a->c_pix; g.c_ch = a->c_ch; g.c_grp = a->c_grp; g.c_grp_stride = a->c_grp_stride;
-  g.flags = a->flags; g.alpha = a->alpha; g.nb0 = a->nb0; g.nb1 = a->nb1; g.nb2 = a->nb2;
+  igemm_op_args(g, a);
+  g.nb0 = a->nb0; g.nb1 = a->nb1; g.nb2 = a->nb2;
   g.W_x3 = w_x3; g.W_sub = w_sub; g.W_sub_x3 = w_sub_x3;
   dt = dtype == IVG_BF16 ? BF16 : F32;
   return true;
@@ -1245,14 +1187,8 @@ int ivg_op_shared_decode_attn(const void* qkv, void* kc, void* vc, void* out, co
   if (B <= 0 || heads <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
   // a head dim the kernel has no instance for is refused here, before anything is allocated or launched
   if ((dtype != IVG_F32 && dtype != IVG_BF16) || !decode_attn_covers(hd, (DType)dtype)) return IVG_ERR_INVALID;
-  StepState* state = nullptr;
-  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_state_set(state, pos, 1, st);
-  if (!rc) rc = launch_decode_attn(qkv, kc, vc, out, cos_t, sin_t, B, heads, hd, Lmax, state, nullptr, (DType)dtype, st, P, G, row0);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(state);
-  return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
+  return one_step(pos, stream, [&](StepState* state, hipStream_t st) {
+    return launch_decode_attn(qkv, kc, vc, out, cos_t, sin_t, B, heads, hd, Lmax, state, nullptr, (DType)dtype, st, P, G, row0); });
 }
 
 int ivg_op_prefill_attn(void* qkv, void* kc, void* vc, void* vt, void* out, const float* cos_t, const float* sin_t, int B, int L, int heads,
@@ -1278,14 +1214,8 @@ int ivg_op_decode_attn24(const float* qkv, void* kc, void* vc, float* out, const
                          int P, int G, int row0, ivg_stream stream) {
   // unit-test hook of one decode-attention step over the 24-bit K / V cache of the x3 rollout (decode_attn24_kernel; G > 1: SHARED)
   if (B <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
-  StepState* state = nullptr;
-  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_state_set(state, pos, 1, st);
-  if (!rc) rc = launch_decode_attn24(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, st, P, G, row0);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(state);
-  return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
+  return one_step(pos, stream, [&](StepState* state, hipStream_t st) {
+    return launch_decode_attn24(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, st, P, G, row0); });
 }
 
 int ivg_op_kv8_pack(const void* k16, const void* v16, void* kc, void* vc, int BH, int L, int Lmax, float k_scale, float v_scale, ivg_stream stream) {
@@ -1298,14 +1228,8 @@ int ivg_op_decode_attn8(const void* qkv, void* kc, void* vc, void* out, const fl
   // unit-test hook of one decode-attention step over the FP8 K / V cache of a bf16 rollout (decode_attn8_kernel; G > 1: SHARED)
   if (B <= 0 || heads <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
   if (!kv8_scale_ok(k_scale) || !kv8_scale_ok(v_scale)) return IVG_ERR_INVALID;
-  StepState* state = nullptr;
-  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_state_set(state, pos, 1, st);
-  if (!rc) rc = launch_decode_attn8(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, k_scale, v_scale, st, P, G, row0);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(state);
-  return rc == 0 ? IVG_OK : IVG_ERR_HIP;
+  return one_step(pos, stream, [&](StepState* state, hipStream_t st) {
+    return launch_decode_attn8(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, k_scale, v_scale, st, P, G, row0); });
 }
 
 // the [heads] tables of a test hook are device memory: read back (after the stream's earlier work) and checked as ivg_set_kv_scales checks
@@ -1327,15 +1251,9 @@ int ivg_op_kv8_pack_heads(const void* k16, const void* v16, void* kc, void* vc, 
 int ivg_op_decode_attn8_heads(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
                               int P, int G, int row0, const float* k_scales, const float* v_scales, ivg_stream stream) {
   if (B <= 0 || heads <= 0 || G < 1 || P < 0 || P > pos || pos >= Lmax || row0 > 0) return IVG_ERR_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  if (!op_scales_ok(k_scales, v_scales, heads, st)) return IVG_ERR_INVALID;
-  StepState* state = nullptr;
-  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
-  int rc = launch_state_set(state, pos, 1, st);
-  if (!rc) rc = launch_decode_attn8(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, 1.0f, 1.0f, st, P, G, row0, k_scales, v_scales);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(state);
-  return rc == 0 ? IVG_OK : IVG_ERR_HIP;
+  if (!op_scales_ok(k_scales, v_scales, heads, (hipStream_t)stream)) return IVG_ERR_INVALID;
+  return one_step(pos, stream, [&](StepState* state, hipStream_t st) {
+    return launch_decode_attn8(qkv, kc, vc, out, cos_t, sin_t, B, heads, Lmax, state, nullptr, 1.0f, 1.0f, st, P, G, row0, k_scales, v_scales); });
 }
 
 int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, uint32_t* out, ivg_stream stream) {
@@ -1344,21 +1262,7 @@ int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, 
 }
 
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream) {
-  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return IVG_ERR_INVALID;   // as ivg_set_temperature
-  // one draw per row through the rollout's sampler kernel (token j = 1 of a prompt of length 0; no embedding: H = 0)
-  StepState* state = nullptr;
-  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_state_set(state, 0, 1, st);
-  SampleArgs sa{};
-  sa.logits = logits; sa.V = V; sa.uniforms = uniforms; sa.n_uni = 1; sa.top_k = top_k;
-  sa.ids_out = out; sa.ids_stride = 1; sa.L0 = 0; sa.forced_period = 0; sa.forced_token = 0;
-  sa.E = logits; sa.x = out; sa.H = 0; sa.act = nullptr; sa.act_T = 0; sa.ctx = 1; sa.slot0 = 0; sa.state = state;
-  sa.temperature = temperature;
-  if (!rc) rc = launch_sample_embed(sa, B, F32, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(state);
-  return rc ? IVG_ERR_HIP : IVG_OK;
+  return ivg_op_sample_top_p(logits, B, V, top_k, temperature, 1.0f /* SampleArgs' default: no nucleus filter */, uniforms, out, stream);
 }
 
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
@@ -1366,20 +1270,15 @@ int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temp
   if (!(temperature > 0.0f) || !std::isfinite(temperature)) return IVG_ERR_INVALID;   // as ivg_set_temperature
   if (!(top_p >= 0.0f && top_p <= 1.0f)) return IVG_ERR_INVALID;                       // as ivg_set_top_p
   // one draw per row through the rollout's sampler kernel (token j = 1 of a prompt of length 0; no embedding: H = 0)
-  StepState* state = nullptr;
-  if (hipMalloc((void**)&state, sizeof(StepState)) != hipSuccess) return IVG_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_state_set(state, 0, 1, st);
-  SampleArgs sa{};
-  sa.logits = logits; sa.V = V; sa.uniforms = uniforms; sa.n_uni = 1; sa.top_k = top_k;
-  sa.ids_out = out; sa.ids_stride = 1; sa.L0 = 0; sa.forced_period = 0; sa.forced_token = 0;
-  sa.E = logits; sa.x = out; sa.H = 0; sa.act = nullptr; sa.act_T = 0; sa.ctx = 1; sa.slot0 = 0; sa.state = state;
-  sa.temperature = temperature;
-  sa.top_p = top_p;
-  if (!rc) rc = launch_sample_embed(sa, B, F32, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(state);
-  return rc ? IVG_ERR_HIP : IVG_OK;
+  return one_step(0, stream, [&](StepState* state, hipStream_t st) {
+    SampleArgs sa{};
+    sa.logits = logits; sa.V = V; sa.uniforms = uniforms; sa.n_uni = 1; sa.top_k = top_k;
+    sa.ids_out = out; sa.ids_stride = 1; sa.L0 = 0; sa.forced_period = 0; sa.forced_token = 0;
+    sa.E = logits; sa.x = out; sa.H = 0; sa.act = nullptr; sa.act_T = 0; sa.ctx = 1; sa.slot0 = 0; sa.state = state;
+    sa.temperature = temperature;
+    sa.top_p = top_p;
+    return launch_sample_embed(sa, B, F32, st);
+  });
 }
 
 }  // extern "C"

@@ -14,6 +14,31 @@ namespace ivg {
 // GroupNorm statistics of an activation tensor that its PRODUCER (a conv3x3 epilogue) already reduced: [N][chunks][groups] double2
 struct GnStats { void* part = nullptr; int chunks = 0; };
 
+// One prompt pass over ids (or embeds) [B][L]: appends K / V of positions [0, L) to the cache and writes whichever outputs are set
+struct PrefillReq {
+  const int64_t* ids = nullptr; int64_t ids_stride = 0; int B = 0, L = 0;
+  const void* act_emb = nullptr; int act_T = 0, ctx = 1; bool all_slots = false;   // embedded action table [B][act_T][H], added on the first sdf slot, or on all
+  float* logits_all = nullptr;      // [B][L][V]
+  float* logits_last = nullptr; void* hidden_last = nullptr;   // [B][V], and the residual rows [B][H] of the last position they come from
+  const void* embeds = nullptr;     // [B][L][H] llm dtype: used instead of the embedding of ids
+  void* hidden_all = nullptr;       // [B][L][H] llm dtype: post-final-norm hidden states (eval heads)
+  const int64_t* labels = nullptr; float* token_nll = nullptr;   // [B][L]: shifted cross-entropy per position
+};
+
+// One rollout of n_new tokens after a prompt of L0, for B trajectories
+struct GenerateReq {
+  const int64_t* prompt = nullptr; int64_t prompt_stride = 0; int B = 0, L0 = 0, n_new = 0;
+  const float* actions = nullptr; int act_T = 0, ctx = 1;
+  const float* uniforms = nullptr; int top_k = 0;
+  int64_t* ids_out = nullptr; float* reward_out = nullptr;
+  bool reuse_kv = false;            // the cache already holds positions [0, L0 - 1) of this prompt
+  // embeds != null: llm.generate(inputs_embeds=...) -- the prompt is given as input embeddings, only the n_new tokens are
+  // returned (new_ids_out [B][n_new]); hidden_out [B][H]: post-norm hidden state of the last forward pass
+  const void* embeds = nullptr; int64_t* new_ids_out = nullptr; void* hidden_out = nullptr;
+  bool force_sdf = false;           // every 17th new token is the forced sdf even without actions (generate_without_action)
+  int group = 1;                    // > 1: shared-context rollout, `prompt` holds one row per group of `group` consecutive trajectories
+};
+
 struct Run {
   ivg_engine* e;
   hipStream_t st;
@@ -49,18 +74,8 @@ struct Run {
                  int group = 1 /* > 1: consecutive rows share their context (decoded / projected once per group) */);
 
   // ---- transformer (transformer.cpp)
-  int prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const void* act_emb, int act_T, int ctx, bool all_slots,
-              float* logits_all /* [B][L][V] or null */, float* logits_last /* [B][V] or null */, void* hidden_last,
-              const void* embeds = nullptr /* [B][L][H] llm dtype: used instead of the embedding of ids */,
-              void* hidden_all = nullptr /* [B][L][H] llm dtype: post-final-norm hidden states (eval heads) */,
-              const int64_t* labels = nullptr, float* token_nll = nullptr /* [B][L]: shifted cross-entropy per position */);
-  // embeds != null: llm.generate(inputs_embeds=...) -- the prompt is given as input embeddings, only the n_new tokens are
-  // returned (new_ids_out [B][n_new]); hidden_out [B][H]: post-norm hidden state of the last forward pass
-  int generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T, int ctx,
-               const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, bool reuse_kv = false,
-               const void* embeds = nullptr, int64_t* new_ids_out = nullptr, void* hidden_out = nullptr,
-               bool force_sdf = false /* every 17th new token is the forced sdf even without actions (generate_without_action) */,
-               int group = 1 /* > 1: shared-context rollout, `prompt` holds one row per group of `group` consecutive trajectories */);
+  int prefill(const PrefillReq& q);
+  int generate(const GenerateReq& q);
 
   // ---- measurement
   void prof_begin(DType dt, double flops, double bytes, int base = 0);   // base 0: igemm classes, 2: conv3x3 classes

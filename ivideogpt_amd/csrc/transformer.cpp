@@ -36,12 +36,10 @@ struct GenBuf {  // persistent decode-step buffers (fixed addresses so the captu
   int sh_P = 0, sh_G = 1, sh_row0 = 0;
 };
 
-static int gen_chunk(const ivg_engine* e) { return std::min(e->cfg.max_batch, 128); }
-
-static void gen_layout(const ivg_engine* e, GenBuf& g, char* base, size_t* total) {
+static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base = null: only the size
   const ivg_config& c = e->cfg;
   const DType dt = e->llm_dt;
-  const int Bc = gen_chunk(e), H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
+  const int Bc = e->kvc.chunk, H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
   g.Bc = Bc;
   g.ids_ld = e->Lmax;
   size_t off = 0;
@@ -57,19 +55,12 @@ static void gen_layout(const ivg_engine* e, GenBuf& g, char* base, size_t* total
   g.act_emb = take((size_t)Bc * std::max(1, c.max_frames) * H * esz(dt));
   g.last_act = (float*)take((size_t)Bc * std::max(1, c.max_frames) * std::max(1, c.action_dim) * 4);
   g.flag = (int*)take(256);
-  *total = off;
+  return off;
 }
 
 size_t gen_buffer_bytes(const ivg_engine* e) {
   GenBuf g;
-  size_t t = 0;
-  gen_layout(e, g, nullptr, &t);
-  return t;
-}
-
-static char* kc_ptr(const ivg_engine* e, int layer, int which) {
-  const size_t per = (size_t)gen_chunk(e) * e->heads * e->Lmax * e->hd * e->kv_elem_bytes();
-  return e->kv + ((size_t)layer * 2 + which) * per;
+  return gen_layout(e, g, nullptr);
 }
 
 // -------------------------------------------------------------------------------------------- prefill
@@ -77,10 +68,10 @@ static bool flash_prefill_covers(DType dt, int hd) {
   return sw().flash_prefill && dt == BF16 && hd == 64;   // IVG_FLASH_PREFILL=0: score GEMM + softmax + P.V GEMM (A/B tests)
 }
 
-int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const void* act_emb, int act_T, int ctx, bool all_slots,
-                 float* logits_all, float* logits_last, void* hidden_last, const void* embeds, void* hidden_all, const int64_t* labels,
-                 float* token_nll) {
+int Run::prefill(const PrefillReq& q) {
   const ivg_config& c = e->cfg;
+  const KvCache& kvc = e->kvc;
+  const int B = q.B, L = q.L;
   const DType dt = e->llm_dt;
   x3 = e->llm_x3;
   const int H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size, heads = e->heads, hd = e->hd, Lmax = e->Lmax;
@@ -94,28 +85,22 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
   char* act = (char*)e->ws.alloc((size_t)M * I * esz(dt));
   const bool flash = flash_prefill_covers(dt, hd);   // one-pass causal attention: no score matrix in HBM
   float* S = flash ? nullptr : (float*)e->ws.alloc((size_t)B * heads * L * Lp * 4);
-  // 24-bit cache (x3 rollout): RoPE writes one layer's fp32 K / V rows here -- the score GEMM reads K as a matrix -- and
-  // kv24_pack_kernel moves them into the cache's planes
-  const bool kv24 = e->kv24;
-  char* k32 = kv24 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 4) : nullptr;
-  char* v32 = kv24 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 4) : nullptr;
-  // FP8 cache (ivg_set_kv_format): the prompt pass itself is untouched -- it writes and reads one layer's bf16 K / V here instead of
-  // the cache (never packed in place: byte row t overlaps bf16 row t / 2), kv8_pack_kernel then stores the rows as e4m3
-  const bool kv8 = e->kv8();
-  char* k16 = kv8 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 2) : nullptr;
-  char* v16 = kv8 ? (char*)e->ws.alloc((size_t)B * heads * Lmax * hd * 2) : nullptr;
+  // a cache that is not in the engine's element type (24-bit planes, FP8): the pass itself is untouched -- RoPE writes one layer's K / V
+  // rows here (the score GEMM reads K as a matrix) and the cache packs them into its own rows
+  char* stage_k = kvc.staged() ? (char*)e->ws.alloc(kvc.stage_bytes(B)) : nullptr;
+  char* stage_v = kvc.staged() ? (char*)e->ws.alloc(kvc.stage_bytes(B)) : nullptr;
   char* Pm = flash ? nullptr : (char*)e->ws.alloc((size_t)B * heads * L * Lp * esz(dt));
   if (!planning) {
-    e->kv_len = 0; e->kv_B = 0;   // the cache rows are about to be overwritten (ivg_generate re-validates them at its end)
-    if (embeds) CK((int)hipMemcpyAsync(x, embeds, (size_t)M * H * esz(dt), hipMemcpyDeviceToDevice, st));
-    else CK(launch_embed(ids, ids_stride, e->embed, x, dt, B, L, H, V, st));
-    if (act_emb) {  // action embedding on the sdf slot(s): slot i (position 257*ctx - 1 + 17*i) gets action i + ctx - 1
+    e->kvc.forget_kept();   // the cache rows are about to be overwritten (ivg_generate re-validates them at its end)
+    if (q.embeds) CK((int)hipMemcpyAsync(x, q.embeds, (size_t)M * H * esz(dt), hipMemcpyDeviceToDevice, st));
+    else CK(launch_embed(q.ids, q.ids_stride, e->embed, x, dt, B, L, H, V, st));
+    if (q.act_emb) {  // action embedding on the sdf slot(s): slot i (position 257*ctx - 1 + 17*i) gets action i + ctx - 1
       for (int i = 0;; ++i) {
-        const int pos = 257 * ctx - 1 + 17 * i;
-        if (pos >= L || i + ctx - 1 >= act_T) break;
-        CK(launch_add_rows(x + (size_t)pos * H * esz(dt), (long)L * H, (const char*)act_emb + (size_t)(i + ctx - 1) * H * esz(dt),
-                           (long)act_T * H, B, H, dt, st));
-        if (!all_slots) break;
+        const int pos = 257 * q.ctx - 1 + 17 * i;
+        if (pos >= L || i + q.ctx - 1 >= q.act_T) break;
+        CK(launch_add_rows(x + (size_t)pos * H * esz(dt), (long)L * H, (const char*)q.act_emb + (size_t)(i + q.ctx - 1) * H * esz(dt),
+                           (long)q.act_T * H, B, H, dt, st));
+        if (!q.all_slots) break;
       }
     }
   }
@@ -124,12 +109,12 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
     if (!planning) CK(launch_add_rmsnorm(x, H, e->ones, xn, (int)M, H, c.rms_norm_eps, dt, st));
     ConvW wq; wq.w = w.wqkv; wq.cin = H; wq.cout = 3 * H;
     IVG_TRY(linear(dt, xn, M, wq, qkv, nullptr, 0, 0));
-    char* kl = kv24 ? k32 : (kv8 ? k16 : kc_ptr(e, l, 0));
+    char* kl = stage_k ? stage_k : kvc.ptr(l, 0);   // where this layer's roped K / V rows are in the engine's element type
+    char* vl = stage_v ? stage_v : kvc.ptr(l, 1);
     if (!planning) {
-      CK(launch_rope_kv(qkv, kl, kv24 ? v32 : (kv8 ? v16 : kc_ptr(e, l, 1)), e->vt, Lp, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, 0, dt, st));
-      if (kv24) CK(launch_kv24_pack(k32, v32, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, st));
-      if (kv_amax) CK(launch_kv_absmax(kl, kv8 ? v16 : kc_ptr(e, l, 1), B, heads, L, Lmax, kv_amax + (size_t)l * 2 * heads, st));
-      if (kv8) CK(launch_kv8_pack(k16, v16, kc_ptr(e, l, 0), kc_ptr(e, l, 1), B * heads, L, Lmax, e->k_scale, e->v_scale, st, heads, e->kv_tab(l, 0), e->kv_tab(l, 1)));
+      CK(launch_rope_kv(qkv, kl, vl, e->vt, Lp, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, 0, dt, st));
+      if (kv_amax) CK(launch_kv_absmax(kl, vl, B, heads, L, Lmax, kv_amax + (size_t)l * 2 * heads, st));
+      CK(kvc.store_staged(l, stage_k, stage_v, B, L, st));
     }
     if (flash) {
       if (!planning) CK(launch_flash_prefill(qkv, kl, e->vt, attn, B, L, Lp, heads, hd, Lmax, dt, st));
@@ -171,34 +156,34 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
     ConvW wd; wd.w = w.wdown; wd.cin = I; wd.cout = H;
     IVG_TRY(linear(dt, act, M, wd, x, x, 0, 0));
   }
-  if (hidden_all && !planning) {
+  if (q.hidden_all && !planning) {
     if (!e->final_norm) return e->fail(IVG_ERR_MISSING, "hidden states requested but 'llm.norm' is not in the weight table");
-    CK(launch_final_hidden(x, e->final_norm, hidden_all, (int)M, H, c.rms_norm_eps, dt, st));
+    CK(launch_final_hidden(x, e->final_norm, q.hidden_all, (int)M, H, c.rms_norm_eps, dt, st));
   }
-  if (logits_all) {
+  if (q.logits_all) {
     if (!planning) CK(launch_add_rmsnorm(x, H, e->ones, xn, (int)M, H, c.rms_norm_eps, dt, st));
     ConvW wl; wl.w = e->lm_head; wl.cin = H; wl.cout = V;
-    IVG_TRY(linear(dt, xn, M, wl, logits_all, nullptr, 0, 1));
+    IVG_TRY(linear(dt, xn, M, wl, q.logits_all, nullptr, 0, 1));
   }
-  if (token_nll) {
+  if (q.token_nll) {
     // loss without the [B][L][V] fp32 logits tensor (3.1 GB at B = 64, L = 751): lm_head over chunks of rows, each chunk reduced
     // to its per-position cross-entropy before the next one overwrites it
     const long Rc = std::min<long>(M, 4096);
     float* chunk = (float*)e->ws.alloc((size_t)Rc * V * 4);
-    if (!planning && !logits_all) CK(launch_add_rmsnorm(x, H, e->ones, xn, (int)M, H, c.rms_norm_eps, dt, st));
+    if (!planning && !q.logits_all) CK(launch_add_rmsnorm(x, H, e->ones, xn, (int)M, H, c.rms_norm_eps, dt, st));
     ConvW wl; wl.w = e->lm_head; wl.cin = H; wl.cout = V;
     for (long r0 = 0; r0 < M; r0 += Rc) {
       const long rows = std::min(Rc, M - r0);
       IVG_TRY(linear(dt, xn + (size_t)r0 * H * esz(dt), rows, wl, chunk, nullptr, 0, 1));
-      if (!planning) CK(launch_ce_rows(chunk, labels, r0, (int)rows, L, V, token_nll, st));
+      if (!planning) CK(launch_ce_rows(chunk, q.labels, r0, (int)rows, L, V, q.token_nll, st));
     }
   }
-  if (logits_last && !planning) {
+  if (q.logits_last && !planning) {
     // last position of every sequence -> residual rows hidden_last [B][H]; final RMSNorm is fused into the lm_head GEMM
-    CK((int)hipMemcpy2DAsync(hidden_last, (size_t)H * esz(dt), x + (size_t)(L - 1) * H * esz(dt), (size_t)L * H * esz(dt),
+    CK((int)hipMemcpy2DAsync(q.hidden_last, (size_t)H * esz(dt), x + (size_t)(L - 1) * H * esz(dt), (size_t)L * H * esz(dt),
                              (size_t)H * esz(dt), B, hipMemcpyDeviceToDevice, st));
     SkinnyArgs s;
-    s.X = hidden_last; s.W = e->lm_head; s.Y = logits_last; s.M = B; s.N = V; s.K = H; s.ldx = H; s.ldw = H; s.ldy = V;
+    s.X = q.hidden_last; s.W = e->lm_head; s.Y = q.logits_last; s.M = B; s.N = V; s.K = H; s.ldx = H; s.ldw = H; s.ldy = V;
     s.flags = IG_OUT_F32 | SK_NORM; s.eps = c.rms_norm_eps; s.lds_kb = e->decode_lds_kb;
     s.w_shared = e->in_flight() && sw().decode_w_shared;   // (the same policy as the steps' lm_head: one copy of the weights under several engines)
     CK(launch_skinny(s, dt, st));
@@ -212,26 +197,13 @@ int Run::prefill(const int64_t* ids, int64_t ids_stride, int B, int L, const voi
 // logits for token j+1, advance the device-side state.
 // (Splitting the rows into several concurrent chains on side streams was measured twice -- rounds 2 and 3, also on CU-masked
 // streams -- without gain: every launch is bound by what one CU ingests, half-batch GEMMs cost what full-batch ones do.  Removed.)
-static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, const SampleArgs& sa0, bool forward, bool skip_sample = false) {
-  constexpr int b0 = 0;
+static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, const SampleArgs& sa, bool forward, bool skip_sample = false) {
   const ivg_config& c = e->cfg;
   const DType dt = e->llm_dt;
   const int H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
   const size_t es = esz(dt);
   StepState* state = g.state;
-  char* x = g.x + (size_t)b0 * H * es;
-  char* qkv = g.qkv + (size_t)b0 * 3 * H * es;
-  char* attn = g.attn + (size_t)b0 * H * es;
-  char* act = g.act + (size_t)b0 * I * es;
-  float* logits = g.logits + (size_t)b0 * V;
-  const size_t kv_off = (size_t)b0 * e->heads * e->Lmax * e->hd * e->kv_elem_bytes();
-  SampleArgs sa = sa0;
-  sa.logits = logits;
-  if (sa.uniforms) sa.uniforms += (size_t)b0 * sa.n_uni;
-  sa.ids_out += (size_t)b0 * sa.ids_stride;
-  sa.x = x;
-  if (sa.act) sa.act = (const char*)sa.act + (size_t)b0 * sa.act_T * H * es;
-  sa.state = state;
+  char* x = g.x; char* qkv = g.qkv; char* attn = g.attn; char* act = g.act; float* logits = g.logits;
   if (!skip_sample) CK(launch_sample_embed(sa, B, dt, st));   // skip: x already holds the input row (embeds path, kept KV cache)
   if (!forward) return 0;
   // 5 launches per layer: RMSNorms are fused into the consuming GEMMs (weights pre-multiplied by the norm weight,
@@ -295,15 +267,7 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
     gprof(cur[0], 4 * l + 0);
     CK(launch_skinny(cur[0], dt, st));
     unsigned long long* aprof = e->attn_prof_on ? e->attn_prof + (size_t)l * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax : nullptr;
-    if (e->kv8())
-      CK(launch_decode_attn8(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->Lmax, state,
-                             aprof, e->k_scale, e->v_scale, st, g.sh_P, g.sh_G, g.sh_row0, e->kv_tab(l, 0), e->kv_tab(l, 1)));
-    else if (e->kv24)
-      CK(launch_decode_attn24(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->Lmax, state,
-                              aprof, st, g.sh_P, g.sh_G, g.sh_row0));
-    else
-      CK(launch_decode_attn(qkv, kc_ptr(e, l, 0) + kv_off, kc_ptr(e, l, 1) + kv_off, attn, e->rope_cos, e->rope_sin, B, e->heads, e->hd,
-                            e->Lmax, state, aprof, dt, st, g.sh_P, g.sh_G, g.sh_row0));
+    CK(e->kvc.decode_attn(l, qkv, attn, e->rope_cos, e->rope_sin, B, state, aprof, st, g.sh_P, g.sh_G, g.sh_row0));
     gprof(cur[1], 4 * l + 1);
     CK(launch_skinny(cur[1], dt, st));
     gprof(cur[2], 4 * l + 2);
@@ -322,33 +286,73 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------- captured step graphs (ivg_engine::graphs)
+// every exec is destroyed only once nothing queued on the stream can still be replaying it
+static int drop_graphs(ivg_engine* e, hipStream_t st) {
+  CK((int)hipStreamSynchronize(st));
+  for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
+  e->graphs.clear();
+  return 0;
+}
+
+// the graph of n_steps consecutive steps under `key`, captured on first use.  *out = null: no graph (IVG_GRAPH off, the null stream, or
+// the capture failed) -- the caller launches eagerly
+static int step_graph(ivg_engine* e, hipStream_t st, const std::string& key, int n_steps, const GenBuf& g, int Bc, const SampleArgs& sa, hipGraphExec_t* out) {
+  *out = nullptr;
+  if (!(e->use_graph && st != nullptr)) return 0;
+  if (e->graphs_gen != switches_generation()) {   // the switch table changed: no captured step of the old table can be replayed again
+    if (!e->graphs.empty()) IVG_TRY(drop_graphs(e, st));
+    e->graphs_gen = switches_generation();
+  }
+  const std::string k = key + (n_steps > 1 ? ":x" + std::to_string(n_steps) : "");
+  auto it = e->graphs.find(k);
+  if (it != e->graphs.end()) { *out = it->second; return 0; }
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t ex = nullptr;
+  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    int rc = 0;
+    for (int i = 0; i < n_steps && rc == 0; ++i) rc = step_body(e, st, g, Bc, sa, true);
+    const hipError_t ce = hipStreamEndCapture(st, &graph);
+    if (rc == 0 && ce == hipSuccess && graph && hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) == hipSuccess) {
+      if (e->graphs.size() >= 64) IVG_TRY(drop_graphs(e, st));   // bound the cache (a server fed ever new prompt lengths): drop all, recapture on demand
+      e->graphs[k] = ex;
+      *out = ex;
+    } else {
+      (void)hipGetLastError();
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+  } else {
+    (void)hipGetLastError();
+  }
+  return 0;
+}
+
 // group > 1 (ivg_generate_shared): `prompt` holds one row per GROUP of `group` consecutive trajectories (B = groups x group rows of
 // actions / uniforms / ids_out).  Per chunk: the prompts of the groups the chunk's rows belong to are prefilled ONCE each -- positions
 // [0, L0 - 1), into cache rows 0 .. n_groups-1 -- and every trajectory then feeds the prompt's last token itself (step j = 0, exactly the
 // kept-cache entry of the step-wise callers: that slot carries the row's own action), appending from position L0 - 1 on in its own
 // cache row; the decode attention reads key rows < L0 - 1 from the group's row (decode_attn_kernel SHARED).
-int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T, int ctx,
-                  const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, bool reuse_kv, const void* embeds,
-                  int64_t* new_ids_out, void* hidden_out, bool force_sdf, int group) {
+int Run::generate(const GenerateReq& q) {
+  const int B = q.B, L0 = q.L0, n_new = q.n_new, act_T = q.act_T, ctx = q.ctx, group = q.group;
+  const float* actions = q.actions; const float* uniforms = q.uniforms; const void* embeds = q.embeds; const bool reuse_kv = q.reuse_kv;
   const ivg_config& c = e->cfg;
   const DType dt = e->llm_dt;
   const int H = c.hidden_size, V = c.vocab_size;
   GenBuf g;
-  size_t tot = 0;
-  gen_layout(e, g, e->gen_buf, &tot);
+  gen_layout(e, g, e->gen_buf);
   const long Ltot = (long)L0 + n_new;
   const bool shared = group > 1;
-  if (planning) {
-    if (shared) return prefill(nullptr, 0, std::min((std::min(B, g.Bc) + group - 1) / group + 1, std::min(B, g.Bc)), L0 - 1, nullptr, 0, ctx, false, nullptr, nullptr, nullptr);
-    return reuse_kv ? 0 : prefill(nullptr, 0, std::min(B, g.Bc), L0, nullptr, 0, ctx, false, nullptr, nullptr, nullptr);
+  if (planning) {   // the prompt pass of the largest chunk (shared: of the most groups a chunk's rows can belong to)
+    PrefillReq p; p.ctx = ctx; p.L = shared ? L0 - 1 : L0;
+    p.B = shared ? std::min((std::min(B, g.Bc) + group - 1) / group + 1, std::min(B, g.Bc)) : std::min(B, g.Bc);
+    return reuse_kv && !shared ? 0 : prefill(p);
   }
-  e->kv_len = 0; e->kv_B = 0;   // set again once every launch of this call is queued
+  e->kvc.forget_kept();   // kept again once every launch of this call is queued
   const size_t es = esz(dt);
   if (embeds && B > g.Bc) return e->fail(IVG_ERR_CAPACITY, "generate (inputs_embeds): batch exceeds the KV-cache chunk");
   if (embeds && !e->emb_snap) {   // one-time: copy of the inputs the cache is built from (verifies later "same prefix" claims)
     if (hipMalloc((void**)&e->emb_snap, (size_t)g.Bc * e->Lmax * H * es) != hipSuccess) return e->fail(IVG_ERR_HIP, "hipMalloc of the embeddings snapshot failed");
   }
-  e->snap_valid = false; e->ids_valid = false;
   for (int b0 = 0; b0 < B; b0 += g.Bc) {
     const int Bc = std::min(g.Bc, B - b0);
     if (e->gemm_prof_on && e->gemm_prof) {
@@ -357,17 +361,18 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     }
     if (e->attn_prof_on) {  // fresh launch windows for this call: every stamp slot back to 0 (= not stamped)
       CK((int)hipMemsetAsync(e->attn_prof, 0, (size_t)c.num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8, st));
-      e->attn_prof_B = Bc; e->attn_prof_kvb = (int)e->kv_elem_bytes();
+      e->attn_prof_B = Bc; e->kvc.prof_eb = (int)e->kvc.elem_bytes();
     }
     if (shared) {   // every trajectory starts from a copy of its group's prompt; groups g_lo .. g_hi have rows in this chunk
       const int g_lo = b0 / group, g_hi = (b0 + Bc - 1) / group;
       g.sh_P = L0 - 1; g.sh_G = group; g.sh_row0 = g_lo * group - b0;
       // (attending the prompt rows once per 16 trajectories on the matrix cores -- tools/ubench/prefix_attn_mfma.hip -- shortens the
       // attention launch but needs a launch of its own per layer: every call measured slower, profiles/r06_shared_prefix_mfma_ab.txt)
-      CK(launch_expand_prompt_rows(prompt, prompt_stride, g.ids, g.ids_ld, Bc, L0, group, b0, st));
-      IVG_TRY(prefill(prompt + (long)g_lo * prompt_stride, prompt_stride, g_hi - g_lo + 1, L0 - 1, nullptr, 0, ctx, false, nullptr, nullptr, nullptr));
+      CK(launch_expand_prompt_rows(q.prompt, q.prompt_stride, g.ids, g.ids_ld, Bc, L0, group, b0, st));
+      PrefillReq p; p.ids = q.prompt + (long)g_lo * q.prompt_stride; p.ids_stride = q.prompt_stride; p.B = g_hi - g_lo + 1; p.L = L0 - 1; p.ctx = ctx;
+      IVG_TRY(prefill(p));
     } else if (!embeds)
-      CK((int)hipMemcpy2DAsync(g.ids, (size_t)g.ids_ld * 8, prompt + (long)b0 * prompt_stride, (size_t)prompt_stride * 8, (size_t)L0 * 8, Bc,
+      CK((int)hipMemcpy2DAsync(g.ids, (size_t)g.ids_ld * 8, q.prompt + (long)b0 * q.prompt_stride, (size_t)q.prompt_stride * 8, (size_t)L0 * 8, Bc,
                                hipMemcpyDeviceToDevice, st));
     if (uniforms)
       CK((int)hipMemcpy2DAsync(g.uni, (size_t)g.ids_ld * 4, uniforms + (long)b0 * n_new, (size_t)n_new * 4, (size_t)n_new * 4, Bc,
@@ -376,7 +381,11 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
       CK(launch_action_embed(actions + (long)b0 * act_T * c.action_dim, e->act_w, e->act_b, g.act_emb, dt, Bc * act_T, c.action_dim, H, st));
       if (B <= g.Bc) CK((int)hipMemcpyAsync(g.last_act, actions, (size_t)B * act_T * c.action_dim * 4, hipMemcpyDeviceToDevice, st));
     }
-    if (!reuse_kv && !shared) IVG_TRY(prefill(g.ids, g.ids_ld, Bc, L0, actions ? g.act_emb : nullptr, act_T, ctx, true, nullptr, g.logits, g.x, embeds));
+    if (!reuse_kv && !shared) {
+      PrefillReq p; p.ids = g.ids; p.ids_stride = g.ids_ld; p.B = Bc; p.L = L0; p.act_emb = actions ? g.act_emb : nullptr; p.act_T = act_T; p.ctx = ctx;
+      p.all_slots = true; p.logits_last = g.logits; p.hidden_last = g.x; p.embeds = embeds;
+      IVG_TRY(prefill(p));
+    }
     if (embeds) {   // keep what the cache is (being) built from: the whole prompt after a prefill, its last row on the kept-cache path
       const int p0 = reuse_kv ? L0 - 1 : 0;
       CK((int)hipMemcpy2DAsync(e->emb_snap + (size_t)p0 * H * es, (size_t)e->Lmax * H * es, (const char*)embeds + (size_t)p0 * H * es,
@@ -393,9 +402,9 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     SampleArgs sa{};
     sa.logits = g.logits; sa.V = V;
     sa.uniforms = uniforms ? g.uni : nullptr; sa.n_uni = g.ids_ld;
-    sa.top_k = top_k;
+    sa.top_k = q.top_k;
     sa.ids_out = g.ids; sa.ids_stride = g.ids_ld; sa.L0 = L0;
-    sa.forced_period = (actions || force_sdf) ? 17 : 0; sa.forced_token = V - 1;   // (no action embedding is added without actions: sa.act == null)
+    sa.forced_period = (actions || q.force_sdf) ? 17 : 0; sa.forced_token = V - 1;   // (no action embedding is added without actions: sa.act == null)
     sa.E = e->embed; sa.x = g.x; sa.H = H;
     sa.act = actions ? g.act_emb : nullptr; sa.act_T = act_T; sa.ctx = ctx;
     sa.slot0 = actions ? (L0 - 257 * ctx) / 17 : 0;  // a prompt that already holds t generated frames (MBRL step-wise rollout)
@@ -407,24 +416,22 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     // engine's LDS budget and the generation of the switch table, whose kernel-selection switches a replayed graph would otherwise keep ignoring)
     uint32_t t_bits; memcpy(&t_bits, &e->temperature, 4);
     uint32_t p_bits; memcpy(&p_bits, &e->top_p, 4);
-    uint32_t ks_bits; memcpy(&ks_bits, &e->k_scale, 4);
-    uint32_t vs_bits; memcpy(&vs_bits, &e->v_scale, 4);
     const std::string key = std::to_string(Bc) + ":" + std::to_string(t_bits) + ":" + std::to_string(p_bits) + ":" + std::to_string(e->decode_lds_kb) + ":" + std::to_string(switches_generation()) +
-                            ":" + (uniforms ? "s" : "g") + ":" + std::to_string(top_k) + ":" +
+                            ":" + (uniforms ? "s" : "g") + ":" + std::to_string(q.top_k) + ":" +
                             std::to_string(sa.forced_period) + ":" + std::to_string(ctx) + ":" + std::to_string(act_T) + ":" +
                             std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)
                             (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "") +
-                            (e->kv8() ? ":kv8:" + std::to_string(ks_bits) + ":" + std::to_string(vs_bits) + ":" + std::to_string(e->kv_gen) : "");   // (the cache format and its scales: kernel and arguments; kv_gen: scalars or which table)
+                            e->kvc.graph_key();   // (the cache format and its scales)
     // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
     // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
     auto reward = [&]() -> int {
-      if (hidden_out) {   // hidden_states[-1][-1] of HF generate: the last forward pass, after the final norm
+      if (q.hidden_out) {   // hidden_states[-1][-1] of HF generate: the last forward pass, after the final norm
         if (!e->final_norm) return e->fail(IVG_ERR_MISSING, "generate: hidden state requested but 'llm.norm' is not in the weight table");
-        CK(launch_final_hidden(g.x, e->final_norm, (char*)hidden_out + (size_t)b0 * H * es, Bc, H, c.rms_norm_eps, dt, st));
+        CK(launch_final_hidden(g.x, e->final_norm, (char*)q.hidden_out + (size_t)b0 * H * es, Bc, H, c.rms_norm_eps, dt, st));
       }
-      if (!reward_out) return 0;
+      if (!q.reward_out) return 0;
       if (!e->rew_w) return e->fail(IVG_ERR_MISSING, "generate: reward requested but reward_linear is not loaded");
-      CK(launch_rowdot(g.x, e->rew_w, e->rew_b, reward_out + b0, Bc, H, c.rms_norm_eps, dt, st));
+      CK(launch_rowdot(g.x, e->rew_w, e->rew_b, q.reward_out + b0, Bc, H, c.rms_norm_eps, dt, st));
       return 0;
     };
     int j = 1;
@@ -434,47 +441,10 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
     // the step sequence is position-independent (all step-dependent scalars live in StepState): it is captured once as a graph of
     // ONE step and once as a graph of `multi` consecutive steps -- the long rollouts replay the multi-step graph (a graph launch
     // costs the host ~10-16 us and leaves a bubble on the device; 8 steps per launch amortise it), the tail the single-step one
-    auto get_graph = [&](int n_steps, hipGraphExec_t* out) -> int {
-      *out = nullptr;
-      if (!(e->use_graph && st != nullptr)) return 0;
-      if (e->graphs_gen != switches_generation()) {   // the switch table changed: no captured step of the old table can be replayed again
-        if (!e->graphs.empty()) {
-          CK((int)hipStreamSynchronize(st));
-          for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-          e->graphs.clear();
-        }
-        e->graphs_gen = switches_generation();
-      }
-      const std::string k = key + (n_steps > 1 ? ":x" + std::to_string(n_steps) : "");
-      auto it = e->graphs.find(k);
-      if (it != e->graphs.end()) { *out = it->second; return 0; }
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t ex = nullptr;
-      if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        int rc = 0;
-        for (int i = 0; i < n_steps && rc == 0; ++i) rc = step_body(e, st, g, Bc, sa, true);
-        const hipError_t ce = hipStreamEndCapture(st, &graph);
-        if (rc == 0 && ce == hipSuccess && graph && hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) == hipSuccess) {
-          if (e->graphs.size() >= 64) {   // bound the cache (a server fed ever new prompt lengths): drop all, recapture on demand
-            CK((int)hipStreamSynchronize(st));
-            for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-            e->graphs.clear();
-          }
-          e->graphs[k] = ex;
-          *out = ex;
-        } else {
-          (void)hipGetLastError();
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-      } else {
-        (void)hipGetLastError();
-      }
-      return 0;
-    };
     constexpr int multi = 8;
     hipGraphExec_t exec = nullptr, exec_multi = nullptr;
-    if (j < n_new) IVG_TRY(get_graph(1, &exec));
-    if (exec && multi > 1 && n_new - j >= 2 * multi) IVG_TRY(get_graph(multi, &exec_multi));
+    if (j < n_new) IVG_TRY(step_graph(e, st, key, 1, g, Bc, sa, &exec));
+    if (exec && multi > 1 && n_new - j >= 2 * multi) IVG_TRY(step_graph(e, st, key, multi, g, Bc, sa, &exec_multi));
     while (j < n_new) {
       if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); j += multi; }
       else if (exec) { CK((int)hipGraphLaunch(exec, st)); ++j; }
@@ -485,21 +455,17 @@ int Run::generate(const int64_t* prompt, int64_t prompt_stride, int B, int L0, i
       IVG_TRY(step_body(e, st, g, Bc, sa, false));  // decide the last token (no forward)
     }
     if (embeds) {
-      CK((int)hipMemcpy2DAsync(new_ids_out + (long)b0 * n_new, (size_t)n_new * 8, g.ids + L0, (size_t)g.ids_ld * 8, (size_t)n_new * 8, Bc,
+      CK((int)hipMemcpy2DAsync(q.new_ids_out + (long)b0 * n_new, (size_t)n_new * 8, g.ids + L0, (size_t)g.ids_ld * 8, (size_t)n_new * 8, Bc,
                                hipMemcpyDeviceToDevice, st));
       if (n_new > 1)   // inputs of the positions the steps appended: the embeddings of the fed new tokens
         CK(launch_embed(g.ids + L0, g.ids_ld, e->embed, e->emb_snap + (size_t)L0 * H * es, dt, Bc, n_new - 1, H, V, st, (long)e->Lmax * H));
     } else {
-      CK((int)hipMemcpy2DAsync(ids_out + (long)b0 * Ltot, (size_t)Ltot * 8, g.ids, (size_t)g.ids_ld * 8, (size_t)Ltot * 8, Bc,
+      CK((int)hipMemcpy2DAsync(q.ids_out + (long)b0 * Ltot, (size_t)Ltot * 8, g.ids, (size_t)g.ids_ld * 8, (size_t)Ltot * 8, Bc,
                                hipMemcpyDeviceToDevice, st));
     }
   }
-  if (B <= g.Bc && !shared) {   // the last new token is decided but never fed (a shared-context cache is not a per-trajectory cache: never kept)
-    e->kv_len = L0 + n_new - 1; e->kv_B = B;
-    e->snap_valid = embeds != nullptr; e->ids_valid = embeds == nullptr;
-    e->last_act_T = actions ? act_T : 0;
-    e->last_ctx = ctx;
-  }
+  // the last new token is decided but never fed (a shared-context cache is not a per-trajectory cache: never kept)
+  if (B <= g.Bc && !shared) e->kvc.keep(L0 + n_new - 1, B, embeds != nullptr, actions ? act_T : 0, ctx);
   return 0;
 }
 
@@ -516,19 +482,18 @@ int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
                           int ctx, hipStream_t st, bool* ok) {
   *ok = false;
   GenBuf g;
-  size_t tot = 0;
-  gen_layout(e, g, e->gen_buf, &tot);
-  if (!e->ids_valid || e->kv_B != B || e->kv_len != L0 - 1 || B > g.Bc) return 0;
+  gen_layout(e, g, e->gen_buf);
+  if (!e->kvc.ids_valid || !e->kvc.holds(B, L0 - 1) || B > g.Bc) return 0;
   // the cache must have been built the same way: with / without actions, the same context length, the same action-table shape;
   // whatever cannot be compared row for row is a mismatch, never a silent "ok"
-  if ((actions != nullptr) != (e->last_act_T > 0)) return 0;
-  if (ctx != e->last_ctx) return 0;
-  if (actions && (e->last_act_T != act_T)) return 0;
+  if ((actions != nullptr) != (e->kvc.last_act_T > 0)) return 0;
+  if (ctx != e->kvc.last_ctx) return 0;
+  if (actions && (e->kvc.last_act_T != act_T)) return 0;
   CK((int)hipMemsetAsync(g.flag, 0, sizeof(int), st));
   CK(launch_compare_rows(prompt, prompt_stride * 8, g.ids, (long)g.ids_ld * 8, B, (long)(L0 - 1) * 8, g.flag, st));
   if (actions) {   // the action rows already baked into the cached sdf slots: slot i (position 257*ctx - 1 + 17*i < kv_len) used row i + ctx - 1
     const int A = e->cfg.action_dim;
-    const int slots = std::max(0, (e->kv_len - (257 * ctx - 1) + 16) / 17);
+    const int slots = std::max(0, (e->kvc.len - (257 * ctx - 1) + 16) / 17);
     if (slots > 0 && ctx - 1 + slots > act_T) return 0;   // the cached slots used action rows the presented table does not have
     if (slots > 0)
       CK(launch_compare_rows(actions + (long)(ctx - 1) * A, (long)act_T * A * 4, g.last_act + (long)(ctx - 1) * A, (long)act_T * A * 4, B,
@@ -540,9 +505,8 @@ int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
 int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, hipStream_t st, bool* ok) {
   *ok = false;
   GenBuf g;
-  size_t tot = 0;
-  gen_layout(e, g, e->gen_buf, &tot);
-  if (!e->snap_valid || !e->emb_snap || e->kv_B != B || e->kv_len != L0 - 1 || B > g.Bc) return 0;
+  gen_layout(e, g, e->gen_buf);
+  if (!e->kvc.snap_valid || !e->emb_snap || !e->kvc.holds(B, L0 - 1) || B > g.Bc) return 0;
   const size_t es = esz(e->llm_dt);
   const long H = e->cfg.hidden_size;
   CK((int)hipMemsetAsync(g.flag, 0, sizeof(int), st));

@@ -99,6 +99,18 @@ def test_shared_group_spanning_two_cache_chunks_and_ragged_row_tiles():
     assert torch.equal(out, ref)
 
 
+def test_shared_graph_replay_equals_eager(switches):
+    """IVG_GRAPH=1 on the native cache: a shared-context rollout replayed from its captured step graphs (the ``:sh...`` key; 40 new
+    tokens replay both the 8-step graph and the single-step tail after the eager first steps) gives the eager engine's tokens."""
+    cfg, sd, g = llama_fixture("llama_tiny_ctx1_free.npz")
+    rep = torch.from_numpy(g["prompt"]).repeat(2, 1).to(DEV)
+    kw = dict(do_sample=False, max_new_tokens=40, shared_context=2)
+    eager = make_llm(cfg, sd).generate(rep, **kw).cpu()
+    switches(IVG_GRAPH="1")
+    replayed = make_llm(cfg, sd).generate(rep, **kw).cpu()
+    assert torch.equal(replayed, eager), f"{(replayed != eager).sum().item()} tokens differ between graph replay and eager launches"
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_shared_full_width_small_llama(dtype):
     """12 layers / 768 wide, 514-token prompt, 5 samples (BASELINE config 1's shape: predict.py --repeat_times 5): fp32 -- greedy and
