@@ -263,6 +263,45 @@ int ivg_generate_forced_sdf(ivg_engine* e, const int64_t* prompt, int64_t prompt
 int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions,
                           int act_T, int ctx, const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, ivg_stream stream);
 
+/* Per-frame rewards and hidden states of one rollout call (the reference's generate is declared to return `reward (B, segment -
+ * context)` and leaves it a TODO, action_model.py:83-99,118-120; its forward reads reward_linear at the hidden state of every frame's
+ * 16th token, :198-204).
+ *
+ * Definition.  Under the forced-sdf schedule the new tokens are, per frame, 16 sampled tokens and then the forced sdf: new token j
+ * (1-based) is forced when j % 17 == 0.  Frame i (0-based, counted from THIS call's first new token) has outputs iff its 16th token,
+ * new token 17 i + 16, is FED to the transformer, i.e. 17 i + 16 <= n_new - 1 (the last new token is decided, never fed).  The number
+ * of frames with outputs is therefore F_out = n_new / 17 (integer division).
+ *   frame_hidden[b][i][:]  the final RMSNorm of the residual stream left by the forward pass that fed new token 17 i + 16, with the
+ *                          rounding of HF's hidden_states[-1] (what ivg_eval_forward's hidden_out and ivg_generate_embeds' hidden_out hold)
+ *   frame_rewards[b][i]    reward_linear on that state, in the arithmetic of ivg_generate's reward_out (norm weight folded into the
+ *                          head's weights)
+ * Consequences:
+ *   - all F frames of a rollout: pass n_new = 17 F; the last forced sdf is decided and dropped by the caller, as the MBRL loop does
+ *     with its 17 (mbrl/video_predictor.py:298-313);
+ *   - n_new % 17 == 0: frame_rewards[:, F_out - 1] is bit for bit the value reward_out of the entry below would hold;
+ *   - n_new = 17 F - 1 (the usual rollout length): F_out = F - 1, the last frame's 16th token is decided but not fed.
+ * Both outputs are produced inside the decode steps (one small kernel per step that acts only on a frame's 16th token, captured with
+ * the step graphs) into engine-owned buffers and copied out per cache chunk: no host work between the steps, any B.
+ *
+ * The entry stands for one of three: group_size == 1 and kept_cache == 0: ivg_generate (actions != NULL) / ivg_generate_forced_sdf
+ * (actions == NULL, force_sdf != 0); group_size > 1: ivg_generate_shared (prompt holds one row per group, B = groups * group_size rows
+ * of everything else); kept_cache != 0: ivg_generate_continue (group_size must be 1).  Arguments, tokens, the kept-cache verification
+ * and the cache kept afterwards are those of that entry.  On top of its checks, before anything is launched or written:
+ * IVG_ERR_INVALID unless the schedule is forced (actions != NULL or force_sdf != 0), n_new >= 17, L0 >= 257*ctx and
+ * (L0 - 257*ctx) % 17 == 0, B a multiple of group_size, and group_size == 1 with kept_cache; IVG_ERR_MISSING for frame_rewards_out
+ * without a reward head; IVG_ERR_CAPACITY for L0 + n_new beyond the cache.
+ *   ids_out            int64 (B, L0 + n_new)
+ *   frame_rewards_out  float32 (B, n_new / 17) or NULL
+ *   frame_hidden_out   (B, n_new / 17, hidden) in the llm dtype, or NULL
+ * With both NULL the call launches exactly what the entry it stands for launches. */
+int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new,
+                        const float* actions, int act_T, int ctx, const float* uniforms, int top_k,
+                        int group_size,   /* 1: as ivg_generate; > 1: as ivg_generate_shared (prompt: one row per group, B = groups * group_size) */
+                        int kept_cache,   /* != 0: as ivg_generate_continue (group_size must be 1) */
+                        int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out /* (B, n_new / 17) or NULL */,
+                        void* frame_hidden_out /* (B, n_new / 17, hidden) llm dtype or NULL */, ivg_stream stream);
+
 /* Embeds-level boundary of the step-wise caller (mbrl/video_predictor.py:286-317 runs these five ops per environment step).
  *
  * ivg_embed_tokens      HeadModelWithAction.get_input_embeddings (action_model.py:47-54): out[b][l][:] = embed_tokens[ids[b][l]],

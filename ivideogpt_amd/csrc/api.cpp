@@ -669,6 +669,36 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
+int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
+                        int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out, void* frame_hidden_out, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  const bool shared = group_size > 1, cont = kept_cache != 0;
+  const char* own = nullptr;
+  if (group_size < 1 || (shared && (B <= 0 || B % group_size != 0))) own = "generate_frames: B must be a positive multiple of a positive group_size";
+  else if (cont && shared) own = "generate_frames: a kept cache is per trajectory (group_size must be 1)";
+  else if (!actions && !force_sdf) own = "generate_frames: frames exist under the forced-sdf schedule only (actions or force_sdf)";
+  else if (cont && !(actions && e->cfg.action_dim > 0 && e->act_w)) own = "generate_continue: action-conditioned models only";
+  IVG_TRY(check_generate(e, shared ? GEN_SHARED : cont ? GEN_CONTINUE : GEN_PLAIN, own, B, L0, n_new, actions, act_T, ctx));
+  if (n_new < 17) return e->fail(IVG_ERR_INVALID, "generate_frames: a frame needs 17 new tokens (its 16th must be fed)");
+  if (ctx < 1 || L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0)
+    return e->fail(IVG_ERR_INVALID, "generate_frames: the prompt must hold 257*ctx + 17*t tokens (frames count from the first new token)");
+  if (frame_rewards_out && !e->rew_w) return e->fail(IVG_ERR_MISSING, "generate_frames: rewards requested but reward_linear is not loaded");
+  if (frame_hidden_out && !e->final_norm) return e->fail(IVG_ERR_MISSING, "generate_frames: hidden states requested but 'llm.norm' is not in the weight table");
+  if (cont) {   // as ivg_generate_continue
+    if (!e->kvc.holds(B, L0 - 1))
+      return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
+                                          " trajectories, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(B));
+    bool same = false;
+    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0, actions, act_T, ctx, (hipStream_t)stream, &same));
+    if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
+  }
+  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = force_sdf != 0; q.group = group_size; q.reuse_kv = cont;
+  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out;
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+}
+
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                         void* hidden_out, int allow_reuse, int* reused_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
@@ -1119,6 +1149,7 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "decode_gemm_gen3")) return decode_gemm_launches(3);
   if (name && !strcmp(name, "decode_gemm_gen2")) return decode_gemm_launches(2);
   if (name && !strcmp(name, "lpips_trunk_images")) return lpips_trunk_images();
+  if (name && !strcmp(name, "frame_heads")) return frame_heads_hits();
   return -1;
 }
 

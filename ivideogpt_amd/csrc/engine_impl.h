@@ -37,6 +37,8 @@ struct GenerateReq {
   const void* embeds = nullptr; int64_t* new_ids_out = nullptr; void* hidden_out = nullptr;
   bool force_sdf = false;           // every 17th new token is the forced sdf even without actions (generate_without_action)
   int group = 1;                    // > 1: shared-context rollout, `prompt` holds one row per group of `group` consecutive trajectories
+  // ivg_generate_frames: reward / post-norm hidden state of every frame whose 16th token is fed, [B][n_new / 17] and [B][n_new / 17][H]
+  float* frame_rewards_out = nullptr; void* frame_hidden_out = nullptr;
 };
 
 struct Run {

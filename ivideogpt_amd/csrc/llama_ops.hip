@@ -1867,6 +1867,62 @@ int launch_final_hidden(const void* x, const float* w, void* out, int B, int H, 
   return (int)hipGetLastError();
 }
 
+// Per-frame heads of a forced-sdf rollout (include/ivg.h ivg_generate_frames), one launch per decode step between the last
+// down-projection and lm_head (which advances the state): state->j is the new token this step FED.  Nothing happens unless that token
+// is a frame's 16th, j = 17 i + 16; then workgroup b leaves frame i of trajectory b: hid[b][i][:] with final_hidden_kernel's
+// arithmetic (all four waves) and rew[b][i] with rowdot_kernel's (wave 0 alone, its own stride-64 sums), so that either equals what
+// those kernels give on the same row bit for bit.  F: frames a row of rew / hid holds; a frame beyond it is never written.
+template <typename T>
+__global__ __launch_bounds__(256) void frame_heads_kernel(const T* __restrict__ x, const StepState* __restrict__ state, const float* __restrict__ rew_w,
+                                                          const float* __restrict__ rew_b, const float* __restrict__ norm_w,
+                                                          float* __restrict__ rew, T* __restrict__ hid, int H, int F, float eps) {
+  const int j = state->j;
+  if (j % 17 != 16) return;
+  const int i = j / 17;
+  if (i >= F) return;
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const T* row = x + (long)b * H;
+  if (hid) {
+    float ss = 0.f;
+    for (int c = tid; c < H; c += 256) { const float v = to_f32(row[c]); ss = fmaf(v, v, ss); }
+    ss = wave_sum(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    const float rs = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + eps);
+    T* out = hid + ((long)b * F + i) * H;
+    for (int c = tid; c < H; c += 256) {
+      const T n = from_f32<T>(to_f32(row[c]) * rs);
+      out[c] = from_f32<T>(to_f32(from_f32<T>(norm_w[c])) * to_f32(n));
+    }
+  }
+  if (rew && tid < 64) {
+    float s = 0.f, ss = 0.f;
+    for (int c = tid; c < H; c += 64) { const float v = to_f32(row[c]); s = fmaf(v, rew_w[c], s); ss = fmaf(v, v, ss); }
+    s = wave_sum(s);
+    ss = wave_sum(ss);
+    if (tid == 0) {
+      // rowdot_kernel rounds the product before it adds the bias (its select keeps the two apart): no contraction into an fma here
+#pragma clang fp contract(off)
+      const float r = s * rsqrtf(ss / (float)H + eps);
+      rew[(long)b * F + i] = r + rew_b[0];
+    }
+  }
+}
+
+int launch_frame_heads(const void* x, const StepState* state, const float* rew_w, const float* rew_b, const float* norm_w, float* rew, void* hid,
+                       int B, int H, int F, float eps, DType dt, hipStream_t st) {
+  if (B <= 0 || F <= 0 || (!rew && !hid)) return 0;
+  if ((rew && !(rew_w && rew_b)) || (hid && !norm_w)) return (int)hipErrorInvalidValue;
+  if (dt == BF16) hipLaunchKernelGGL(frame_heads_kernel<bf16_t>, dim3(B), dim3(256), 0, st, (const bf16_t*)x, state, rew_w, rew_b, norm_w, rew, (bf16_t*)hid, H, F, eps);
+  else hipLaunchKernelGGL(frame_heads_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)x, state, rew_w, rew_b, norm_w, rew, (float*)hid, H, F, eps);
+  return (int)hipGetLastError();
+}
+
+static std::atomic<long long> g_frame_heads_hits{0};
+void frame_heads_note(int hits) { g_frame_heads_hits += hits; }
+long long frame_heads_hits() { return g_frame_heads_hits.load(); }
+
 // ------------------------------------------------------------------------------------------------ eval heads
 // Shifted cross-entropy of teacher-forced logits (HF ForCausalLM loss, train_gpt.py:356-376): row r = (b, l) of a chunk of logits
 // [rows][V] fp32 predicts labels[b][l + 1]; nll[r] = logsumexp(logits[r]) - logits[r][target], 0 where the target is -100 (or l is

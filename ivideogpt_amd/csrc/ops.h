@@ -128,6 +128,14 @@ int launch_add_rows(void* x, long x_stride, const void* add, long add_stride, in
 int launch_rowdot(const void* h, const float* w, const float* bias, float* out, int B, int H, float eps, DType dt, hipStream_t st);
 // out[b] = final RMSNorm of the residual rows x[b] as HF reports them in hidden_states[-1] (normalised row rounded to T, times w)
 int launch_final_hidden(const void* x, const float* w, void* out, int B, int H, float eps, DType dt, hipStream_t st);
+// per-frame heads of a forced-sdf rollout (ivg_generate_frames), launched once per decode step BEFORE the lm_head that advances the
+// state: when the new token this step fed, state->j, is a frame's 16th (j = 17 i + 16, i < F), rew[b][i] = launch_rowdot's value and
+// hid[b][i][:] = launch_final_hidden's row of the residual row x[b] (bit for bit); any other step writes nothing.  rew / hid: [B][F]
+// floats / [B][F][H] T, either may be null
+int launch_frame_heads(const void* x, const StepState* state, const float* rew_w, const float* rew_b, const float* norm_w, float* rew, void* hid,
+                       int B, int H, int F, float eps, DType dt, hipStream_t st);
+void frame_heads_note(int hits);   // the host's count of the launches above that hit a frame (test hook, ivg_debug_counter("frame_heads"))
+long long frame_heads_hits();
 // eval heads: shifted cross-entropy per row of a logits chunk, per-trajectory (sum, count), action reconstruction squared error
 int launch_ce_rows(const float* logits, const int64_t* labels, long row0, int rows, int L, int V, float* nll, hipStream_t st);
 int launch_ce_reduce(const float* nll, const int64_t* labels, int B, int L, int V, float* out, hipStream_t st);

@@ -34,6 +34,10 @@ struct GenBuf {  // persistent decode-step buffers (fixed addresses so the captu
   // shared-context rollout (ivg_generate_shared; set per chunk by Run::generate): rows of the chunk in groups of sh_G sharing the cache
   // rows of their prompt -- see decode_attn_kernel SHARED.  sh_G = 1: off
   int sh_P = 0, sh_G = 1, sh_row0 = 0;
+  // per-frame heads (ivg_generate_frames): [Bc][F_max] rewards and [Bc][F_max][H] post-norm hidden rows, written by frame_heads_kernel
+  // inside the steps and copied to the caller per chunk, like ids.  fr_rew / fr_hid: which of them this call's steps write
+  float* frame_rew; char* frame_hid; int F_max;
+  bool fr_rew = false, fr_hid = false;
 };
 
 static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base = null: only the size
@@ -55,6 +59,9 @@ static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base
   g.act_emb = take((size_t)Bc * std::max(1, c.max_frames) * H * esz(dt));
   g.last_act = (float*)take((size_t)Bc * std::max(1, c.max_frames) * std::max(1, c.action_dim) * 4);
   g.flag = (int*)take(256);
+  g.F_max = std::max(1, e->Lmax / 17);   // a frame needs 17 new tokens
+  g.frame_rew = (float*)take((size_t)Bc * g.F_max * 4);
+  g.frame_hid = take((size_t)Bc * g.F_max * H * esz(dt));
   return off;
 }
 
@@ -281,6 +288,11 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
     layer_args(0, first);
     link_next(lm, first[0]);
   }
+  // per-frame heads: x is final here (the last down-projection is done, the next sampler has not run) and the state still names the
+  // token this step fed (lm_head advances it)
+  if (g.fr_rew || g.fr_hid)
+    CK(launch_frame_heads(x, state, e->rew_w, e->rew_b, e->final_norm, g.fr_rew ? g.frame_rew : nullptr, g.fr_hid ? g.frame_hid : nullptr, B, H,
+                          g.F_max, c.rms_norm_eps, dt, st));
   gprof(lm, 4 * c.num_layers);
   CK(launch_skinny(lm, dt, st));
   return 0;
@@ -342,6 +354,9 @@ int Run::generate(const GenerateReq& q) {
   gen_layout(e, g, e->gen_buf);
   const long Ltot = (long)L0 + n_new;
   const bool shared = group > 1;
+  g.fr_rew = q.frame_rewards_out != nullptr; g.fr_hid = q.frame_hidden_out != nullptr;
+  const bool frames = g.fr_rew || g.fr_hid;
+  const int F_out = n_new / 17;   // frames whose 16th token, new token 17 i + 16, is fed (<= n_new - 1)
   if (planning) {   // the prompt pass of the largest chunk (shared: of the most groups a chunk's rows can belong to)
     PrefillReq p; p.ctx = ctx; p.L = shared ? L0 - 1 : L0;
     p.B = shared ? std::min((std::min(B, g.Bc) + group - 1) / group + 1, std::min(B, g.Bc)) : std::min(B, g.Bc);
@@ -421,6 +436,7 @@ int Run::generate(const GenerateReq& q) {
                             std::to_string(sa.forced_period) + ":" + std::to_string(ctx) + ":" + std::to_string(act_T) + ":" +
                             std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)
                             (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "") +
+                            (frames ? std::string(":f") + (g.fr_rew ? "r" : "") + (g.fr_hid ? "h" : "") : "") +   // (the steps carry frame_heads_kernel)
                             e->kvc.graph_key();   // (the cache format and its scales)
     // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
     // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
@@ -434,10 +450,17 @@ int Run::generate(const GenerateReq& q) {
       CK(launch_rowdot(g.x, e->rew_w, e->rew_b, q.reward_out + b0, Bc, H, c.rms_norm_eps, dt, st));
       return 0;
     };
+    // steps of this call that feed new tokens [j0, j0 + n) and carry frame_heads_kernel: those that hit a frame (test hook)
+    auto note_frames = [&](int j0, int n) {
+      if (!frames) return;
+      int hits = 0;
+      for (int t = j0; t < j0 + n; ++t) hits += t % 17 == 16 && t / 17 < g.F_max;
+      frame_heads_note(hits);
+    };
     int j = 1;
     if (feed_last) IVG_TRY(step_body(e, st, g, Bc, sa, true, embeds != nullptr));   // j = 0: feed the prompt's last token
     if (n_new == 1) IVG_TRY(reward());
-    if (n_new >= 1) { IVG_TRY(step_body(e, st, g, Bc, sa, j < n_new)); ++j; }
+    if (n_new >= 1) { IVG_TRY(step_body(e, st, g, Bc, sa, j < n_new)); if (j < n_new) note_frames(j, 1); ++j; }
     // the step sequence is position-independent (all step-dependent scalars live in StepState): it is captured once as a graph of
     // ONE step and once as a graph of `multi` consecutive steps -- the long rollouts replay the multi-step graph (a graph launch
     // costs the host ~10-16 us and leaves a bubble on the device; 8 steps per launch amortise it), the tail the single-step one
@@ -446,9 +469,9 @@ int Run::generate(const GenerateReq& q) {
     if (j < n_new) IVG_TRY(step_graph(e, st, key, 1, g, Bc, sa, &exec));
     if (exec && multi > 1 && n_new - j >= 2 * multi) IVG_TRY(step_graph(e, st, key, multi, g, Bc, sa, &exec_multi));
     while (j < n_new) {
-      if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); j += multi; }
-      else if (exec) { CK((int)hipGraphLaunch(exec, st)); ++j; }
-      else { IVG_TRY(step_body(e, st, g, Bc, sa, true)); ++j; }
+      if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); note_frames(j, multi); j += multi; }
+      else if (exec) { CK((int)hipGraphLaunch(exec, st)); note_frames(j, 1); ++j; }
+      else { IVG_TRY(step_body(e, st, g, Bc, sa, true)); note_frames(j, 1); ++j; }
     }
     if (j == n_new && n_new > 1) {
       IVG_TRY(reward());
@@ -463,6 +486,12 @@ int Run::generate(const GenerateReq& q) {
       CK((int)hipMemcpy2DAsync(q.ids_out + (long)b0 * Ltot, (size_t)Ltot * 8, g.ids, (size_t)g.ids_ld * 8, (size_t)Ltot * 8, Bc,
                                hipMemcpyDeviceToDevice, st));
     }
+    if (g.fr_rew)
+      CK((int)hipMemcpy2DAsync(q.frame_rewards_out + (long)b0 * F_out, (size_t)F_out * 4, g.frame_rew, (size_t)g.F_max * 4, (size_t)F_out * 4, Bc,
+                               hipMemcpyDeviceToDevice, st));
+    if (g.fr_hid)
+      CK((int)hipMemcpy2DAsync((char*)q.frame_hidden_out + (size_t)b0 * F_out * H * es, (size_t)F_out * H * es, g.frame_hid, (size_t)g.F_max * H * es,
+                               (size_t)F_out * H * es, Bc, hipMemcpyDeviceToDevice, st));
   }
   // the last new token is decided but never fed (a shared-context cache is not a per-trajectory cache: never kept)
   if (B <= g.Bc && !shared) e->kvc.keep(L0 + n_new - 1, B, embeds != nullptr, actions ? act_T : 0, ctx);

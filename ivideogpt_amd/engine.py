@@ -267,6 +267,22 @@ class Engine:
                 if t is not None:
                     t.record_stream(self._run)
 
+    def generate_frames(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,
+                        frame_rewards=None, frame_hidden=None):
+        """ivg_generate_frames: the rollout of ``generate`` (``group_size`` > 1: of ``generate_shared``, ``prompt`` one row per group;
+        ``reuse_kv``: of ``ivg_generate_continue``) that also leaves ``frame_rewards`` (B, n_new // 17) float32 and / or ``frame_hidden``
+        (B, n_new // 17, hidden) in the llm dtype: reward and post-norm hidden state at the 16th token of every frame that was fed."""
+        B = out.shape[0]
+        L0 = prompt.shape[1]
+        act_T = actions.shape[1] if actions is not None else 0
+        with self.stream() as s:
+            self.check(self.lib.ivg_generate_frames(self.h, _ptr(prompt), prompt.stride(0), B, L0, int(n_new), _ptr(actions), act_T, int(ctx),
+                                                    _ptr(uniforms), int(top_k), int(group_size), int(bool(reuse_kv)), int(bool(force_sdf)), _ptr(out),
+                                                    _ptr(frame_rewards), _ptr(frame_hidden), s), "generate_frames")
+            for t in (prompt, out, actions, uniforms, frame_rewards, frame_hidden):
+                if t is not None:
+                    t.record_stream(self._run)
+
     def embed_tokens(self, ids, out):
         B, L = ids.shape
         with self.stream() as s:

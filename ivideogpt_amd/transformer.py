@@ -464,6 +464,32 @@ class LlamaForCausalLM:
     forward = __call__
 
 
+def _frames_of(max_new_tokens):
+    """Frames with per-frame outputs of a rollout of ``max_new_tokens`` (include/ivg.h ivg_generate_frames): the engine is asked for
+    ``max_new_tokens + 1`` tokens, whole frames of 16 + the forced sdf, so that the last frame's 16th token is fed too."""
+    if not (isinstance(max_new_tokens, int) and max_new_tokens >= 16 and (max_new_tokens + 1) % 17 == 0):
+        raise ValueError(f"per-frame outputs need max_new_tokens = 17 * frames - 1 (16 tokens per frame + the sdf between frames), not {max_new_tokens!r}")
+    return (max_new_tokens + 1) // 17
+
+
+def _generate_frames(llm, eng, ids, max_new_tokens, act, ctx, u, top_k, t, B0, reuse_kv, force_sdf, want_rewards, want_hidden):
+    """One ivg_generate_frames call of ``max_new_tokens + 1`` tokens -> (tokens (B, L0 + max_new_tokens), rewards (B, F) or None, hidden
+    (B, F, H) or None), rows in the caller's order (``t`` > 1: translated to and from the engine's group-major order)."""
+    B, L0 = ids.shape
+    F, n_new = _frames_of(max_new_tokens), max_new_tokens + 1
+    if u is not None and u.shape[1] < n_new:   # (the extra token is the forced sdf: its column is never read)
+        u = torch.cat([u, u.new_zeros(B, n_new - u.shape[1])], 1)
+    if u is not None:
+        u = u[:, :n_new].contiguous()
+    out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=llm.device)
+    fr = torch.empty(B, F, dtype=torch.float32, device=llm.device) if want_rewards else None
+    fh = torch.empty(B, F, llm._cfg["hidden_size"], dtype=llm.torch_dtype, device=llm.device) if want_hidden else None
+    eng.generate_frames(ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx,
+                        uniforms=_to_group_major(u, t, B0), top_k=top_k, group_size=t, reuse_kv=reuse_kv, force_sdf=force_sdf,
+                        frame_rewards=fr, frame_hidden=fh)
+    return _from_group_major(out, t, B0)[:, :-1], _from_group_major(fr, t, B0), _from_group_major(fh, t, B0)
+
+
 class HeadModelWithAction:
     """action_model.py:8-45: wraps an ``llm`` and adds ``action_linear`` (+ optional ``reward_linear``)."""
     supports_shared_context = True   # generate / detokenize accept shared_context= (libivg ivg_generate_shared / ivg_detokenize_shared)
@@ -569,7 +595,8 @@ class HeadModelWithAction:
 
     @torch.no_grad()
     def generate(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=50256,
-                 action=None, generator=None, uniforms=None, return_reward=False, reuse_cache=False, shared_context=None, top_p=None):
+                 action=None, generator=None, uniforms=None, return_reward=False, reuse_cache=False, shared_context=None, top_p=None,
+                 output_frame_hidden_states=False):
         """action_model.py:56-121: action (B, T, D); new token j is the forced sdf when j % 17 == 0; the i-th sdf slot's
         embedding gets ``action_linear(action[:, i + context - 1])``.  -> int64 (B, L0 + max_new_tokens).
         ``shared_context``: as ``LlamaForCausalLM.generate`` -- ``inputs_token`` is ``prompts.repeat(t, 1)`` (train_gpt.py:170, VP2's
@@ -578,14 +605,48 @@ class HeadModelWithAction:
         ``reuse_cache=True`` (step-wise rollouts, mbrl/video_predictor.py:286-317): the prompt is the previous call's full
         output plus the forced ``sdf``; the engine keeps the KV cache of that call and feeds only the last prompt token
         instead of prefilling the grown prompt again (raises AssertionError when the cache holds something else).
-        ``top_p`` (not in the reference's signature; an extension like ``shared_context``): as ``LlamaForCausalLM.generate``."""
+        ``top_p`` (not in the reference's signature; an extension like ``shared_context``): as ``LlamaForCausalLM.generate``.
+        ``return_reward="frames"`` (the reference declares ``reward (B, segment - context)`` and leaves it a TODO, action_model.py:83-99):
+        -> ``(tokens (B, L0 + max_new_tokens), rewards (B, F))``, ``F = (max_new_tokens + 1) // 17``: ``reward_linear`` at the hidden
+        state of every predicted frame's 16th token, the position the head is trained on (action_model.py:198-204), from ONE call
+        (include/ivg.h ivg_generate_frames).  ``max_new_tokens + 1`` must be a multiple of 17 (ValueError): the engine runs one token
+        more, the forced ``sdf`` that feeds the last frame's 16th token, and that column is dropped.  ``return_reward=True`` keeps its
+        meaning: one value (B), read at the last forward pass.
+        ``output_frame_hidden_states=True`` appends the post-norm hidden states (B, F, hidden) at those positions to the result, under
+        the same condition on ``max_new_tokens`` (with ``return_reward`` False or "frames").  Both work with ``shared_context`` and ``reuse_cache``."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
         top_p = _top_p_of(top_p, do_sample)
+        per_frame = isinstance(return_reward, str)
+        if per_frame and return_reward != "frames":
+            raise ValueError(f"return_reward must be False, True or 'frames', not {return_reward!r}")
+        if per_frame or output_frame_hidden_states:
+            _frames_of(max_new_tokens)   # (ValueError before any engine work)
+            if per_frame and not self.reward_prediction:
+                raise ValueError("return_reward='frames' needs a model with reward_prediction=True")
+            if return_reward is True:   # (its value is read one token earlier than a frame's: no single call yields both)
+                raise ValueError("output_frame_hidden_states goes with return_reward='frames' or False, not True")
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
         act = action.to(device=llm.device, dtype=torch.float32).contiguous()
+        if per_frame or output_frame_hidden_states:
+            # the extra token, the forced sdf after the last frame, is decided with the action row after the last one: a table that
+            # ends with the last frame's action gets a zero row (the token is dropped and never fed, the row reaches no output)
+            need = (L0 - 257 * self.context) // 17 + (max_new_tokens + 1) // 17 + self.context
+            if act.shape[1] < need:
+                act = torch.cat([act, act.new_zeros(B, need - act.shape[1], act.shape[2])], 1)
+            t, B0 = shared_prompt_groups(ids, shared_context) if (shared_context and not reuse_cache) else (1, B)
+            if not (t > 1 and L0 == 257 * self.context):
+                t, B0 = 1, B
+            u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
+            out, fr, fh = _generate_frames(llm, llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens,
+                                           act, self.context, u, top_k or llm._cfg["vocab_size"], t, B0, reuse_cache, False, per_frame,
+                                           output_frame_hidden_states)
+            res = (out,)
+            if per_frame:
+                res += (fr,)
+            return res + (fh,) if output_frame_hidden_states else res
         out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
         u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
         reward = torch.empty(B, dtype=torch.float32, device=llm.device) if return_reward else None
@@ -603,20 +664,28 @@ class HeadModelWithAction:
 
     @torch.no_grad()
     def generate_without_action(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, generator=None,
-                                uniforms=None, top_p=None):
+                                uniforms=None, top_p=None, output_frame_hidden_states=False):
         """action_model.py:123-152 (no caller in the reference): per future frame 16 sampled tokens, then the forced ``sdf`` -- the
         schedule of ``generate`` without any action embedding; the last forced ``sdf`` is dropped.  -> int64 (B, L0 + max_new_tokens).
         One prefill + cached steps instead of the reference's per-frame re-prefill (token-identical: same argument as ``generate``).
-        ``top_p`` (an extension, as in ``generate``): as ``LlamaForCausalLM.generate``."""
+        ``top_p`` (an extension, as in ``generate``): as ``LlamaForCausalLM.generate``.
+        ``output_frame_hidden_states=True``: -> ``(tokens, hidden (B, F, hidden))``, the post-norm hidden state at every predicted
+        frame's 16th token (as ``generate``); the tokens are those of the plain call."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
         top_p = _top_p_of(top_p, do_sample)
+        if output_frame_hidden_states:
+            _frames_of(max_new_tokens)   # (ValueError before any engine work)
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
         assert (max_new_tokens + 1) % (self.segment_length - self.context) == 0, "max_new_tokens must be (tokens_per_dyna + 1) * frames - 1"
         out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
         u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
+        if output_frame_hidden_states:
+            out, _, fh = _generate_frames(llm, llm._ensure(B).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens, None, self.context, u,
+                                          top_k or llm._cfg["vocab_size"], 1, B, False, True, False, True)
+            return out, fh
         llm._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_forced_sdf(ids, max_new_tokens, out, ctx=self.context, uniforms=u,
                                                                                top_k=top_k or llm._cfg["vocab_size"])
         return out

@@ -139,3 +139,42 @@ class VideoPredictor:
         if self.symlog:
             rewards = [symexp(r) for r in rewards]
         return obss, actions, torch.stack(rewards, 1).float()
+
+    @torch.no_grad()
+    def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None):
+        """Open-loop rollout of given action sequences (a CEM / MPPI / MPC planner's candidates, MBPO with a fixed plan) in three calls
+        instead of ``horizon`` steps: one ``encode_context``, one ``generate`` that also returns the hidden state at every frame's
+        16th token, where the reward head is trained (include/ivg.h ivg_generate_frames), and one ``detokenize``.  The rewards are
+        ``reward_linear`` of those hidden states, the very arithmetic of ``rollout``: for the same actions and uniforms the two give the
+        same rewards bit for bit (``generate(return_reward="frames")`` folds the final norm into the head and differs in the last bit).
+        obs [B, 9, H, W] in 0..255; actions [B * samples, horizon, A]: with ``samples`` > 1, rows ``b * samples .. (b + 1) * samples - 1``
+        are the candidates of observation b, whose context is prefilled, kept and decoded once (``shared_context``).
+        ``uniforms`` [B * samples, 17 * horizon - 1] (rows as ``actions``) or ``generator`` drive the sampler.
+        -> (obss [B * samples, horizon + 1, 9, H, W], actions [B * samples, horizon + 1, A], rewards [B * samples, horizon + 1, 1]):
+        ``rollout``'s layout, with its dummy step 0 and ``symexp``."""
+        from ivideogpt_amd.transformer import _from_group_major, _to_group_major
+        ctx, model = self.context_length, self.model
+        B, t = obs.shape[0], int(samples)
+        N, horizon = actions.shape[0], actions.shape[1]
+        assert t >= 1 and N == B * t, "actions must hold `samples` consecutive rows per observation"
+        obs = obs.to(self.device).float() / 255.
+        stack = list(torch.chunk(obs, 3, dim=1))                               # frame_stack = 3
+        prompt = self.tokenizer.encode_context(torch.stack(stack[-ctx:], dim=1), ctx)   # [B, 257*ctx], ends with the first sdf
+        act = actions.to(self.device).float()
+        # the engine's action table: row i + ctx - 1 goes onto the i-th sdf slot (rows below ctx - 1 are never read)
+        table = torch.cat([act.new_zeros(N, ctx - 1, act.shape[2]), act], 1)
+        # generate / detokenize take the candidates in ``prompt.repeat(t, 1)`` order (row k * B + b)
+        u = _from_group_major(uniforms.to(self.device).float().contiguous(), t, B) if uniforms is not None else None
+        tokens, hidden = model.generate(prompt.repeat(t, 1), do_sample=True, temperature=1.0, top_k=100, max_new_tokens=17 * horizon - 1,
+                                        action=_from_group_major(table.contiguous(), t, B), generator=generator, uniforms=u,
+                                        output_frame_hidden_states=True, shared_context=t if t > 1 else None)
+        rewards = model.reward_linear(hidden).squeeze(-1)                      # (B * samples, horizon)
+        clip = self.tokenizer.detokenize(tokens, ctx, shared_context=t if t > 1 else None)
+        rewards, clip = _to_group_major(rewards, t, B), _to_group_major(clip, t, B)
+        frames = [f.repeat_interleave(t, 0) if t > 1 else f for f in stack] + list(clip[:, ctx:].clamp(0.0, 1.0).unbind(1))
+        obss = torch.stack([torch.cat(frames[s:s + 3], dim=1) for s in range(horizon + 1)], 1).float()
+        actions = torch.cat([torch.zeros_like(act[:, :1]), act], 1).float()
+        rewards = torch.cat([torch.zeros_like(rewards[:, :1]), rewards], 1).unsqueeze(-1)
+        if self.symlog:
+            rewards = symexp(rewards)
+        return obss, actions, rewards.float()
