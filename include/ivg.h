@@ -302,6 +302,40 @@ int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
                         float* frame_rewards_out /* (B, n_new / 17) or NULL */,
                         void* frame_hidden_out /* (B, n_new / 17, hidden) llm dtype or NULL */, ivg_stream stream);
 
+/* Token log-probabilities and predictive entropy of a rollout: how sure the model was at every decision (HF generate's
+ * output_logits = True with compute_transition_scores(..., normalize_logits = True), without the (B, V) logits ever leaving the device).
+ *
+ * Definition.  For every DECIDED new token j (1-based) of trajectory b let z be the fp32 logits row (V entries) the sampler reads for
+ * that decision: the raw row as lm_head or the prompt pass left it, BEFORE the temperature division and before top-k and top-p, and
+ * tok the id the sampler wrote.  Natural logarithms.
+ *   logprob     = z[tok] - logsumexp(z)
+ *   entropy     = - sum_i p_i log p_i,  p = softmax(z), a term with p_i = 0 counted as 0 (rows may hold -inf)
+ *   max_logprob = max(z) - logsumexp(z), the log-confidence of the arg-max
+ * All three describe the MODEL's distribution: they do not depend on the temperature, top_k, top_p, or on greedy against sampled
+ * decoding (HF's `logits`, not its `scores`).  With greedy decoding logprob == max_logprob bit for bit.  Columns that decide nothing
+ * are exactly 0.0 in all three: the forced sdf tokens (j % 17 == 0 under the forced schedule); the j = 0 step of kept-cache and
+ * shared-context calls writes nothing at all.  A row whose maximum is not finite (NaN, +inf, all -inf) gives NaN in all three (such a
+ * row decides token 0); nothing is read outside the row.
+ * Out of scope: the probability under the FILTERED distribution actually drawn from (HF `scores`): it would need a second
+ * instantiation of the sampler, whose instances stay instruction-identical.  The scores come from a kernel of their own
+ * (token_scores_kernel, one workgroup per trajectory) launched inside the decode steps right after the sampler and captured with the
+ * step graphs: fp32 with max subtraction, entropy as log s - (sum e_i (z_i - m)) / s, every sum in one fixed order -- the same bits
+ * run to run, eager or replayed, in one call or step by step on the kept cache.  Engine-owned buffer, copied out per cache chunk.
+ *
+ * ivg_generate_scored: the arguments of ivg_generate_frames plus token_scores_out, and it stands for the same three entries.  The
+ * forced-schedule, n_new >= 17 and prompt-length conditions of ivg_generate_frames apply ONLY when a frame output is requested: with
+ * both frame outputs NULL it also serves the action-free ivg_generate (actions == NULL, force_sdf == 0).  With all three outputs NULL
+ * it launches exactly what the entry it stands for launches.  Rows are in the engine's order (group-major for a shared context).
+ * Refusals come before anything is launched or written and leave the outputs and the kept cache untouched.
+ *   token_scores_out  float32 (B, n_new, 3): logprob, entropy, max_logprob; or NULL
+ * ivg_generate_embeds_scored: ivg_generate_embeds (below) plus the same output; no column is forced there. */
+int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new,
+                        const float* actions, int act_T, int ctx, const float* uniforms, int top_k,
+                        int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out /* (B, n_new / 17) or NULL */,
+                        void* frame_hidden_out /* (B, n_new / 17, hidden) llm dtype or NULL */,
+                        float* token_scores_out /* (B, n_new, 3): logprob, entropy, max_logprob; or NULL */, ivg_stream stream);
+
 /* Embeds-level boundary of the step-wise caller (mbrl/video_predictor.py:286-317 runs these five ops per environment step).
  *
  * ivg_embed_tokens      HeadModelWithAction.get_input_embeddings (action_model.py:47-54): out[b][l][:] = embed_tokens[ids[b][l]],
@@ -322,6 +356,9 @@ int ivg_embed_tokens(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int 
 int ivg_action_linear(ivg_engine* e, const float* actions, int rows, void* out, ivg_stream stream);
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                         void* hidden_out, int allow_reuse, int* reused_out, ivg_stream stream);
+int ivg_generate_embeds_scored(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k,
+                               int64_t* new_ids_out, void* hidden_out, int allow_reuse, int* reused_out,
+                               float* token_scores_out /* (B, n_new, 3) as ivg_generate_scored; or NULL */, ivg_stream stream);
 int ivg_reward_linear(ivg_engine* e, const void* hidden, int rows, float* out, ivg_stream stream);
 
 /* Teacher-forced logits (LlamaForCausalLM.forward / HeadModelWithAction.forward, action_model.py:154-185):
@@ -534,6 +571,10 @@ int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperatur
 /* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
                         ivg_stream stream);
+/* the arithmetic of token_scores_kernel (ivg_generate_scored has the definition) on given rows: logits (B, V) float32, ids (B) the
+ * chosen token of each row (not forced, j >= 1), out (B, 3) = logprob, entropy, max_logprob; V <= 256 * 72; an id outside [0, V) gives
+ * a NaN logprob without a read */
+int ivg_op_token_scores(const float* logits, const int64_t* ids, int B, int V, float* out, ivg_stream stream);
 /* LPIPS pieces (csrc/lpips.hip).  ivg_op_lpips_features: n images (n, 3, H, W) in [0, 1] (IVG_F32 / IVG_BF16) through the VGG-16 trunk,
  * taps_out[k] (n, H >> k, W >> k, 64 / 128 / 256 / 512 / 512) NHWC float32 (NULL entries are skipped); ws as ivg_lpips_rows (one image
  * at least).  ivg_op_lpips_head: out[i] = mean over the P pixels of sum_c lin[c] (f0n - f1n)^2 with f normalised per pixel by
@@ -548,7 +589,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

@@ -5,7 +5,7 @@ There is no CPU / eager-PyTorch compute path: using a model without the built li
 non-GPU device, raises.
 """
 from .vq_model import CompressiveVQModel, DetokenizeCache  # noqa: F401
-from .transformer import HeadModelWithAction, LlamaForCausalLM  # noqa: F401
+from .transformer import HeadModelWithAction, LlamaForCausalLM, TokenScores  # noqa: F401
 from . import switches, weights  # noqa: F401
 
-__all__ = ["CompressiveVQModel", "DetokenizeCache", "HeadModelWithAction", "LlamaForCausalLM", "switches", "weights"]
+__all__ = ["CompressiveVQModel", "DetokenizeCache", "HeadModelWithAction", "LlamaForCausalLM", "TokenScores", "switches", "weights"]

@@ -669,19 +669,22 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
-int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
-                        int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
-                        float* frame_rewards_out, void* frame_hidden_out, ivg_stream stream) {
+// ivg_generate_frames (need_frames: its conditions on the schedule and the lengths always hold) and ivg_generate_scored (they hold only
+// when a frame output is asked for: without one the entry also stands for the action-free ivg_generate)
+static int generate_frames_scored(ivg_engine* e, bool need_frames, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new,
+                                  const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int group_size, int kept_cache,
+                                  int force_sdf, int64_t* ids_out, float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out,
+                                  ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   const bool shared = group_size > 1, cont = kept_cache != 0;
   const char* own = nullptr;
   if (group_size < 1 || (shared && (B <= 0 || B % group_size != 0))) own = "generate_frames: B must be a positive multiple of a positive group_size";
   else if (cont && shared) own = "generate_frames: a kept cache is per trajectory (group_size must be 1)";
-  else if (!actions && !force_sdf) own = "generate_frames: frames exist under the forced-sdf schedule only (actions or force_sdf)";
+  else if (need_frames && !actions && !force_sdf) own = "generate_frames: frames exist under the forced-sdf schedule only (actions or force_sdf)";
   else if (cont && !(actions && e->cfg.action_dim > 0 && e->act_w)) own = "generate_continue: action-conditioned models only";
   IVG_TRY(check_generate(e, shared ? GEN_SHARED : cont ? GEN_CONTINUE : GEN_PLAIN, own, B, L0, n_new, actions, act_T, ctx));
-  if (n_new < 17) return e->fail(IVG_ERR_INVALID, "generate_frames: a frame needs 17 new tokens (its 16th must be fed)");
-  if (ctx < 1 || L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0)
+  if (need_frames && n_new < 17) return e->fail(IVG_ERR_INVALID, "generate_frames: a frame needs 17 new tokens (its 16th must be fed)");
+  if (need_frames && (ctx < 1 || L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0))
     return e->fail(IVG_ERR_INVALID, "generate_frames: the prompt must hold 257*ctx + 17*t tokens (frames count from the first new token)");
   if (frame_rewards_out && !e->rew_w) return e->fail(IVG_ERR_MISSING, "generate_frames: rewards requested but reward_linear is not loaded");
   if (frame_hidden_out && !e->final_norm) return e->fail(IVG_ERR_MISSING, "generate_frames: hidden states requested but 'llm.norm' is not in the weight table");
@@ -695,12 +698,31 @@ int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
   }
   GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
   q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = force_sdf != 0; q.group = group_size; q.reuse_kv = cont;
-  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out;
+  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+}
+
+int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
+                        int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out, void* frame_hidden_out, ivg_stream stream) {
+  return generate_frames_scored(e, true, prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, group_size, kept_cache, force_sdf,
+                                ids_out, frame_rewards_out, frame_hidden_out, nullptr, stream);
+}
+
+int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
+                        int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
+  return generate_frames_scored(e, frame_rewards_out || frame_hidden_out, prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k,
+                                group_size, kept_cache, force_sdf, ids_out, frame_rewards_out, frame_hidden_out, token_scores_out, stream);
 }
 
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                         void* hidden_out, int allow_reuse, int* reused_out, ivg_stream stream) {
+  return ivg_generate_embeds_scored(e, embeds, B, L0, n_new, uniforms, top_k, new_ids_out, hidden_out, allow_reuse, reused_out, nullptr, stream);
+}
+
+int ivg_generate_embeds_scored(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
+                               void* hidden_out, int allow_reuse, int* reused_out, float* token_scores_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   if (reused_out) *reused_out = 0;
   IVG_TRY(check_generate(e, GEN_EMBEDS, embeds && new_ids_out ? nullptr : "generate_embeds: null argument", B, L0, n_new, nullptr, 0, 1));
@@ -708,7 +730,7 @@ int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_
   if (allow_reuse && L0 >= 2) IVG_TRY(kv_prefix_matches_embeds(e, embeds, B, L0, (hipStream_t)stream, &reuse));
   if (reused_out) *reused_out = reuse ? 1 : 0;
   GenerateReq q; q.B = B; q.L0 = L0; q.n_new = n_new; q.uniforms = uniforms; q.top_k = top_k;
-  q.reuse_kv = reuse; q.embeds = embeds; q.new_ids_out = new_ids_out; q.hidden_out = hidden_out;
+  q.reuse_kv = reuse; q.embeds = embeds; q.new_ids_out = new_ids_out; q.hidden_out = hidden_out; q.token_scores_out = token_scores_out;
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
 
@@ -1150,6 +1172,7 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "decode_gemm_gen2")) return decode_gemm_launches(2);
   if (name && !strcmp(name, "lpips_trunk_images")) return lpips_trunk_images();
   if (name && !strcmp(name, "frame_heads")) return frame_heads_hits();
+  if (name && !strcmp(name, "token_scores")) return token_scores_launches();
   return -1;
 }
 
@@ -1310,6 +1333,12 @@ int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temp
     sa.top_p = top_p;
     return launch_sample_embed(sa, B, F32, st);
   });
+}
+
+int ivg_op_token_scores(const float* logits, const int64_t* ids, int B, int V, float* out, ivg_stream stream) {
+  if (!logits || !ids || !out || B <= 0 || V < 1 || V > 256 * 72) return IVG_ERR_INVALID;
+  // the rollout's score kernel on given rows and ids: new token j = 1 of a prompt of length 0, no forced schedule, one column
+  return one_step(0, stream, [&](StepState* state, hipStream_t st) { return launch_token_scores(logits, V, state, ids, 1, 0, 0, out, 1, B, st); });
 }
 
 }  // extern "C"

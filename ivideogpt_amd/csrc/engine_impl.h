@@ -39,6 +39,8 @@ struct GenerateReq {
   int group = 1;                    // > 1: shared-context rollout, `prompt` holds one row per group of `group` consecutive trajectories
   // ivg_generate_frames: reward / post-norm hidden state of every frame whose 16th token is fed, [B][n_new / 17] and [B][n_new / 17][H]
   float* frame_rewards_out = nullptr; void* frame_hidden_out = nullptr;
+  // ivg_generate_scored / ivg_generate_embeds_scored: [B][n_new][3] = logprob, entropy, max logprob of every decided new token
+  float* token_scores_out = nullptr;
 };
 
 struct Run {

@@ -1923,6 +1923,88 @@ static std::atomic<long long> g_frame_heads_hits{0};
 void frame_heads_note(int hits) { g_frame_heads_hits += hits; }
 long long frame_heads_hits() { return g_frame_heads_hits.load(); }
 
+// Token scores of a rollout (include/ivg.h ivg_generate_scored), one launch per decode step directly after the sampler: state->j is
+// the new token the sampler just DECIDED, ids[b][L0 + j - 1] the id it stored, logits[b][:] the raw fp32 row it read (before the
+// temperature division and the top-k / top-p filters; lm_head of this step overwrites it later in stream order).  Workgroup b leaves
+// out[b][j - 1][0..2] = { z[tok] - lse(z), H(softmax(z)), max(z) - lse(z) }; a forced column (j % period == 0) gets three zeros,
+// j = 0 (the step that only feeds the prompt's last token) and j > cols write nothing.  fp32, max subtraction, entropy as
+// log s - (sum e_i (z_i - m)) / s with the terms of e_i == 0 left out (rows may hold -inf); a maximum that is not finite gives NaN
+// in all three, an id outside [0, V) a NaN logprob without a read.  Element i belongs to thread (i / 4) % 256 whatever the row's
+// alignment (16-, 8- or 4-byte loads), and the sums run in one fixed order (thread, wave butterfly, waves 0..3): no atomics, the same
+// bits on every run, in a replayed graph and for a row at any place in the batch.  The sampler's own instances are untouched.
+constexpr int SCORE_GROUPS = 18;   // 4 logits each: vocab <= 256 * 72, the sampler's own limit
+__global__ __launch_bounds__(256) void token_scores_kernel(const float* __restrict__ logits, int V, const StepState* __restrict__ state,
+                                                           const int64_t* __restrict__ ids, long ids_stride, int L0, int forced_period,
+                                                           float* __restrict__ out, int cols) {
+  const int j = state->j;
+  if (j < 1 || j > cols) return;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float* o = out + ((long)b * cols + (j - 1)) * 3;
+  if (forced_period > 0 && j % forced_period == 0) {
+    if (tid < 3) o[tid] = 0.f;
+    return;
+  }
+  __shared__ float red[12];
+  const float* row = logits + (long)b * V;
+  const int al = (int)(((uintptr_t)row) & 15);
+  float v[4 * SCORE_GROUPS];
+#pragma unroll
+  for (int q = 0; q < SCORE_GROUPS; ++q) {
+    const int i = (q * 256 + tid) * 4;
+    float4 t = float4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};   // past the row: weight 0 in every sum
+    if (i + 3 < V) {
+      if (al == 0) t = *(const float4*)(row + i);
+      else if ((al & 7) == 0) { const float2 a = *(const float2*)(row + i), c = *(const float2*)(row + i + 2); t = float4{a.x, a.y, c.x, c.y}; }
+      else t = float4{row[i], row[i + 1], row[i + 2], row[i + 3]};
+    } else if (i < V) {
+      t.x = row[i];
+      if (i + 1 < V) t.y = row[i + 1];
+      if (i + 2 < V) t.z = row[i + 2];
+    }
+    v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < 4 * SCORE_GROUPS; ++q) mx = fmaxf(mx, v[q]);
+  mx = wave_max(mx);
+  if (lane == 0) red[wv] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float s = 0.f, t = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4 * SCORE_GROUPS; ++q) {
+    const float d = v[q] - mx, e = expf(d);
+    s += e;
+    if (e != 0.f) t = fmaf(e, d, t);
+  }
+  s = wave_sum(s);
+  t = wave_sum(t);
+  if (lane == 0) { red[4 + wv] = s; red[8 + wv] = t; }
+  __syncthreads();
+  if (tid == 0) {
+    s = (red[4] + red[5]) + (red[6] + red[7]);
+    t = (red[8] + red[9]) + (red[10] + red[11]);
+    const long tok = ids[(long)b * ids_stride + L0 + (j - 1)];
+    const float ls = logf(s), nan = __int_as_float(0x7fc00000);
+    const bool ok = mx > -INFINITY && mx < INFINITY;   // (a NaN among finite entries reaches s and t by itself)
+    o[0] = ok && tok >= 0 && tok < V ? (row[tok] - mx) - ls : nan;
+    o[1] = ok ? ls - t / s : nan;
+    o[2] = ok ? (mx - mx) - ls : nan;   // (the very expression of o[0] at the arg-max: greedy gives the same bits)
+  }
+}
+
+int launch_token_scores(const float* logits, int V, const StepState* state, const int64_t* ids, long ids_stride, int L0, int forced_period,
+                        float* out, int cols, int B, hipStream_t st) {
+  if (B <= 0 || cols <= 0) return 0;
+  if (!logits || !ids || !out || V < 1 || V > 256 * 4 * SCORE_GROUPS) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(token_scores_kernel, dim3(B), dim3(256), 0, st, logits, V, state, ids, ids_stride, L0, forced_period, out, cols);
+  return (int)hipGetLastError();
+}
+
+static std::atomic<long long> g_token_scores_launches{0};
+void token_scores_note(int launches) { g_token_scores_launches += launches; }
+long long token_scores_launches() { return g_token_scores_launches.load(); }
+
 // ------------------------------------------------------------------------------------------------ eval heads
 // Shifted cross-entropy of teacher-forced logits (HF ForCausalLM loss, train_gpt.py:356-376): row r = (b, l) of a chunk of logits
 // [rows][V] fp32 predicts labels[b][l + 1]; nll[r] = logsumexp(logits[r]) - logits[r][target], 0 where the target is -100 (or l is

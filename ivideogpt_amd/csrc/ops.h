@@ -136,6 +136,13 @@ int launch_frame_heads(const void* x, const StepState* state, const float* rew_w
                        int B, int H, int F, float eps, DType dt, hipStream_t st);
 void frame_heads_note(int hits);   // the host's count of the launches above that hit a frame (test hook, ivg_debug_counter("frame_heads"))
 long long frame_heads_hits();
+// token scores of a rollout (ivg_generate_scored), launched directly after launch_sample_embed: out[b][j - 1][0..2] = { logprob of the
+// id the sampler stored for new token j = state->j, entropy, max logprob } of the raw fp32 row logits[b][:]; three zeros on a forced
+// column (j % forced_period == 0), nothing for j = 0 or j > cols.  out: [B][cols][3] floats
+int launch_token_scores(const float* logits, int V, const StepState* state, const int64_t* ids, long ids_stride, int L0, int forced_period,
+                        float* out, int cols, int B, hipStream_t st);
+void token_scores_note(int launches);   // the host's count of the launches above (test hook, ivg_debug_counter("token_scores"))
+long long token_scores_launches();
 // eval heads: shifted cross-entropy per row of a logits chunk, per-trajectory (sum, count), action reconstruction squared error
 int launch_ce_rows(const float* logits, const int64_t* labels, long row0, int rows, int L, int V, float* nll, hipStream_t st);
 int launch_ce_reduce(const float* nll, const int64_t* labels, int B, int L, int V, float* out, hipStream_t st);

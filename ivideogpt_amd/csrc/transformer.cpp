@@ -38,6 +38,10 @@ struct GenBuf {  // persistent decode-step buffers (fixed addresses so the captu
   // inside the steps and copied to the caller per chunk, like ids.  fr_rew / fr_hid: which of them this call's steps write
   float* frame_rew; char* frame_hid; int F_max;
   bool fr_rew = false, fr_hid = false;
+  // token scores (ivg_generate_scored): [Bc][ids_ld][3] floats, column j - 1 written by token_scores_kernel right after the sampler
+  // decided new token j; copied to the caller per chunk.  scored: this call's steps carry that kernel
+  float* tok_scores;
+  bool scored = false;
 };
 
 static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base = null: only the size
@@ -62,6 +66,7 @@ static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base
   g.F_max = std::max(1, e->Lmax / 17);   // a frame needs 17 new tokens
   g.frame_rew = (float*)take((size_t)Bc * g.F_max * 4);
   g.frame_hid = take((size_t)Bc * g.F_max * H * esz(dt));
+  g.tok_scores = (float*)take((size_t)Bc * g.ids_ld * 3 * 4);
   return off;
 }
 
@@ -212,6 +217,9 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
   StepState* state = g.state;
   char* x = g.x; char* qkv = g.qkv; char* attn = g.attn; char* act = g.act; float* logits = g.logits;
   if (!skip_sample) CK(launch_sample_embed(sa, B, dt, st));   // skip: x already holds the input row (embeds path, kept KV cache)
+  // token scores: the row the sampler just read is still whole (this step's lm_head overwrites it), the id it stored is in the id row
+  if (!skip_sample && g.scored)
+    CK(launch_token_scores(sa.logits, V, state, sa.ids_out, sa.ids_stride, sa.L0, sa.forced_period, g.tok_scores, g.ids_ld, B, st));
   if (!forward) return 0;
   // 5 launches per layer: RMSNorms are fused into the consuming GEMMs (weights pre-multiplied by the norm weight,
   // row scale computed from the activations the GEMM streams anyway), residual adds into the producing GEMMs.
@@ -357,6 +365,7 @@ int Run::generate(const GenerateReq& q) {
   g.fr_rew = q.frame_rewards_out != nullptr; g.fr_hid = q.frame_hidden_out != nullptr;
   const bool frames = g.fr_rew || g.fr_hid;
   const int F_out = n_new / 17;   // frames whose 16th token, new token 17 i + 16, is fed (<= n_new - 1)
+  g.scored = q.token_scores_out != nullptr;
   if (planning) {   // the prompt pass of the largest chunk (shared: of the most groups a chunk's rows can belong to)
     PrefillReq p; p.ctx = ctx; p.L = shared ? L0 - 1 : L0;
     p.B = shared ? std::min((std::min(B, g.Bc) + group - 1) / group + 1, std::min(B, g.Bc)) : std::min(B, g.Bc);
@@ -437,6 +446,7 @@ int Run::generate(const GenerateReq& q) {
                             std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)
                             (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "") +
                             (frames ? std::string(":f") + (g.fr_rew ? "r" : "") + (g.fr_hid ? "h" : "") : "") +   // (the steps carry frame_heads_kernel)
+                            (g.scored ? ":ts" : "") +   // (the steps carry token_scores_kernel)
                             e->kvc.graph_key();   // (the cache format and its scales)
     // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
     // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
@@ -457,10 +467,12 @@ int Run::generate(const GenerateReq& q) {
       for (int t = j0; t < j0 + n; ++t) hits += t % 17 == 16 && t / 17 < g.F_max;
       frame_heads_note(hits);
     };
+    // steps of this call that ran the sampler, and token_scores_kernel after it (test hook)
+    auto note_scores = [&](int n) { if (g.scored) token_scores_note(n); };
     int j = 1;
-    if (feed_last) IVG_TRY(step_body(e, st, g, Bc, sa, true, embeds != nullptr));   // j = 0: feed the prompt's last token
+    if (feed_last) { IVG_TRY(step_body(e, st, g, Bc, sa, true, embeds != nullptr)); if (!embeds) note_scores(1); }   // j = 0: feed the prompt's last token
     if (n_new == 1) IVG_TRY(reward());
-    if (n_new >= 1) { IVG_TRY(step_body(e, st, g, Bc, sa, j < n_new)); if (j < n_new) note_frames(j, 1); ++j; }
+    if (n_new >= 1) { IVG_TRY(step_body(e, st, g, Bc, sa, j < n_new)); note_scores(1); if (j < n_new) note_frames(j, 1); ++j; }
     // the step sequence is position-independent (all step-dependent scalars live in StepState): it is captured once as a graph of
     // ONE step and once as a graph of `multi` consecutive steps -- the long rollouts replay the multi-step graph (a graph launch
     // costs the host ~10-16 us and leaves a bubble on the device; 8 steps per launch amortise it), the tail the single-step one
@@ -469,13 +481,14 @@ int Run::generate(const GenerateReq& q) {
     if (j < n_new) IVG_TRY(step_graph(e, st, key, 1, g, Bc, sa, &exec));
     if (exec && multi > 1 && n_new - j >= 2 * multi) IVG_TRY(step_graph(e, st, key, multi, g, Bc, sa, &exec_multi));
     while (j < n_new) {
-      if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); note_frames(j, multi); j += multi; }
-      else if (exec) { CK((int)hipGraphLaunch(exec, st)); note_frames(j, 1); ++j; }
-      else { IVG_TRY(step_body(e, st, g, Bc, sa, true)); note_frames(j, 1); ++j; }
+      if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); note_frames(j, multi); note_scores(multi); j += multi; }
+      else if (exec) { CK((int)hipGraphLaunch(exec, st)); note_frames(j, 1); note_scores(1); ++j; }
+      else { IVG_TRY(step_body(e, st, g, Bc, sa, true)); note_frames(j, 1); note_scores(1); ++j; }
     }
     if (j == n_new && n_new > 1) {
       IVG_TRY(reward());
       IVG_TRY(step_body(e, st, g, Bc, sa, false));  // decide the last token (no forward)
+      note_scores(1);
     }
     if (embeds) {
       CK((int)hipMemcpy2DAsync(q.new_ids_out + (long)b0 * n_new, (size_t)n_new * 8, g.ids + L0, (size_t)g.ids_ld * 8, (size_t)n_new * 8, Bc,
@@ -488,6 +501,9 @@ int Run::generate(const GenerateReq& q) {
     }
     if (g.fr_rew)
       CK((int)hipMemcpy2DAsync(q.frame_rewards_out + (long)b0 * F_out, (size_t)F_out * 4, g.frame_rew, (size_t)g.F_max * 4, (size_t)F_out * 4, Bc,
+                               hipMemcpyDeviceToDevice, st));
+    if (g.scored)
+      CK((int)hipMemcpy2DAsync(q.token_scores_out + (long)b0 * n_new * 3, (size_t)n_new * 12, g.tok_scores, (size_t)g.ids_ld * 12, (size_t)n_new * 12, Bc,
                                hipMemcpyDeviceToDevice, st));
     if (g.fr_hid)
       CK((int)hipMemcpy2DAsync((char*)q.frame_hidden_out + (size_t)b0 * F_out * H * es, (size_t)F_out * H * es, g.frame_hid, (size_t)g.F_max * H * es,

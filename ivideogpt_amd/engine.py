@@ -283,6 +283,21 @@ class Engine:
                 if t is not None:
                     t.record_stream(self._run)
 
+    def generate_scored(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,
+                        frame_rewards=None, frame_hidden=None, token_scores=None):
+        """ivg_generate_scored: ``generate_frames`` (without frame outputs also the action-free ``generate``) that also leaves
+        ``token_scores`` (B, n_new, 3) float32: logprob, entropy and max_logprob of every decided new token (zeros on forced columns)."""
+        B = out.shape[0]
+        L0 = prompt.shape[1]
+        act_T = actions.shape[1] if actions is not None else 0
+        with self.stream() as s:
+            self.check(self.lib.ivg_generate_scored(self.h, _ptr(prompt), prompt.stride(0), B, L0, int(n_new), _ptr(actions), act_T, int(ctx),
+                                                    _ptr(uniforms), int(top_k), int(group_size), int(bool(reuse_kv)), int(bool(force_sdf)), _ptr(out),
+                                                    _ptr(frame_rewards), _ptr(frame_hidden), _ptr(token_scores), s), "generate_scored")
+            for t in (prompt, out, actions, uniforms, frame_rewards, frame_hidden, token_scores):
+                if t is not None:
+                    t.record_stream(self._run)
+
     def embed_tokens(self, ids, out):
         B, L = ids.shape
         with self.stream() as s:
@@ -299,14 +314,20 @@ class Engine:
             self.check(self.lib.ivg_reward_linear(self.h, _ptr(hidden), hidden.numel() // hidden.shape[-1], _ptr(out), s), "reward_linear")
             hidden.record_stream(self._run); out.record_stream(self._run)
 
-    def generate_embeds(self, embeds, n_new, out, hidden=None, uniforms=None, top_k=100, allow_reuse=True):
-        """-> True when the kept KV cache was reused (only the last row of ``embeds`` was fed)."""
+    def generate_embeds(self, embeds, n_new, out, hidden=None, uniforms=None, top_k=100, allow_reuse=True, token_scores=None):
+        """-> True when the kept KV cache was reused (only the last row of ``embeds`` was fed).  ``token_scores`` (B, n_new, 3) float32:
+        ivg_generate_embeds_scored instead, which also leaves logprob, entropy and max_logprob of every new token."""
         B, L0 = embeds.shape[:2]
         reused = C.c_int(0)
         with self.stream() as s:
-            self.check(self.lib.ivg_generate_embeds(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
-                                                    _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), s), "generate_embeds")
-            for t in (embeds, out, hidden, uniforms):
+            if token_scores is None:
+                self.check(self.lib.ivg_generate_embeds(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
+                                                        _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), s), "generate_embeds")
+            else:
+                self.check(self.lib.ivg_generate_embeds_scored(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
+                                                               _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), _ptr(token_scores), s),
+                           "generate_embeds_scored")
+            for t in (embeds, out, hidden, uniforms, token_scores):
                 if t is not None:
                     t.record_stream(self._run)
         return bool(reused.value)

@@ -14,6 +14,7 @@ All compute is in libivg (HIP); this file is tensor plumbing and checkpoint I/O.
 """
 import math
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 
@@ -105,6 +106,40 @@ def _from_group_major(x, t, B0):
     if x is None or t == 1 or B0 == 1:
         return x
     return x.view(B0, t, *x.shape[1:]).transpose(0, 1).reshape(x.shape).contiguous()
+
+
+class TokenScores(NamedTuple):
+    """``generate(..., output_token_scores=True)``: how sure the MODEL was at every new token (include/ivg.h ivg_generate_scored), each
+    float32 (B, max_new_tokens), natural logarithms, of the raw logits row ``z`` the sampler read -- before temperature, top-k and top-p
+    (HF's ``output_logits`` / ``compute_transition_scores(..., normalize_logits=True)``): ``logprob = z[tok] - logsumexp(z)``,
+    ``entropy`` of ``softmax(z)``, ``max_logprob = max(z) - logsumexp(z)``.  Forced ``sdf`` columns are exactly 0 in all three."""
+    logprob: torch.Tensor
+    entropy: torch.Tensor
+    max_logprob: torch.Tensor
+
+    def per_frame(self):
+        """-> ``(frame_logprob, frame_entropy)``, each (B, F), ``F = (max_new_tokens + 1) // 17``: the SUM of ``logprob`` and the MEAN of
+        ``entropy`` over each frame's 16 sampled tokens (the 17th column of a frame, the forced ``sdf`` and its zeros, is left out).
+        Added column by column in one order, so that a frame of a long call and the same frame of a 17-token call give the same bits."""
+        n = self.logprob.shape[1]
+        F = (n + 1) // 17
+        if F < 1:
+            raise ValueError(f"per_frame needs at least one frame of 16 tokens, not {n} columns")
+        col = torch.arange(F, device=self.logprob.device) * 17
+        lp, en = self.logprob[:, col], self.entropy[:, col]
+        for k in range(1, 16):
+            lp, en = lp + self.logprob[:, col + k], en + self.entropy[:, col + k]
+        return lp, en / 16
+
+
+def _token_scores_buffer(B, n_new, device):
+    return torch.empty(B, n_new, 3, dtype=torch.float32, device=device)
+
+
+def _token_scores_of(ts, t=1, B0=1, n=None):
+    """(B, n_new, 3) in the engine's row order -> TokenScores of (B, n) in the caller's"""
+    ts = _from_group_major(ts, t, B0)
+    return TokenScores(*(ts[:, :n, k].contiguous() for k in range(3)))
 
 
 def _top_p_of(top_p, do_sample):
@@ -387,8 +422,11 @@ class LlamaForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=None,
                  generator=None, uniforms=None, inputs_embeds=None, return_dict_in_generate=False, output_hidden_states=False,
-                 use_cache=True, shared_context=None, top_p=None, **unused):
+                 use_cache=True, shared_context=None, top_p=None, output_token_scores=False, **unused):
         """``input_ids`` prompt -> int64 (B, L0 + max_new_tokens), prompt included (HF convention).
+        ``output_token_scores=True`` (HF: ``output_logits`` + ``compute_transition_scores(normalize_logits=True)``, computed on the device
+        inside the decode steps): the result becomes ``(tokens, TokenScores)``; on the ``inputs_embeds`` path with
+        ``return_dict_in_generate`` the field ``.token_scores``.  The tokens are those of the call without it.
         ``top_p``: HF's nucleus filter after the top-k filter (include/ivg.h ivg_set_top_p); ``None`` / 1.0: none, ignored without
         ``do_sample``, ValueError outside [0, 1] or NaN (``_top_p_of``).
         ``shared_context`` (not in HF; round 6): ``t`` or ``"auto"`` when ``input_ids`` is ``prompts.repeat(t, 1)`` -- what
@@ -410,16 +448,29 @@ class LlamaForCausalLM:
             out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=self.device)
             hidden = torch.empty(B, 1, emb.shape[-1], dtype=self.torch_dtype, device=self.device) if output_hidden_states else None
             u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
+            ts = _token_scores_buffer(B, max_new_tokens, self.device) if output_token_scores else None
             self.last_generate_reused_cache = self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_embeds(
-                emb, max_new_tokens, out, hidden=hidden, uniforms=u, top_k=top_k or self._cfg["vocab_size"], allow_reuse=use_cache)
+                emb, max_new_tokens, out, hidden=hidden, uniforms=u, top_k=top_k or self._cfg["vocab_size"], allow_reuse=use_cache, token_scores=ts)
+            scores = _token_scores_of(ts) if output_token_scores else None
             if not return_dict_in_generate:
-                return out
-            return SimpleNamespace(sequences=out, hidden_states=((hidden,),) if output_hidden_states else None)
+                return (out, scores) if output_token_scores else out
+            res = SimpleNamespace(sequences=out, hidden_states=((hidden,),) if output_hidden_states else None)
+            if output_token_scores:
+                res.token_scores = scores
+            return res
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
         out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=self.device)
         u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
         t, B0 = shared_prompt_groups(ids, shared_context) if shared_context else (1, B)
+        if output_token_scores:
+            if not (t > 1 and L0 >= 2):
+                t, B0 = 1, B
+            ts = _token_scores_buffer(B, max_new_tokens, self.device)
+            self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_scored(
+                ids[:B0].contiguous() if t > 1 else ids, max_new_tokens, out, uniforms=_to_group_major(u, t, B0), top_k=top_k or self._cfg["vocab_size"],
+                group_size=t, token_scores=ts)
+            return _from_group_major(out, t, B0), _token_scores_of(ts, t, B0)
         if t > 1 and L0 >= 2:
             self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_shared(
                 ids[:B0].contiguous(), t, max_new_tokens, out, uniforms=_to_group_major(u, t, B0), top_k=top_k or self._cfg["vocab_size"])
@@ -472,9 +523,10 @@ def _frames_of(max_new_tokens):
     return (max_new_tokens + 1) // 17
 
 
-def _generate_frames(llm, eng, ids, max_new_tokens, act, ctx, u, top_k, t, B0, reuse_kv, force_sdf, want_rewards, want_hidden):
+def _generate_frames(llm, eng, ids, max_new_tokens, act, ctx, u, top_k, t, B0, reuse_kv, force_sdf, want_rewards, want_hidden, want_scores=False):
     """One ivg_generate_frames call of ``max_new_tokens + 1`` tokens -> (tokens (B, L0 + max_new_tokens), rewards (B, F) or None, hidden
-    (B, F, H) or None), rows in the caller's order (``t`` > 1: translated to and from the engine's group-major order)."""
+    (B, F, H) or None), rows in the caller's order (``t`` > 1: translated to and from the engine's group-major order).
+    ``want_scores``: ivg_generate_scored instead, and a fourth value, the TokenScores of the ``max_new_tokens`` columns."""
     B, L0 = ids.shape
     F, n_new = _frames_of(max_new_tokens), max_new_tokens + 1
     if u is not None and u.shape[1] < n_new:   # (the extra token is the forced sdf: its column is never read)
@@ -484,6 +536,13 @@ def _generate_frames(llm, eng, ids, max_new_tokens, act, ctx, u, top_k, t, B0, r
     out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=llm.device)
     fr = torch.empty(B, F, dtype=torch.float32, device=llm.device) if want_rewards else None
     fh = torch.empty(B, F, llm._cfg["hidden_size"], dtype=llm.torch_dtype, device=llm.device) if want_hidden else None
+    if want_scores:
+        ts = _token_scores_buffer(B, n_new, llm.device)
+        eng.generate_scored(ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx,
+                            uniforms=_to_group_major(u, t, B0), top_k=top_k, group_size=t, reuse_kv=reuse_kv, force_sdf=force_sdf,
+                            frame_rewards=fr, frame_hidden=fh, token_scores=ts)
+        return (_from_group_major(out, t, B0)[:, :-1], _from_group_major(fr, t, B0), _from_group_major(fh, t, B0),
+                _token_scores_of(ts, t, B0, max_new_tokens))
     eng.generate_frames(ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx,
                         uniforms=_to_group_major(u, t, B0), top_k=top_k, group_size=t, reuse_kv=reuse_kv, force_sdf=force_sdf,
                         frame_rewards=fr, frame_hidden=fh)
@@ -596,7 +655,7 @@ class HeadModelWithAction:
     @torch.no_grad()
     def generate(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=50256,
                  action=None, generator=None, uniforms=None, return_reward=False, reuse_cache=False, shared_context=None, top_p=None,
-                 output_frame_hidden_states=False):
+                 output_frame_hidden_states=False, output_token_scores=False):
         """action_model.py:56-121: action (B, T, D); new token j is the forced sdf when j % 17 == 0; the i-th sdf slot's
         embedding gets ``action_linear(action[:, i + context - 1])``.  -> int64 (B, L0 + max_new_tokens).
         ``shared_context``: as ``LlamaForCausalLM.generate`` -- ``inputs_token`` is ``prompts.repeat(t, 1)`` (train_gpt.py:170, VP2's
@@ -613,7 +672,12 @@ class HeadModelWithAction:
         more, the forced ``sdf`` that feeds the last frame's 16th token, and that column is dropped.  ``return_reward=True`` keeps its
         meaning: one value (B), read at the last forward pass.
         ``output_frame_hidden_states=True`` appends the post-norm hidden states (B, F, hidden) at those positions to the result, under
-        the same condition on ``max_new_tokens`` (with ``return_reward`` False or "frames").  Both work with ``shared_context`` and ``reuse_cache``."""
+        the same condition on ``max_new_tokens`` (with ``return_reward`` False or "frames").  Both work with ``shared_context`` and ``reuse_cache``.
+        ``output_token_scores=True`` appends, as the LAST element of the result (a bare tensor becomes a 2-tuple), the ``TokenScores``
+        ``(logprob, entropy, max_logprob)``, each float32 (B, max_new_tokens), of the model's distribution at every new token, forced
+        ``sdf`` columns 0 (include/ivg.h ivg_generate_scored); the other results are those of the call without it.  With
+        ``return_reward=True`` the single reward is read off the per-frame rewards of the same call, which needs
+        ``max_new_tokens`` a positive multiple of 17 (the step-wise callers' 17; ValueError otherwise)."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
         top_p = _top_p_of(top_p, do_sample)
@@ -626,6 +690,9 @@ class HeadModelWithAction:
                 raise ValueError("return_reward='frames' needs a model with reward_prediction=True")
             if return_reward is True:   # (its value is read one token earlier than a frame's: no single call yields both)
                 raise ValueError("output_frame_hidden_states goes with return_reward='frames' or False, not True")
+        if output_token_scores and return_reward is True and not (isinstance(max_new_tokens, int) and max_new_tokens >= 17 and max_new_tokens % 17 == 0):
+            # (the scored entry has the per-frame rewards only; the last of them is reward_out iff the call ends with a frame's sdf)
+            raise ValueError(f"output_token_scores with return_reward=True needs max_new_tokens a positive multiple of 17, not {max_new_tokens!r}")
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
@@ -640,17 +707,30 @@ class HeadModelWithAction:
             if not (t > 1 and L0 == 257 * self.context):
                 t, B0 = 1, B
             u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
-            out, fr, fh = _generate_frames(llm, llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens,
-                                           act, self.context, u, top_k or llm._cfg["vocab_size"], t, B0, reuse_cache, False, per_frame,
-                                           output_frame_hidden_states)
+            out, fr, fh, *sc = _generate_frames(llm, llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens,
+                                                act, self.context, u, top_k or llm._cfg["vocab_size"], t, B0, reuse_cache, False, per_frame,
+                                                output_frame_hidden_states, output_token_scores)
             res = (out,)
             if per_frame:
                 res += (fr,)
-            return res + (fh,) if output_frame_hidden_states else res
+            if output_frame_hidden_states:
+                res += (fh,)
+            return res + (sc[0],) if output_token_scores else res
         out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
         u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
         reward = torch.empty(B, dtype=torch.float32, device=llm.device) if return_reward else None
         t, B0 = shared_prompt_groups(ids, shared_context) if (shared_context and not reuse_cache) else (1, B)
+        if output_token_scores:
+            if not (t > 1 and L0 == 257 * self.context):
+                t, B0 = 1, B
+            ts = _token_scores_buffer(B, max_new_tokens, llm.device)
+            fr = torch.empty(B, max_new_tokens // 17, dtype=torch.float32, device=llm.device) if return_reward else None
+            llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate_scored(
+                ids[:B0].contiguous() if t > 1 else ids, max_new_tokens, out, actions=_to_group_major(act, t, B0), ctx=self.context,
+                uniforms=_to_group_major(u, t, B0), top_k=top_k or llm._cfg["vocab_size"], group_size=t, reuse_kv=reuse_cache, frame_rewards=fr,
+                token_scores=ts)
+            out, sc = _from_group_major(out, t, B0), _token_scores_of(ts, t, B0)
+            return (out, _from_group_major(fr, t, B0)[:, -1].contiguous(), sc) if return_reward else (out, sc)
         if t > 1 and L0 == 257 * self.context:
             llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate_shared(
                 ids[:B0].contiguous(), t, max_new_tokens, out, actions=_to_group_major(act, t, B0), ctx=self.context, uniforms=_to_group_major(u, t, B0),
@@ -664,13 +744,14 @@ class HeadModelWithAction:
 
     @torch.no_grad()
     def generate_without_action(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, generator=None,
-                                uniforms=None, top_p=None, output_frame_hidden_states=False):
+                                uniforms=None, top_p=None, output_frame_hidden_states=False, output_token_scores=False):
         """action_model.py:123-152 (no caller in the reference): per future frame 16 sampled tokens, then the forced ``sdf`` -- the
         schedule of ``generate`` without any action embedding; the last forced ``sdf`` is dropped.  -> int64 (B, L0 + max_new_tokens).
         One prefill + cached steps instead of the reference's per-frame re-prefill (token-identical: same argument as ``generate``).
         ``top_p`` (an extension, as in ``generate``): as ``LlamaForCausalLM.generate``.
         ``output_frame_hidden_states=True``: -> ``(tokens, hidden (B, F, hidden))``, the post-norm hidden state at every predicted
-        frame's 16th token (as ``generate``); the tokens are those of the plain call."""
+        frame's 16th token (as ``generate``); the tokens are those of the plain call.
+        ``output_token_scores=True`` appends the ``TokenScores`` as the last element (as ``generate``)."""
         if not (isinstance(temperature, (int, float)) and temperature > 0):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
         top_p = _top_p_of(top_p, do_sample)
@@ -683,9 +764,14 @@ class HeadModelWithAction:
         out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
         u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
         if output_frame_hidden_states:
-            out, _, fh = _generate_frames(llm, llm._ensure(B).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens, None, self.context, u,
-                                          top_k or llm._cfg["vocab_size"], 1, B, False, True, False, True)
-            return out, fh
+            out, _, fh, *sc = _generate_frames(llm, llm._ensure(B).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens, None, self.context, u,
+                                               top_k or llm._cfg["vocab_size"], 1, B, False, True, False, True, output_token_scores)
+            return (out, fh, sc[0]) if output_token_scores else (out, fh)
+        if output_token_scores:
+            ts = _token_scores_buffer(B, max_new_tokens, llm.device)
+            llm._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_scored(ids, max_new_tokens, out, ctx=self.context, uniforms=u,
+                                                                                        top_k=top_k or llm._cfg["vocab_size"], force_sdf=True, token_scores=ts)
+            return out, _token_scores_of(ts)
         llm._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_forced_sdf(ids, max_new_tokens, out, ctx=self.context, uniforms=u,
                                                                                top_k=top_k or llm._cfg["vocab_size"])
         return out

@@ -105,9 +105,12 @@ class VideoPredictor:
         return self
 
     @torch.no_grad()
-    def rollout(self, obs, policy, horizon):
+    def rollout(self, obs, policy, horizon, return_uncertainty=False):
         """obs [B, 9, H, W] in 0..255 (3 stacked RGB frames); policy(obs, t) -> [B, A].
-        -> (obss [B, horizon+1, 9, H, W], actions [B, horizon+1, A], rewards [B, horizon+1, 1])"""
+        -> (obss [B, horizon+1, 9, H, W], actions [B, horizon+1, A], rewards [B, horizon+1, 1])
+        ``return_uncertainty=True`` appends ``uncertainty [B, horizon+1, 1]``: per imagined step the mean predictive entropy (nats) of
+        the model over the frame's 16 sampled tokens (``TokenScores.per_frame``), 0 for the dummy step 0; no ``symexp``, no transform --
+        for MOPO / MOReL-style penalties and rollout truncation."""
         ctx, model, llm = self.context_length, self.model, self.model.llm
         B = obs.shape[0]
         obs = obs.to(self.device).float() / 255.
@@ -116,14 +119,14 @@ class VideoPredictor:
         prompt = self.tokenizer.encode_context(torch.stack(stack[-ctx:], dim=1), ctx)   # [B, 257*ctx], ends with the first sdf
         embeds = model.get_input_embeddings(prompt)
         sdf_col = torch.full((B, 1), model.token_for_sdf, dtype=prompt.dtype, device=self.device)
-        cache, trace = None, {"obs": [], "act": [], "rew": []}
+        cache, trace = None, {"obs": [], "act": [], "rew": [], "unc": []}
         self.steps_with_kept_cache = 0
         for t in range(horizon):
             action = policy(obs, t).to(self.device).float()
             embeds[:, -1] += model.action_linear(action)                       # this step's sdf slot carries the action
             result = llm.generate(inputs_embeds=embeds, do_sample=True, temperature=1.0, top_k=100, pad_token_id=50256,
                                   use_cache=self.reuse_cache, max_new_tokens=TOKENS_PER_DYN + 1, return_dict_in_generate=True,
-                                  output_hidden_states=True)
+                                  output_hidden_states=True, output_token_scores=return_uncertainty)
             self.steps_with_kept_cache += int(llm.last_generate_reused_cache)
             predicted = result.sequences[:, :-1]                               # the 17th token is replaced by the forced sdf
             reward = model.reward_linear(result.hidden_states[-1][-1]).squeeze(-2)   # last layer, last forward pass
@@ -132,16 +135,21 @@ class VideoPredictor:
             stack = stack[1:] + [fmap.clamp(0.0, 1.0)[:, -1]]
             obs = torch.cat(stack, dim=1)
             trace["obs"].append(obs); trace["act"].append(action); trace["rew"].append(reward)
+            if return_uncertainty:
+                trace["unc"].append(result.token_scores.per_frame()[1])       # [B, 1]: the 16 sampled tokens of this step's frame
         # dummy step 0: the initial observation with a zero action / reward
         obss = torch.stack([first_obs] + trace["obs"], 1).float()
         actions = torch.stack([torch.zeros_like(trace["act"][0])] + trace["act"], 1).float()
         rewards = [torch.zeros_like(trace["rew"][0])] + trace["rew"]
         if self.symlog:
             rewards = [symexp(r) for r in rewards]
+        if return_uncertainty:
+            uncertainty = torch.stack([torch.zeros_like(trace["unc"][0])] + trace["unc"], 1).float()
+            return obss, actions, torch.stack(rewards, 1).float(), uncertainty
         return obss, actions, torch.stack(rewards, 1).float()
 
     @torch.no_grad()
-    def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None):
+    def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None, return_uncertainty=False):
         """Open-loop rollout of given action sequences (a CEM / MPPI / MPC planner's candidates, MBPO with a fixed plan) in three calls
         instead of ``horizon`` steps: one ``encode_context``, one ``generate`` that also returns the hidden state at every frame's
         16th token, where the reward head is trained (include/ivg.h ivg_generate_frames), and one ``detokenize``.  The rewards are
@@ -151,7 +159,9 @@ class VideoPredictor:
         are the candidates of observation b, whose context is prefilled, kept and decoded once (``shared_context``).
         ``uniforms`` [B * samples, 17 * horizon - 1] (rows as ``actions``) or ``generator`` drive the sampler.
         -> (obss [B * samples, horizon + 1, 9, H, W], actions [B * samples, horizon + 1, A], rewards [B * samples, horizon + 1, 1]):
-        ``rollout``'s layout, with its dummy step 0 and ``symexp``."""
+        ``rollout``'s layout, with its dummy step 0 and ``symexp``.  ``return_uncertainty=True`` appends ``uncertainty
+        [B * samples, horizon + 1, 1]`` as ``rollout`` does: the per-frame mean predictive entropy from the same ``generate`` call
+        (``output_token_scores``), equal to ``rollout``'s bit for bit on the same actions and uniforms."""
         from ivideogpt_amd.transformer import _from_group_major, _to_group_major
         ctx, model = self.context_length, self.model
         B, t = obs.shape[0], int(samples)
@@ -165,9 +175,10 @@ class VideoPredictor:
         table = torch.cat([act.new_zeros(N, ctx - 1, act.shape[2]), act], 1)
         # generate / detokenize take the candidates in ``prompt.repeat(t, 1)`` order (row k * B + b)
         u = _from_group_major(uniforms.to(self.device).float().contiguous(), t, B) if uniforms is not None else None
-        tokens, hidden = model.generate(prompt.repeat(t, 1), do_sample=True, temperature=1.0, top_k=100, max_new_tokens=17 * horizon - 1,
-                                        action=_from_group_major(table.contiguous(), t, B), generator=generator, uniforms=u,
-                                        output_frame_hidden_states=True, shared_context=t if t > 1 else None)
+        tokens, hidden, *scores = model.generate(prompt.repeat(t, 1), do_sample=True, temperature=1.0, top_k=100, max_new_tokens=17 * horizon - 1,
+                                                 action=_from_group_major(table.contiguous(), t, B), generator=generator, uniforms=u,
+                                                 output_frame_hidden_states=True, shared_context=t if t > 1 else None,
+                                                 output_token_scores=return_uncertainty)
         rewards = model.reward_linear(hidden).squeeze(-1)                      # (B * samples, horizon)
         clip = self.tokenizer.detokenize(tokens, ctx, shared_context=t if t > 1 else None)
         rewards, clip = _to_group_major(rewards, t, B), _to_group_major(clip, t, B)
@@ -177,4 +188,7 @@ class VideoPredictor:
         rewards = torch.cat([torch.zeros_like(rewards[:, :1]), rewards], 1).unsqueeze(-1)
         if self.symlog:
             rewards = symexp(rewards)
+        if return_uncertainty:
+            unc = _to_group_major(scores[0].per_frame()[1], t, B)             # (B * samples, horizon)
+            return obss, actions, rewards.float(), torch.cat([torch.zeros_like(unc[:, :1]), unc], 1).unsqueeze(-1).float()
         return obss, actions, rewards.float()
