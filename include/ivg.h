@@ -220,6 +220,13 @@ int ivg_detokenize_shared(ivg_engine* e, const int64_t* ids, int n_groups, int g
 int ivg_set_output_clamp(ivg_engine* e, int on);
 int ivg_cache_create(ivg_engine* e, int B, ivg_cache** out);
 void ivg_cache_destroy(ivg_engine* e, ivg_cache* c);
+/* A NEW cache of n rows, row i gathered from row parents[i] of src (what ivg_kv_select does to the transformer's kept cache, for the
+ * detokenizer's context cache; parents is a HOST array; src is unchanged and stays the caller's).  src must be filled.  The new cache
+ * inherits the element type of the kept pixels, the clamp mode and the fill of src; its context pixels and every feature map are
+ * gathered per trajectory on `stream`.  Refusals are those of ivg_cache_create (n against max_batch: IVG_ERR_CAPACITY) plus
+ * IVG_ERR_INVALID for an empty src or a parent outside [0, rows of src); on failure everything allocated is released and *out is
+ * not written. */
+int ivg_cache_select(ivg_engine* e, const ivg_cache* src, const int32_t* parents, int n, ivg_cache** out, ivg_stream stream);
 
 /* LlamaForCausalLM.generate (predict.py:57-69) when actions == NULL: every new token is sampled;
  * HeadModelWithAction.generate (action_model.py:56-121) when actions != NULL: the action embedding is added to the
@@ -262,6 +269,30 @@ int ivg_generate_forced_sdf(ivg_engine* e, const int64_t* prompt, int64_t prompt
  * other tokens / actions (the cached prefix is compared with the prompt on the device: one stream synchronisation). */
 int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions,
                           int act_T, int ctx, const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, ivg_stream stream);
+
+/* Resample the kept cache (HF's _reorder_cache): new row i of the kept cache := old row parents[i], 0 <= i < n.  parents is a HOST
+ * array.  For callers that act on rewards / uncertainties in the middle of a step-wise rollout -- drop trajectories, duplicate them,
+ * reorder them -- and go on with ivg_generate_continue (or the reuse path of ivg_generate_embeds) instead of a new prompt pass.
+ *
+ * Precondition: the engine holds a kept cache, i.e. the last call was ivg_generate, _continue, _forced_sdf, _frames / _scored with
+ * group_size == 1, or ivg_generate_embeds, with B within the cache chunk (min(max_batch, 128) rows).
+ * Refusals, each before anything is launched or written -- the kept cache stays usable exactly as it was:
+ *   IVG_ERR_INVALID   no kept cache (a fresh engine; after a shared-context call, ivg_set_kv_format, ivg_set_kv_scales, ivg_kv_calibrate);
+ *                     n <= 0; a parents[i] outside [0, rows of the kept cache)
+ *   IVG_ERR_CAPACITY  n above the cache chunk
+ * Effect: as if the rows were gathered from a snapshot taken before the call -- duplicates, drops, growth (n above the kept rows) and
+ * any permutation.  Gathered by the same map: positions [0, len) of every (layer, K | V) slab in the cache's own format (native bf16 /
+ * fp32, both planes of the 24-bit format, FP8 bytes; FP8 scales are per head, not per trajectory: untouched), columns [0, len] of the
+ * engine's id rows, the rows of the kept action table, and rows [0, len) of the embeddings snapshot of an embeds call.  Afterwards the
+ * kept cache holds n trajectories at the same length, built under the same context length and action-table shape.  The kept-cache
+ * entries then accept a prompt / actions / embeds the caller gathered by the same parents, and still refuse anything else: the
+ * on-device verification stays the guard.
+ * Rows >= n, positions >= len and rows with parents[i] == i are neither read nor written; parents equal to the identity over the kept
+ * rows launches nothing.  Rows whose source is not itself overwritten (it keeps its place, or is dropped) are copied in place in one
+ * launch; the others pass through the engine's workspace (planned at ivg_create: the call never grows it).  The work is enqueued on
+ * `stream`; there is no host synchronisation, and no captured step graph is invalidated (a graph does not bake in which trajectory
+ * a row is). */
+int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream stream);
 
 /* Per-frame rewards and hidden states of one rollout call (the reference's generate is declared to return `reward (B, segment -
  * context)` and leaves it a TODO, action_model.py:83-99,118-120; its forward reads reward_linear at the hidden state of every frame's
@@ -567,6 +598,13 @@ int ivg_op_kv8_pack_heads(const void* k16, const void* v16, void* kc, void* vc, 
 int ivg_op_decode_attn8_heads(const void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int heads, int Lmax, int pos,
                               int P, int G, int row0, const float* k_scales, const float* v_scales, ivg_stream stream);
 int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, uint32_t* out, ivg_stream stream);
+/* ivg_kv_select's move planner and kv_gather_rows_kernel on a caller-owned buffer laid out as the cache is:
+ * [layers][2][chunk][heads]{[Lmax] rows of row_bytes_a | [Lmax] rows of row_bytes_b} (row_bytes_b = 0: one plane; both multiples of
+ * 16, chunk <= 128).  New row i := old row parents[i] (host array, [0, B_old)) for i < n, positions [0, len); every other byte stays.
+ * scratch (device, 16-byte aligned) stages the rows whose source is itself overwritten, slabs in groups as large as scratch_bytes
+ * allows; IVG_ERR_CAPACITY, with nothing launched, when it does not hold one slab's staged rows or n > chunk.  Enqueued on `stream`. */
+int ivg_op_kv_select(void* base, int layers, int chunk, int heads, int Lmax, int row_bytes_a, int row_bytes_b /* second plane, 0 if none */,
+                     int len, int B_old, const int32_t* parents, int n, void* scratch, size_t scratch_bytes, ivg_stream stream);
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream);
 /* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
@@ -589,7 +627,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

@@ -78,6 +78,8 @@ EXPORTS = {
     "ivg_set_output_clamp": (C.c_int, [C.c_void_p, C.c_int]),
     "ivg_cache_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "ivg_cache_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ivg_cache_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "ivg_kv_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ivg_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_generate_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -146,6 +148,7 @@ EXPORTS = {
     "ivg_op_vq_argmin": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     "ivg_op_add_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "ivg_op_conv_in": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
+    "ivg_op_kv_select": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ivg_op_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_op_sample_top_p": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_op_token_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

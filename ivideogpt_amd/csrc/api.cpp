@@ -251,6 +251,8 @@ static int plan_and_allocate(ivg_engine* e) {
     const int Lpre = std::min(e->Lmax - 1, 514);  // typical prompt (2 context frames); larger calls grow the arena on demand
     GenerateReq q; q.B = B; q.L0 = Lpre; q.n_new = 1;
     int rc = r.generate(q); if (rc) return rc;
+    e->ws.reset(0);
+    (void)e->ws.alloc(kv_select_scratch_bytes(e));   // ivg_kv_select stages rows here and never grows the arena (no host synchronisation)
   }
   e->ws.cap = e->ws.high + (1 << 20);
   API_CK(hipMalloc((void**)&e->ws.base, e->ws.cap));
@@ -587,6 +589,35 @@ int ivg_cache_create(ivg_engine* e, int B, ivg_cache** out) {
   return IVG_OK;
 }
 
+int ivg_cache_select(ivg_engine* e, const ivg_cache* src, const int32_t* parents, int n, ivg_cache** out, ivg_stream stream) {
+  if (!e || !out || e->cfg.n_levels <= 0) return IVG_ERR_INVALID;
+  if (!src || !src->filled || src->ctx <= 0) return e->fail(IVG_ERR_INVALID, "cache_select: the source cache is empty");
+  if (!parents) return e->fail(IVG_ERR_INVALID, "cache_select: null argument");
+  for (int i = 0; i < n; ++i)
+    if (parents[i] < 0 || parents[i] >= src->B) return e->fail(IVG_ERR_INVALID, "cache_select: every parent must be a row of the source cache, [0, " + std::to_string(src->B) + ")");
+  ivg_cache* k = nullptr;
+  IVG_TRY(ivg_cache_create(e, n, &k));
+  if (k->feat.size() != src->feat.size()) { ivg_cache_destroy(e, k); return e->fail(IVG_ERR_INVALID, "cache_select: cache layout mismatch"); }
+  k->pix_dt = src->pix_dt; k->clamped = src->clamped; k->filled = true; k->ctx = src->ctx;
+  // rows are contiguous per trajectory, in the sizes Run::detokenize filled them with: ctx frames of pixels / of every feature map
+  const ivg_config& c = e->cfg;
+  const int nl = c.n_levels;
+  const long ctx = src->ctx, res = c.resolution;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_gather_rows_by_parent(src->ctx_pixels, k->ctx_pixels, ctx * 3 * res * res * (src->pix_dt == (int)F32 ? 4 : 2), parents, n, st);
+  size_t fi = 0;
+  auto feat = [&](long side, long C) {
+    if (rc == 0) rc = launch_gather_rows_by_parent(src->feat[fi], k->feat[fi], ctx * side * side * C * (long)dtype_size(e->dec_dt), parents, n, st);
+    ++fi;
+  };
+  feat(16, c.block_out_channels[nl - 1]);   // (the order of ivg_cache_create)
+  long s = 16;
+  for (int i = 0; i < nl; ++i) { if (i != nl - 1) s *= 2; if (s <= c.max_att_resolution) feat(s, c.block_out_channels[nl - 1 - i]); }
+  if (rc) { ivg_cache_destroy(e, k); return e->fail(IVG_ERR_HIP, "cache_select: gather launch failed: hip error " + std::to_string(rc)); }
+  *out = k;
+  return IVG_OK;
+}
+
 void ivg_cache_destroy(ivg_engine* e, ivg_cache* c) {
   if (!c) return;
   if (e) (void)hipSetDevice(e->device);
@@ -667,6 +698,12 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
   GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
   q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out; q.reuse_kv = true;
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+}
+
+int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "kv_select: engine was created without a transformer");
+  return kv_select(e, parents, n, (hipStream_t)stream);
 }
 
 // ivg_generate_frames (need_frames: its conditions on the schedule and the lengths always hold) and ivg_generate_scored (they hold only
@@ -1173,6 +1210,8 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "lpips_trunk_images")) return lpips_trunk_images();
   if (name && !strcmp(name, "frame_heads")) return frame_heads_hits();
   if (name && !strcmp(name, "token_scores")) return token_scores_launches();
+  if (name && !strcmp(name, "kv_select_direct")) return kv_select_rows(0);
+  if (name && !strcmp(name, "kv_select_staged")) return kv_select_rows(1);
   return -1;
 }
 
@@ -1313,6 +1352,22 @@ int ivg_op_decode_attn8_heads(const void* qkv, void* kc, void* vc, void* out, co
 int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, int Lmax, uint32_t* out, ivg_stream stream) {
   if (!k16 || !v16 || !out || B <= 0 || heads <= 0 || L < 0 || L > Lmax) return IVG_ERR_INVALID;
   return launch_kv_absmax(k16, v16, B, heads, L, Lmax, out, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
+}
+
+int ivg_op_kv_select(void* base, int layers, int chunk, int heads, int Lmax, int row_bytes_a, int row_bytes_b, int len, int B_old, const int32_t* parents,
+                     int n, void* scratch, size_t scratch_bytes, ivg_stream stream) {
+  if (!base || layers <= 0 || heads <= 0 || Lmax <= 0 || row_bytes_a <= 0 || row_bytes_b < 0 || row_bytes_a % 16 || row_bytes_b % 16 || len < 1 || len > Lmax)
+    return IVG_ERR_INVALID;
+  KvSelectPlan plan;
+  const int prc = kv_select_plan(parents, n, B_old, chunk, &plan);
+  if (prc != KV_PLAN_OK) return prc == KV_PLAN_CAPACITY ? IVG_ERR_CAPACITY : IVG_ERR_INVALID;
+  KvSelectBuf b;   // [layers][2][chunk][heads]{[Lmax] rows of row_bytes_a | [Lmax] rows of row_bytes_b}
+  b.base = (char*)base; b.slabs = layers * 2; b.heads = heads;
+  b.head_stride = (long)Lmax * (row_bytes_a + row_bytes_b); b.row_stride = heads * b.head_stride; b.slab_stride = chunk * b.row_stride;
+  b.bytes_a = (long)len * row_bytes_a; b.bytes_b = (long)len * row_bytes_b; b.plane_b = (long)Lmax * row_bytes_a;
+  const int rc = launch_kv_select(b, plan, scratch, scratch_bytes, (hipStream_t)stream);
+  if (rc == 0) kv_select_note(plan.n_direct, plan.n_staged);
+  return rc == 0 ? IVG_OK : (rc == -4 ? IVG_ERR_CAPACITY : IVG_ERR_HIP);
 }
 
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream) {

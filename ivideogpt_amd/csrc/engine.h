@@ -209,6 +209,7 @@ struct ivg_cache {
   std::vector<void*> feat;                  // un-repeated per-trajectory context decoder features (NHWC)
   bool filled = false;
   bool clamped = false;                     // the kept context pixels were written with the output clamp on (ivg_set_output_clamp at fill time)
+  int ctx = 0;                              // context length in force at fill time: rows of ctx_pixels / feat[] hold that many frames (ivg_cache_select)
 };
 
 struct ivg_engine {

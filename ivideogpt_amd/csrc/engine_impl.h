@@ -95,5 +95,8 @@ size_t gen_buffer_bytes(const ivg_engine* e);
 int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, const float* actions, int act_T,
                           int ctx, hipStream_t st, bool* ok);
 int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, hipStream_t st, bool* ok);
+// ivg_kv_select: the kept cache's rows, and everything the verification above compares them with, gathered by `parents`
+int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st);
+size_t kv_select_scratch_bytes(const ivg_engine* e);   // workspace that stages one slab of any buffer ivg_kv_select gathers, all rows staged
 
 }  // namespace ivg

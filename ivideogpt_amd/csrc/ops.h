@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "igemm.h"
+#include "kv_select_plan.h"
 
 namespace ivg {
 
@@ -151,6 +152,27 @@ int launch_action_recon(const void* hidden, const float* W, const float* bias, c
 // *flag += number of differing 32-bit words between `rows` rows of row_bytes bytes (strides in bytes)
 int launch_compare_rows(const void* a, long a_stride_bytes, const void* b, long b_stride_bytes, int rows, long row_bytes, int* flag,
                         hipStream_t st);
+
+// ---- kv_select.hip (ivg_kv_select / ivg_cache_select: rows of a buffer gathered by a parents map)
+// one buffer whose trajectory rows a select gathers: `slabs` slabs of rows at row_stride, each row `heads` blocks at head_stride, of
+// which the first bytes_a bytes move -- and bytes_b more from plane_b on (0: one plane).  vec: 16 (every stride, offset and byte count a
+// multiple of 16: the K / V slabs, the embeddings snapshot) or 4 (multiples of 4: the id rows, the action table)
+struct KvSelectBuf {
+  char* base = nullptr;
+  int slabs = 1; long slab_stride = 0, row_stride = 0;
+  int heads = 1; long head_stride = 0;
+  long bytes_a = 0, bytes_b = 0, plane_b = 0;
+  int vec = 16;
+  size_t staged_bytes_per_slab(int n_staged) const { return (size_t)n_staged * heads * (bytes_a + bytes_b); }
+};
+// the plan's moves on one buffer: staged rows out to scratch, direct rows in place, staged rows back in -- slabs in groups as large as
+// the scratch allows.  0, a hipError_t, or -4 (nothing launched) when the scratch does not hold one slab's staged rows
+int launch_kv_select(const KvSelectBuf& b, const KvSelectPlan& plan, void* scratch, size_t scratch_bytes, hipStream_t st);
+// dst row i := src row parents[i], 0 <= i < n, rows of row_bytes (a multiple of 16) bytes, contiguous, in two buffers that do not
+// overlap; any n and any parents[i] >= 0 (the rows go in launches of at most 128 moves within windows of 256 rows)
+int launch_gather_rows_by_parent(const void* src, void* dst, long row_bytes, const int32_t* parents, int n, hipStream_t st);
+void kv_select_note(int direct, int staged);   // trajectory rows a select moved (test hook, ivg_debug_counter("kv_select_direct" / "_staged"))
+long long kv_select_rows(int staged);
 
 // ---- ingest.hip
 // uint8 frames [T][H][W][3] -> planar [T][3][R][R] in [0, 1]: / 255, optional centre crop, antialiased bilinear resize (ATen semantics)

@@ -646,6 +646,7 @@ int Run::detokenize(const int64_t* ids, int B, int F, void* out_pixels, DType ou
       cache->filled = true;
       cache->clamped = e->clamp_out;
       cache->pix_dt = (int)out_dt;
+      cache->ctx = ctx;
     }
   } else if (!planning) {
     CK((int)hipMemcpy2DAsync(out_pixels, (size_t)T * 3 * res * res * psz, cache->ctx_pixels, (size_t)ctx * 3 * res * res * psz,

@@ -559,4 +559,60 @@ int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, h
   return read_flag(e, g, st, ok);
 }
 
+// ---------------------------------------------------------------------------------------- kept-cache row selection (ivg_kv_select)
+// the buffers whose rows belong to the kept trajectories: the K / V slabs in the cache's own format, and what the verification above
+// compares a caller's "same prefix" claim with -- the id rows, the action table, the embeddings snapshot
+static void kv_select_bufs(const ivg_engine* e, const GenBuf& g, std::vector<KvSelectBuf>& out) {
+  const KvCache& k = e->kvc;
+  const long eb = (long)k.elem_bytes(), blk = (long)k.Lmax * k.hd * eb;
+  KvSelectBuf c;
+  c.base = k.base; c.slabs = k.layers * 2; c.row_stride = (long)k.heads * blk; c.slab_stride = (long)k.chunk * c.row_stride;
+  c.heads = k.heads; c.head_stride = blk;
+  if (k.format == KvFormat::Planes24) { c.bytes_a = (long)k.len * k.hd * 2; c.bytes_b = (long)k.len * k.hd; c.plane_b = (long)k.Lmax * k.hd * 2; }
+  else c.bytes_a = (long)k.len * k.hd * eb;
+  out.push_back(c);
+  KvSelectBuf ids;
+  ids.base = (char*)g.ids; ids.row_stride = (long)g.ids_ld * 8; ids.bytes_a = (long)(k.len + 1) * 8; ids.vec = 4;   // (column len: decided, not yet fed)
+  out.push_back(ids);
+  if (k.last_act_T > 0) {
+    KvSelectBuf a;
+    a.base = (char*)g.last_act; a.row_stride = (long)k.last_act_T * e->cfg.action_dim * 4; a.bytes_a = a.row_stride; a.vec = 4;
+    out.push_back(a);
+  }
+  if (k.snap_valid && e->emb_snap) {
+    const long rowb = (long)e->cfg.hidden_size * (long)esz(e->llm_dt);
+    KvSelectBuf s;
+    s.base = e->emb_snap; s.row_stride = (long)e->Lmax * rowb; s.bytes_a = (long)k.len * rowb;
+    out.push_back(s);
+  }
+}
+
+size_t kv_select_scratch_bytes(const ivg_engine* e) {   // (a native K / V slab and the embeddings snapshot are the same size; the id rows the rest)
+  return (size_t)e->kvc.chunk * e->Lmax * std::max<size_t>((size_t)e->cfg.hidden_size * esz(e->llm_dt), 8);
+}
+
+int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st) {
+  KvCache& k = e->kvc;
+  if (k.len <= 0 || k.B <= 0 || !(k.ids_valid || k.snap_valid))
+    return e->fail(IVG_ERR_INVALID, "kv_select: the engine holds no kept cache (the last call was not a per-trajectory generate within the cache chunk, or the format or scales changed since)");
+  if (!parents || n <= 0) return e->fail(IVG_ERR_INVALID, "kv_select: parents must hold at least one row");
+  KvSelectPlan plan;
+  const int prc = kv_select_plan(parents, n, k.B, k.chunk, &plan);
+  if (prc == KV_PLAN_CAPACITY) return e->fail(IVG_ERR_CAPACITY, "kv_select: " + std::to_string(n) + " rows exceed the KV-cache chunk (" + std::to_string(k.chunk) + ")");
+  if (prc != KV_PLAN_OK) return e->fail(IVG_ERR_INVALID, "kv_select: every parent must be a row of the kept cache, [0, " + std::to_string(k.B) + ")");
+  if (plan.n_direct + plan.n_staged > 0) {
+    GenBuf g;
+    gen_layout(e, g, e->gen_buf);
+    std::vector<KvSelectBuf> bufs;
+    kv_select_bufs(e, g, bufs);
+    for (const KvSelectBuf& b : bufs)   // refused before the first launch: a select never leaves the buffers half gathered
+      if (plan.n_staged > 0 && (!e->ws.base || b.staged_bytes_per_slab(plan.n_staged) > e->ws.cap))
+        return e->fail(IVG_ERR_CAPACITY, "kv_select: the workspace does not hold one slab's staged rows");
+    for (const KvSelectBuf& b : bufs) CK(launch_kv_select(b, plan, e->ws.base, e->ws.cap, st));
+    kv_select_note(plan.n_direct, plan.n_staged);
+  }
+  k.B = n;
+  return 0;
+}
+
 }  // namespace ivg

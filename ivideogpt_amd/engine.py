@@ -2,6 +2,7 @@
 library; PyTorch only owns the device buffers (weights, inputs, outputs) and the stream."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -233,6 +234,22 @@ class Engine:
         if self.h is not None and h.value in self._caches:   # (already released when the engine was closed first)
             self._caches.discard(h.value)
             self.lib.ivg_cache_destroy(self.h, h)
+
+    def cache_select(self, h, parents):
+        """``ivg_cache_select``: a new detokenizer cache whose row i is row ``parents[i]`` (host integers) of cache ``h``; ``h`` is unchanged."""
+        p = np.ascontiguousarray(parents, dtype=np.int32)
+        out = C.c_void_p()
+        with self.stream() as s:
+            self.check(self.lib.ivg_cache_select(self.h, h, p.ctypes.data_as(C.c_void_p), int(p.size), C.byref(out), s), "cache_select")
+        self._caches.add(out.value)
+        return out
+
+    def kv_select(self, parents):
+        """``ivg_kv_select``: new row i of the kept K / V cache := old row ``parents[i]`` (host integers).  Enqueued, no synchronisation."""
+        p = np.ascontiguousarray(parents, dtype=np.int32)
+        with self.stream() as s:
+            self.check(self.lib.ivg_kv_select(self.h, p.ctypes.data_as(C.c_void_p), int(p.size), s), "kv_select")
+        return self
 
     def generate(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, reward=None, reuse_kv=False):
         B, L0 = prompt.shape

@@ -16,6 +16,7 @@ import math
 from types import SimpleNamespace
 from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -197,6 +198,51 @@ def _kv_cache_setting(name, k_scale, v_scale, dtype, cfg, scales=None):
     table = tuple(tuple(tuple(_kv_scale_checked(f"scales[{l}][{w}][{h}]", x) for h, x in enumerate(row)) for w, row in enumerate(lay))
                   for l, lay in enumerate(t.tolist()))
     return name, ks, vs, table
+
+
+def normalize_parents(parents, rows=None):
+    """``parents`` of a row selection (a list, a numpy array or a tensor of integers, one dimension, at least one entry) -> a
+    contiguous int32 numpy array on the host.  A device tensor is copied to the host, which synchronises.  ValueError for anything
+    else: another shape, no entry, a type that is not an integer type (bool included), and -- with ``rows`` -- an entry outside
+    ``[0, rows)``."""
+    if isinstance(parents, torch.Tensor):
+        if parents.dtype in (torch.bool,) or parents.is_floating_point() or parents.is_complex():
+            raise ValueError(f"parents must hold integers, not {parents.dtype}")
+        a = parents.detach().cpu().numpy()
+    else:
+        a = np.asarray(parents)
+        if a.size == 0 and a.ndim == 1:
+            raise ValueError("parents must hold at least one row")
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"parents must hold integers, not {a.dtype}")
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"parents must be one-dimensional with at least one row, not of shape {tuple(a.shape)}")
+    lo, hi = int(a.min()), int(a.max())
+    if lo < 0 or hi > 2 ** 31 - 1 or (rows is not None and hi >= rows):
+        raise ValueError(f"every parent must be a row index in [0, {rows if rows is not None else 2 ** 31}), not {lo if lo < 0 else hi}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def stable_parents(parents, B):
+    """The same multiset of ``parents`` (rows of a batch of ``B``), arranged so that every surviving parent keeps its own row wherever
+    possible: ``arranged[v] == v`` for every value ``v < len(parents)`` that occurs in ``parents`` -- the largest number of fixed points
+    any arrangement has -- and the other entries fill the remaining rows in their original order.  ``select_kept_cache(arranged)`` then
+    copies every moved row in place from a row that stays (ivg_kv_select: direct moves only, nothing staged).
+    -> ``(arranged, perm)``, int64 CPU tensors with ``arranged == parents[perm]``: ``perm`` reorders whatever the caller keeps per
+    CHOSEN row (weights, ranks) the same way."""
+    p = normalize_parents(parents, B)
+    n = p.size
+    perm = np.full(n, -1, dtype=np.int64)
+    used = np.zeros(n, dtype=bool)
+    for j, v in enumerate(p):          # the first copy of every surviving parent goes to the parent's own row
+        if v < n and perm[v] < 0:
+            perm[v] = j
+            used[j] = True
+    rest = iter(np.flatnonzero(~used))
+    for i in range(n):
+        if perm[i] < 0:
+            perm[i] = next(rest)
+    return torch.from_numpy(p[perm].astype(np.int64)), torch.from_numpy(perm)
 
 
 class LlamaForCausalLM:
@@ -410,6 +456,25 @@ class LlamaForCausalLM:
             self._engine.set_decode_lds_kb(self._decode_lds_kb)
         return self
 
+    def select_kept_cache(self, parents):
+        """Resamples the KV cache the last ``generate`` call kept (include/ivg.h ivg_kv_select; HF: ``_reorder_cache``): row i of the
+        kept cache becomes what row ``parents[i]`` was -- duplicates, drops, any order, and more rows than before up to the batch the
+        engine was built for (the largest batch this model has run).  A following ``reuse_cache=True`` / ``use_cache=True`` call then
+        accepts the prompt, actions or embeddings gathered by the same ``parents`` (``x[parents]``) and feeds only the last token;
+        anything else is still refused by the on-device comparison.  ``parents``: a list, numpy array or tensor of integers; a device
+        tensor is brought to the host, which synchronises -- the call itself only enqueues copies.  ``stable_parents`` arranges a
+        resampling so that survivors stay in place, the cheapest case.  ValueError, with the kept cache untouched, when there is no
+        kept cache (no call yet, a shared-context call, a change of the K / V format or scales since), for an index outside the kept
+        rows, or for more rows than the engine holds."""
+        p = normalize_parents(parents)
+        if self._engine is None:
+            raise ValueError("select_kept_cache: no kept cache (the model has not generated yet)")
+        try:
+            self._engine.kv_select(p)
+        except (AssertionError, _lib.IvgError) as err:
+            raise ValueError(f"select_kept_cache: {err}") from None
+        return self
+
     # ------------------------------------------------------------------ hot path
     def _uniforms(self, B, n, do_sample, generator):
         if not do_sample:
@@ -620,6 +685,12 @@ class HeadModelWithAction:
     @property
     def kv_scales(self):
         return self.llm.kv_scales
+
+    def select_kept_cache(self, parents):
+        """``LlamaForCausalLM.select_kept_cache``: the kept cache of the last ``generate`` call (its action table included) gathered by
+        ``parents``; continue with ``reuse_cache=True`` on ``inputs_token[parents]`` and ``action[parents]``."""
+        self.llm.select_kept_cache(parents)
+        return self
 
     def calibrate_kv_cache(self, input_ids, action=None, headroom=1, reset=True):
         """``LlamaForCausalLM.calibrate_kv_cache`` with the action embeddings added on every sdf slot (as ``logits``) at this wrapper's

@@ -26,9 +26,22 @@ class DetokenizeCache:
     Unlike the reference's dict (valid only for F == 1 calls) it holds the un-repeated
     per-trajectory context features, so it can be reused with any number of future frames."""
 
-    def __init__(self, engine, B):
+    def __init__(self, engine, B, handle=None):
         self.engine, self.B = engine, B
-        self.handle = engine.cache_create(B)   # the engine owns the device memory: Engine.close releases what is still alive
+        self.handle = handle if handle is not None else engine.cache_create(B)   # the engine owns the device memory: Engine.close releases what is still alive
+
+    def select(self, parents):
+        """A NEW cache whose row i is row ``parents[i]`` of this one (include/ivg.h ivg_cache_select; this cache is unchanged): what
+        ``select_kept_cache`` does to the transformer's cache, for ``detokenize(ids[parents], cache=...)``.  ``parents`` as there (a
+        device tensor synchronises).  ValueError for an index outside this cache's rows, a cache that was never filled, or more rows
+        than the engine's batch."""
+        from .transformer import normalize_parents
+        from ._lib import IvgError
+        p = normalize_parents(parents, self.B)
+        try:
+            return DetokenizeCache(self.engine, int(p.size), self.engine.cache_select(self.handle, p))
+        except (AssertionError, IvgError) as err:
+            raise ValueError(f"DetokenizeCache.select: {err}") from None
 
     def __del__(self):
         try:

@@ -105,12 +105,22 @@ class VideoPredictor:
         return self
 
     @torch.no_grad()
-    def rollout(self, obs, policy, horizon, return_uncertainty=False):
+    def rollout(self, obs, policy, horizon, return_uncertainty=False, select=None):
         """obs [B, 9, H, W] in 0..255 (3 stacked RGB frames); policy(obs, t) -> [B, A].
         -> (obss [B, horizon+1, 9, H, W], actions [B, horizon+1, A], rewards [B, horizon+1, 1])
         ``return_uncertainty=True`` appends ``uncertainty [B, horizon+1, 1]``: per imagined step the mean predictive entropy (nats) of
         the model over the frame's 16 sampled tokens (``TokenScores.per_frame``), 0 for the dummy step 0; no ``symexp``, no transform --
-        for MOPO / MOReL-style penalties and rollout truncation."""
+        for MOPO / MOReL-style penalties and rollout truncation.
+        ``select`` (not in the reference): resampling in the middle of the rollout -- truncation of uncertain trajectories, particle
+        resampling, beam or successive-halving planners.  After every imagined step ``select(t, obs [B, 9, H, W], reward [B, 1],
+        uncertainty [B, 1] or None)`` -- this step's values as the results hold them -- returns ``None`` (go on) or ``parents``
+        (list / array / tensor of n row indices): row i of the rollout becomes a copy of row ``parents[i]``.  The engine's kept KV
+        cache (``select_kept_cache``), the detokenizer cache (``DetokenizeCache.select``), the prompt, the embeddings, the frame stack
+        and every earlier entry of the trace are gathered, so the next step still runs on the kept cache (``steps_with_kept_cache``),
+        ``policy`` sees n rows from then on, and the returned tensors are the genealogies of the FINAL rows, with batch dimension n.
+        n may exceed B up to the batch the models' engines were built for.  ``ivideogpt_amd.transformer.stable_parents`` keeps
+        survivors in their rows, the cheapest resampling.  ``select=None``: exactly the rollout without it."""
+        from ivideogpt_amd.transformer import normalize_parents
         ctx, model, llm = self.context_length, self.model, self.model.llm
         B = obs.shape[0]
         obs = obs.to(self.device).float() / 255.
@@ -137,6 +147,18 @@ class VideoPredictor:
             trace["obs"].append(obs); trace["act"].append(action); trace["rew"].append(reward)
             if return_uncertainty:
                 trace["unc"].append(result.token_scores.per_frame()[1])       # [B, 1]: the 16 sampled tokens of this step's frame
+            if select is not None:
+                parents = select(t, obs, symexp(reward) if self.symlog else reward, trace["unc"][-1] if return_uncertainty else None)
+                if parents is not None:
+                    p = normalize_parents(parents, obs.shape[0])
+                    if p.tolist() != list(range(obs.shape[0])):                   # (the identity: nothing to do)
+                        llm.select_kept_cache(p)
+                        cache = cache.select(p)
+                        idx = torch.from_numpy(p).to(self.device, torch.int64)
+                        embeds, prompt, obs, first_obs = embeds[idx], prompt[idx], obs[idx], first_obs[idx]
+                        stack = [f[idx] for f in stack]
+                        trace = {k: [x[idx] for x in v] for k, v in trace.items()}
+                        sdf_col = sdf_col[:1].expand(p.size, 1)
         # dummy step 0: the initial observation with a zero action / reward
         obss = torch.stack([first_obs] + trace["obs"], 1).float()
         actions = torch.stack([torch.zeros_like(trace["act"][0])] + trace["act"], 1).float()
