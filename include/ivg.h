@@ -294,6 +294,37 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
  * a row is). */
 int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream stream);
 
+/* Extend the kept cache with GIVEN tokens (teacher forcing), or rewind it: afterwards it holds positions [0, L0 - 1) of prompt, of which
+ * [0, keep_len) are the kept rows as they were and [keep_len, L0 - 1) are appended by this call.  T = L0 - 1 - keep_len.  For callers
+ * that replace an imagined frame by the one they then observed, teacher-force ground-truth frames after the context, or rewind a few
+ * frames and branch -- without a prompt pass over the whole prefix.
+ *
+ * Precondition: the engine holds a kept cache built from ids (ivg_generate, _continue, _forced_sdf, _frames / _scored with
+ * group_size == 1, ivg_kv_select or this entry) of exactly B trajectories at length len; 1 <= keep_len <= min(len, L0 - 1);
+ * prompt[:, :keep_len] equals the kept id rows; the cache was built the same way (with / without actions, the same ctx, the same act_T)
+ * and the action rows baked into the sdf slots at positions < keep_len equal the presented ones.  Verified on the device as for
+ * ivg_generate_continue: one stream synchronisation.
+ * Refusals, each before anything but that comparison is launched -- outputs untouched, the kept cache usable exactly as it was:
+ *   IVG_ERR_INVALID   no kept cache; a cache built from input embeddings (ivg_generate_embeds); another B; keep_len out of range; any
+ *                     mismatch; an action table too short for the sdf slots among positions [0, L0 - 1) (or longer than max_frames)
+ *   IVG_ERR_CAPACITY  L0 - 1 above the cache length
+ * Effect: position p in [keep_len, L0 - 1) is fed embed_tokens[prompt[b][p]], plus action_linear(actions[b][i + ctx - 1]) when
+ * p = 257*ctx - 1 + 17 i is an sdf slot and actions != NULL, and every layer's K / V rows are appended at p in the cache's own format.
+ * The kept state is then: length L0 - 1, id columns [keep_len, L0 - 1] equal to prompt, the kept action table equal to actions -- so
+ * ivg_generate_continue(prompt, L0, ..) is accepted, and ivg_kv_select, another ivg_kv_extend or ivg_generate_fanout.  Cache rows at
+ * positions >= L0 - 1 are neither read nor written.  T == 0 is a pure rewind (also with keep_len < len: branch from an earlier frame):
+ * nothing is launched after the verification.  No captured step graph is invalidated.
+ *   token_nll_out  float32 (B, T) or NULL: column c = -log softmax(z_p)[prompt[b][p + 1]], p = keep_len + c, z_p the fp32 lm_head row of
+ *                  position p (natural logarithm, the arithmetic of ivg_eval_forward's token_nll): how surprised the model was by each
+ *                  given token.  An id outside [0, vocab) gives 0.
+ * Two routes.  A native bf16 cache at head_dim 64 makes ONE pass over the B * T rows through the prompt-pass GEMMs with
+ * chunk_attn_kernel as its attention (every K / V row read once per 32 query rows).  Every other engine (fp32, other head dims, the FP8
+ * and 24-bit caches; or IVG_KV_EXTEND_CHUNK=0 under IVG_DEV=1) runs T decode steps with the given inputs instead of sampled ones, which
+ * appends bit for bit what a rollout that had sampled these tokens would have appended.  ivg_debug_counter("kv_extend_chunk_rows" /
+ * "kv_extend_step_rows") count B * T per call of either route. */
+int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0,
+                  const float* actions, int act_T, int ctx, float* token_nll_out /* (B, L0 - 1 - keep_len) or NULL */, ivg_stream stream);
+
 /* Per-frame rewards and hidden states of one rollout call (the reference's generate is declared to return `reward (B, segment -
  * context)` and leaves it a TODO, action_model.py:83-99,118-120; its forward reads reward_linear at the hidden state of every frame's
  * 16th token, :198-204).
@@ -385,6 +416,26 @@ int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
  *                       dtype -> float32 (rows). */
 int ivg_embed_tokens(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, void* out, ivg_stream stream);
 int ivg_action_linear(ivg_engine* e, const float* actions, int rows, void* out, ivg_stream stream);
+/* Fan candidates out of the kept cache: ivg_generate_scored with group_size > 1 whose shared prefix is not prefilled -- it IS the kept
+ * cache.  prompt has one row per group; actions, uniforms and every output have n_groups * group_size rows, group-major.  Arguments,
+ * outputs and the frame / score conditions are those of ivg_generate_scored, except that an action-conditioned prompt may hold
+ * generated frames (L0 = 257*ctx + 17 t, as for ivg_generate_continue).
+ * Precondition: the kept cache, built from ids, holds positions [0, L0 - 1) of exactly n_groups trajectories that equal
+ * prompt[:, :L0 - 1], under the same ctx and the same with / without actions (verified as for ivg_generate_continue).  The action rows
+ * of the candidates that belong to sdf slots already in the cache are neither read nor compared: the kept action table defined those
+ * cache rows.  Candidate b = s * group_size + k reads key rows < L0 - 1 from cache row s and appends its own from position L0 - 1 on
+ * in cache row b (decode_attn_kernel SHARED), in every cache format.
+ * Refusals, before anything is launched or written, kept cache untouched: IVG_ERR_CAPACITY for n_groups * group_size above the cache
+ * chunk (min(max_batch, 128)); IVG_ERR_INVALID without such a kept cache or on a mismatch; everything ivg_generate_scored refuses.
+ * Afterwards the kept state is exactly what it was -- length L0 - 1, n_groups rows, the same ids, the same action table (the
+ * candidates' rows lie at positions >= L0 - 1, outside it): the caller can fan out again, ivg_generate_continue with the chosen action,
+ * or ivg_kv_extend with what it observed. */
+int ivg_generate_fanout(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
+                        const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out /* (n_groups * group_size, n_new / 17) or NULL */,
+                        void* frame_hidden_out /* (n_groups * group_size, n_new / 17, hidden) llm dtype or NULL */,
+                        float* token_scores_out /* (n_groups * group_size, n_new, 3) or NULL */, ivg_stream stream);
+
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                         void* hidden_out, int allow_reuse, int* reused_out, ivg_stream stream);
 int ivg_generate_embeds_scored(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k,
@@ -572,6 +623,13 @@ int ivg_op_shared_decode_attn(const void* qkv, void* kc, void* vc, void* out, co
  * which covers bf16 and hd = 64 only: IVG_ERR_INVALID otherwise.  cos_t / sin_t: [Lmax][hd / 2] fp32 as the engine holds them. */
 int ivg_op_prefill_attn(void* qkv, void* kc, void* vc, void* vt, void* out, const float* cos_t, const float* sin_t, int B, int L, int heads, int hd,
                         int Lmax, int dtype, ivg_stream stream);
+/* One layer's attention of ivg_kv_extend's chunk pass: T tokens per trajectory at positions [pos0, pos0 + T) against a cache that holds
+ * [0, pos0).  qkv [B * T][3 * heads * hd] gets RoPE (at pos0 + t) applied to q in place; the roped k and the v of row (b, t) are written
+ * to row pos0 + t of kc / vc [B][heads][Lmax][hd] (no other row is touched); out [B * T][heads * hd] = softmax(q k^T / sqrt(hd), key j
+ * visible to row t iff j <= pos0 + t) v by chunk_attn_kernel.  bf16 and hd = 64 only; IVG_ERR_INVALID before any launch otherwise, and
+ * for pos0 < 0, T < 1, pos0 + T > Lmax, or qkv / kc / vc not 16-byte, out not 8-byte aligned. */
+int ivg_op_chunk_attn(void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int T, int heads, int hd, int Lmax,
+                      int pos0, int dtype, ivg_stream stream);
 /* one top-k draw per logits row [B][V] fp32 with the rollout's sampler (uniforms [B] in [0,1), or NULL = greedy): HF
  * TemperatureLogitsWarper (logits / temperature, > 0) + TopKLogitsWarper + softmax + draw as restated by oracle/llama.py
  * sample_from_logits */
@@ -627,7 +685,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

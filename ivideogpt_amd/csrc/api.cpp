@@ -692,7 +692,7 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
   {  // same (batch, length) is not enough: another caller may have used the model in between.  Compare the cached prefix
      // (token ids + the action rows baked into its sdf slots) with the prompt on the device (one stream synchronisation).
     bool same = false;
-    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0, actions, act_T, ctx, (hipStream_t)stream, &same));
+    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0 - 1, actions, act_T, ctx, (hipStream_t)stream, &same));
     if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
   }
   GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
@@ -706,20 +706,54 @@ int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream strea
   return kv_select(e, parents, n, (hipStream_t)stream);
 }
 
+int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0, const float* actions, int act_T, int ctx,
+                  float* token_nll_out, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "kv_extend: engine was created without a transformer");
+  const KvCache& k = e->kvc;
+  if (!prompt) return e->fail(IVG_ERR_INVALID, "kv_extend: null prompt");
+  if (k.len <= 0 || k.B <= 0 || !(k.ids_valid || k.snap_valid))
+    return e->fail(IVG_ERR_INVALID, "kv_extend: the engine holds no kept cache (the last call was not a per-trajectory generate within the cache chunk, or the format or scales changed since)");
+  if (!k.ids_valid) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache was built from input embeddings (only caches built from ids are extended)");
+  if (L0 - 1 > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "kv_extend: " + std::to_string(L0 - 1) + " positions exceed the KV cache (" + std::to_string(e->Lmax) + ")");
+  if (B != k.B) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache holds " + std::to_string(k.B) + " trajectories, the call presents " + std::to_string(B));
+  if (keep_len < 1 || keep_len > k.len || keep_len > L0 - 1)
+    return e->fail(IVG_ERR_INVALID, "kv_extend: keep_len must lie in [1, min(" + std::to_string(k.len) + " kept positions, L0 - 1)]");
+  if (actions) {
+    if (e->cfg.action_dim <= 0 || !e->act_w) return e->fail(IVG_ERR_INVALID, "kv_extend: actions given but the model is action-free");
+    const int slots = std::max(0, (L0 - 1 - (257 * ctx - 1) + 16) / 17);   // sdf slots among positions [0, L0 - 1)
+    if (ctx < 1 || act_T < 1 || act_T > e->cfg.max_frames || (slots > 0 && ctx - 1 + slots > act_T))
+      return e->fail(IVG_ERR_INVALID, "kv_extend: action tensor too short for the sdf slots of the prompt (or longer than max_frames)");
+  }
+  bool same = false;
+  IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, keep_len, actions, act_T, ctx, (hipStream_t)stream, &same));
+  if (!same) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache was built from a different prefix (tokens, actions or context length differ)");
+  if (keep_len == L0 - 1) {   // a pure rewind: the kept rows [0, keep_len) are what they were, nothing is launched
+    e->kvc.len = keep_len;
+    return IVG_OK;
+  }
+  ExtendReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.keep_len = keep_len; q.L0 = L0; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
+  q.token_nll = token_nll_out; q.chunk = kv_extend_chunk_covers(e);
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.extend(q); });
+}
+
 // ivg_generate_frames (need_frames: its conditions on the schedule and the lengths always hold) and ivg_generate_scored (they hold only
 // when a frame output is asked for: without one the entry also stands for the action-free ivg_generate)
 static int generate_frames_scored(ivg_engine* e, bool need_frames, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new,
                                   const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int group_size, int kept_cache,
                                   int force_sdf, int64_t* ids_out, float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out,
-                                  ivg_stream stream) {
+                                  ivg_stream stream, bool fanout = false) {
   if (!e) return IVG_ERR_INVALID;
-  const bool shared = group_size > 1, cont = kept_cache != 0;
+  // fanout (ivg_generate_fanout): B = n_groups * group_size candidates whose groups' prefixes are the kept cache's rows -- the lengths
+  // and the action table are checked as for a kept-cache call (the prompt may hold generated frames), the rows as for a shared one
+  const bool shared = group_size > 1 && !fanout, cont = kept_cache != 0;
   const char* own = nullptr;
   if (group_size < 1 || (shared && (B <= 0 || B % group_size != 0))) own = "generate_frames: B must be a positive multiple of a positive group_size";
+  else if (fanout && (group_size < 1 || B <= 0 || B % group_size != 0)) own = "generate_fanout: n_groups and group_size must be positive";
   else if (cont && shared) own = "generate_frames: a kept cache is per trajectory (group_size must be 1)";
   else if (need_frames && !actions && !force_sdf) own = "generate_frames: frames exist under the forced-sdf schedule only (actions or force_sdf)";
   else if (cont && !(actions && e->cfg.action_dim > 0 && e->act_w)) own = "generate_continue: action-conditioned models only";
-  IVG_TRY(check_generate(e, shared ? GEN_SHARED : cont ? GEN_CONTINUE : GEN_PLAIN, own, B, L0, n_new, actions, act_T, ctx));
+  IVG_TRY(check_generate(e, shared ? GEN_SHARED : (cont || fanout) ? GEN_CONTINUE : GEN_PLAIN, own, B, L0, n_new, actions, act_T, ctx));
   if (need_frames && n_new < 17) return e->fail(IVG_ERR_INVALID, "generate_frames: a frame needs 17 new tokens (its 16th must be fed)");
   if (need_frames && (ctx < 1 || L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0))
     return e->fail(IVG_ERR_INVALID, "generate_frames: the prompt must hold 257*ctx + 17*t tokens (frames count from the first new token)");
@@ -730,11 +764,22 @@ static int generate_frames_scored(ivg_engine* e, bool need_frames, const int64_t
       return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
                                           " trajectories, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(B));
     bool same = false;
-    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0, actions, act_T, ctx, (hipStream_t)stream, &same));
+    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0 - 1, actions, act_T, ctx, (hipStream_t)stream, &same));
     if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
   }
+  if (fanout) {
+    const int n_groups = B / group_size;
+    if (B > e->kvc.chunk)
+      return e->fail(IVG_ERR_CAPACITY, "generate_fanout: " + std::to_string(B) + " candidates exceed the KV-cache chunk (" + std::to_string(e->kvc.chunk) + ")");
+    if (!e->kvc.ids_valid || !e->kvc.holds(n_groups, L0 - 1))
+      return e->fail(IVG_ERR_INVALID, "generate_fanout: the kept KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
+                                          " trajectories built from ids, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(n_groups));
+    bool same = false;
+    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, n_groups, L0 - 1, actions, act_T, ctx, (hipStream_t)stream, &same, true));
+    if (!same) return e->fail(IVG_ERR_INVALID, "generate_fanout: the kept KV cache was built from a different prefix (tokens, context length or action conditioning differ)");
+  }
   GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
-  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = force_sdf != 0; q.group = group_size; q.reuse_kv = cont;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = force_sdf != 0; q.group = group_size; q.reuse_kv = cont; q.fanout = fanout;
   q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
 }
@@ -751,6 +796,15 @@ int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
                         float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
   return generate_frames_scored(e, frame_rewards_out || frame_hidden_out, prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k,
                                 group_size, kept_cache, force_sdf, ids_out, frame_rewards_out, frame_hidden_out, token_scores_out, stream);
+}
+
+int ivg_generate_fanout(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
+                        const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out,
+                        float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
+  const bool sized = n_groups > 0 && group_size > 0 && (long)n_groups * group_size <= INT32_MAX;
+  return generate_frames_scored(e, frame_rewards_out || frame_hidden_out, prompt, prompt_stride, sized ? n_groups * group_size : 0, L0, n_new, actions, act_T,
+                                ctx, uniforms, top_k, sized ? group_size : 0, 0, force_sdf, ids_out, frame_rewards_out, frame_hidden_out, token_scores_out,
+                                stream, true);
 }
 
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
@@ -1212,6 +1266,8 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "token_scores")) return token_scores_launches();
   if (name && !strcmp(name, "kv_select_direct")) return kv_select_rows(0);
   if (name && !strcmp(name, "kv_select_staged")) return kv_select_rows(1);
+  if (name && !strcmp(name, "kv_extend_chunk_rows")) return kv_extend_rows(0);
+  if (name && !strcmp(name, "kv_extend_step_rows")) return kv_extend_rows(1);
   return -1;
 }
 
@@ -1295,6 +1351,19 @@ int ivg_op_prefill_attn(void* qkv, void* kc, void* vc, void* vt, void* out, cons
   hipStream_t st = (hipStream_t)stream;
   int rc = launch_rope_kv(qkv, kc, vc, vt, Lp, cos_t, sin_t, B, L, heads, hd, Lmax, nullptr, 0, (DType)dtype, st);
   if (rc == 0 && out) rc = launch_flash_prefill(qkv, kc, vt, out, B, L, Lp, heads, hd, Lmax, (DType)dtype, st);
+  return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
+}
+
+int ivg_op_chunk_attn(void* qkv, void* kc, void* vc, void* out, const float* cos_t, const float* sin_t, int B, int T, int heads, int hd, int Lmax,
+                      int pos0, int dtype, ivg_stream stream) {
+  // unit-test hook of one layer's attention in ivg_kv_extend's chunk pass: rope_kv at pos0 (q in place, K / V appended at positions
+  // [pos0, pos0 + T), no V^T) then chunk_attn_kernel -- what Run::prefill launches per layer in append mode.  Everything it does not
+  // cover is refused before anything is written
+  if (dtype != IVG_BF16 || hd != 64 || B <= 0 || heads <= 0 || T < 1 || pos0 < 0 || (long)pos0 + T > Lmax) return IVG_ERR_INVALID;
+  if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7) || ((uintptr_t)kc & 15) || ((uintptr_t)vc & 15)) return IVG_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_rope_kv(qkv, kc, vc, nullptr, 0, cos_t, sin_t, B, T, heads, hd, Lmax, nullptr, pos0, BF16, st);
+  if (rc == 0) rc = launch_chunk_attn(qkv, kc, vc, out, B, T, heads, hd, Lmax, pos0, BF16, st);
   return rc == 0 ? IVG_OK : (rc > 0 ? IVG_ERR_HIP : IVG_ERR_INVALID);
 }
 

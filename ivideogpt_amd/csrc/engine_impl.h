@@ -23,6 +23,17 @@ struct PrefillReq {
   const void* embeds = nullptr;     // [B][L][H] llm dtype: used instead of the embedding of ids
   void* hidden_all = nullptr;       // [B][L][H] llm dtype: post-final-norm hidden states (eval heads)
   const int64_t* labels = nullptr; float* token_nll = nullptr;   // [B][L]: shifted cross-entropy per position
+  // ivg_kv_extend's chunk pass: the L rows are positions [pos0, pos0 + L) appended to the kept cache (`ids` points at column pos0);
+  // next_ids (stride ids_stride, pointing at column pos0 + 1): the given next tokens token_nll [B][L] is taken against, instead of labels
+  bool append = false; int pos0 = 0; const int64_t* next_ids = nullptr;
+};
+
+// ivg_kv_extend: positions [keep_len, L0 - 1) of `prompt` teacher-forced onto the kept cache (arguments already checked and verified)
+struct ExtendReq {
+  const int64_t* prompt = nullptr; int64_t prompt_stride = 0; int B = 0, keep_len = 0, L0 = 0;
+  const float* actions = nullptr; int act_T = 0, ctx = 1;
+  float* token_nll = nullptr;       // [B][L0 - 1 - keep_len] or null
+  bool chunk = false;               // route: one chunk pass (native bf16 cache, head_dim 64) or decode steps with given inputs
 };
 
 // One rollout of n_new tokens after a prompt of L0, for B trajectories
@@ -36,6 +47,7 @@ struct GenerateReq {
   // returned (new_ids_out [B][n_new]); hidden_out [B][H]: post-norm hidden state of the last forward pass
   const void* embeds = nullptr; int64_t* new_ids_out = nullptr; void* hidden_out = nullptr;
   bool force_sdf = false;           // every 17th new token is the forced sdf even without actions (generate_without_action)
+  bool fanout = false;              // ivg_generate_fanout: a shared-context rollout whose prefix [0, L0 - 1) IS the kept cache (no prompt pass)
   int group = 1;                    // > 1: shared-context rollout, `prompt` holds one row per group of `group` consecutive trajectories
   // ivg_generate_frames: reward / post-norm hidden state of every frame whose 16th token is fed, [B][n_new / 17] and [B][n_new / 17][H]
   float* frame_rewards_out = nullptr; void* frame_hidden_out = nullptr;
@@ -80,6 +92,7 @@ struct Run {
   // ---- transformer (transformer.cpp)
   int prefill(const PrefillReq& q);
   int generate(const GenerateReq& q);
+  int extend(const ExtendReq& q);
 
   // ---- measurement
   void prof_begin(DType dt, double flops, double bytes, int base = 0);   // base 0: igemm classes, 2: conv3x3 classes
@@ -92,8 +105,10 @@ int build_tokenizer(ivg_engine* e);
 int build_transformer(ivg_engine* e);
 size_t gen_buffer_bytes(const ivg_engine* e);
 // device-side verification (one stream synchronisation) that the kept KV cache was built from this very prefix
-int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, const float* actions, int act_T,
-                          int ctx, hipStream_t st, bool* ok);
+// (positions [0, len) of B kept trajectories, 1 <= len <= the kept length; ids_only: the action rows of the cached slots are not compared)
+int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int len, const float* actions, int act_T,
+                          int ctx, hipStream_t st, bool* ok, bool ids_only = false);
+bool kv_extend_chunk_covers(const ivg_engine* e);   // ivg_kv_extend takes the chunk pass on this engine (format, element type, head dim, switch)
 int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, hipStream_t st, bool* ok);
 // ivg_kv_select: the kept cache's rows, and everything the verification above compares them with, gathered by `parents`
 int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st);

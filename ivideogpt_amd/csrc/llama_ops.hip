@@ -367,6 +367,201 @@ int launch_flash_prefill(const void* qkv, const void* kc, const void* vt, void* 
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ chunk attention (ivg_kv_extend)
+// T given tokens appended to a kept cache: query rows t = 0 .. T-1 of one (trajectory, head) at positions pos0 + t against keys
+// [0, pos0 + t] of the cache, whose rows [pos0, pos0 + T) launch_rope_kv(pos0) has just appended.  bf16, head_dim 64.
+// Workgroup = one tile of 16 * NQ query rows; its key range [0, nk), nk = pos0 + (last row of the tile) + 1, is cut into 64-key tiles and
+// tile kt belongs to wave kt % 4: every K / V row is read once per query tile.  Per tile, flash_prefill_kernel's dataflow:
+//   S = K Q^T      a = K rows straight from the cache, b = Q rows                          -> lane: S[key = 16 sub + 4 lg + r][q = lr]
+//   online softmax in fp32 per wave (a row lives in the 4 lanes lr + 16 lg); P rounded to bf16 for P.V, the row sum keeps the fp32 P
+//   O += V^T P     b = the lane's own S registers (K index of a 32-key step pr: element j = key (2 pr + j / 4) * 16 + 4 lg + j % 4)
+//                  a = V^T in that key order.  V is row-major in the cache and no V^T image of past rows exists: the wave stages its
+//                  tile row-major in LDS and reads it back transposed (ds_read_b64_tr_b16: the 16 lanes of group lg fetch keys
+//                  (2 pr + half) * 16 + 4 lg + 0..3 x channels 16 d .. 16 d + 15, lane lr receives channel 16 d + lr of the 4 keys)
+// The four waves' (max, sum, O) are merged by wave 0 in the order 0, 1, 2, 3 (LDS, no atomics).  Keys past a row's diagonal are masked
+// by select; V rows >= nk are staged as zeros (they may hold NaN, and P = 0 would not silence that).  A row's result depends on
+// (pos0, T, t) and its own trajectory's data only.
+template <int NQ>
+__global__ __launch_bounds__(256) void chunk_attn_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ kc,
+                                                         const bf16_t* __restrict__ vc, bf16_t* __restrict__ out, int T, int pos0,
+                                                         int heads, int Lmax, float scale) {
+  constexpr int HD = 64, QT = 16 * NQ, PITCH = HD + 8;   // staged V rows of 144 bytes: 16-byte chunks in, 8-byte transposed reads out
+  typedef short s16x4 __attribute__((ext_vector_type(4)));
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lg = lane >> 4;
+  const int bh = blockIdx.y, b = bh / heads, h = bh - b * heads;
+  const int H = heads * HD;
+  const int t0 = blockIdx.x * QT;
+  const int nk = pos0 + (t0 + QT < T ? t0 + QT : T);   // keys any row of this tile sees: [0, nk)
+  const int ntile = (nk + 63) >> 6;
+  // one buffer: the four waves' V tiles during the key loop, then the partial O of waves 1 .. 3 for the merge
+  __shared__ __attribute__((aligned(16))) bf16_t sbuf[4 * 64 * PITCH];
+  __shared__ float sM[4][QT], sL[4][QT];
+  bf16_t* sV = sbuf + wave * 64 * PITCH;
+  bf16x8 qf[NQ][2];
+  int qpos[NQ];
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    const int t = t0 + n * 16 + lr, tc = t < T ? t : T - 1;   // rows past T repeat the last one and are not stored
+    qpos[n] = pos0 + tc;
+    const bf16_t* qrow = qkv + ((long)b * T + tc) * 3 * H + h * HD;
+    qf[n][0] = *(const bf16x8*)(qrow + lg * 8);
+    qf[n][1] = *(const bf16x8*)(qrow + 32 + lg * 8);
+  }
+  const bf16_t* kb = kc + (long)bh * Lmax * HD;
+  const bf16_t* vb = vc + (long)bh * Lmax * HD;
+  f32x4 o[NQ][4];
+  float m[NQ], lsum[NQ];
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    m[n] = -INFINITY; lsum[n] = 0.f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[n][d] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int kt = wave; kt < ntile; kt += 4) {   // (wave-uniform trip count: every lane is active at the transposed reads)
+    const int k0 = kt * 64;
+    bf16x8 kf[4][2];
+#pragma unroll
+    for (int sub = 0; sub < 4; ++sub) {
+      const int kr = k0 + sub * 16 + lr;
+      const bf16_t* krow = kb + (long)(kr < Lmax ? kr : Lmax - 1) * HD;   // rows past the diagonal are masked below
+      kf[sub][0] = *(const bf16x8*)(krow + lg * 8);
+      kf[sub][1] = *(const bf16x8*)(krow + 32 + lg * 8);
+    }
+    Chunk16 pv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = i * 8 + (lane >> 3);
+      pv[i] = k0 + row < nk ? *(const Chunk16*)(vb + (long)(k0 + row) * HD + (lane & 7) * 8) : Chunk16{0u, 0u, 0u, 0u};
+    }
+    __builtin_amdgcn_wave_barrier();   // the wave's transposed reads of the previous tile come before these stores
+#pragma unroll
+    for (int i = 0; i < 8; ++i) *(Chunk16*)(sV + (i * 8 + (lane >> 3)) * PITCH + (lane & 7) * 8) = pv[i];
+    __builtin_amdgcn_wave_barrier();   // LDS operations of one wave complete in order: the reads below see every lane's stores
+    bf16x8 vf[4][2];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr) {
+        bf16x4 half[2];
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          const bf16_t* p = sV + ((2 * pr + hh) * 16 + 4 * lg + (lr >> 2)) * PITCH + d * 16 + 4 * (lr & 3);
+          half[hh] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)p));
+        }
+        vf[d][pr] = bf16x8{half[0][0], half[0][1], half[0][2], half[0][3], half[1][0], half[1][1], half[1][2], half[1][3]};
+      }
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) {
+      f32x4 sc[4];
+      float mt = -INFINITY;
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub) {
+        sc[sub] = f32x4{0.f, 0.f, 0.f, 0.f};
+        sc[sub] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[sub][0], qf[n][0], sc[sub], 0, 0, 0);
+        sc[sub] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[sub][1], qf[n][1], sc[sub], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = k0 + sub * 16 + lg * 4 + r;
+          sc[sub][r] = key <= qpos[n] ? sc[sub][r] * scale : -INFINITY;
+          mt = fmaxf(mt, sc[sub][r]);
+        }
+      }
+      mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+      const float mn = fmaxf(m[n], mt);
+      const float ms = mn == -INFINITY ? 0.f : mn;   // a wave's tiles may all lie past an early row's diagonal: its P stays 0
+      const float alpha = expf(m[n] - ms);           // first visible tile: exp(-inf) = 0
+      m[n] = mn;
+      float ps = 0.f;
+      bf16x8 pf[2];
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pw = expf(sc[sub][r] - ms);
+          ps += pw;
+          pf[sub >> 1][(sub & 1) * 4 + r] = (bf16_t)pw;
+        }
+      lsum[n] = lsum[n] * alpha + ps;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[n][d][r] *= alpha;
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) o[n][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[d][pr], pf[pr], o[n][d], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    lsum[n] += __shfl_xor(lsum[n], 16, 64);
+    lsum[n] += __shfl_xor(lsum[n], 32, 64);
+    if (lg == 0) { sM[wave][n * 16 + lr] = m[n]; sL[wave][n * 16 + lr] = lsum[n]; }
+  }
+  __syncthreads();   // every wave is done with its V tiles
+  float* sO = (float*)sbuf;   // [wave - 1][n][d][r][lane]
+  if (wave > 0) {
+#pragma unroll
+    for (int n = 0; n < NQ; ++n)
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sO[((((wave - 1) * NQ + n) * 4 + d) * 4 + r) * 64 + lane] = o[n][d][r];
+  }
+  __syncthreads();
+  if (wave != 0) return;
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    const int qi = n * 16 + lr, t = t0 + qi;
+    float M = m[n];   // finite: key 0 is in tile 0, wave 0's, and every row sees it
+#pragma unroll
+    for (int w = 1; w < 4; ++w) M = fmaxf(M, sM[w][qi]);
+    const float s0 = expf(m[n] - M);
+    float L = lsum[n] * s0;
+    f32x4 acc[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[d][r] = o[n][d][r] * s0;
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const float sw_ = expf(sM[w][qi] - M);   // a wave without a visible key: exp(-inf) = 0 times its zeros
+      L += sL[w][qi] * sw_;
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[d][r] += sO[((((w - 1) * NQ + n) * 4 + d) * 4 + r) * 64 + lane] * sw_;
+    }
+    if (t < T) {
+      const float inv = 1.0f / L;
+      bf16_t* orow = out + ((long)b * T + t) * H + h * HD + lg * 4;
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        *(bf16x4*)(orow + d * 16) = bf16x4{(bf16_t)(acc[d][0] * inv), (bf16_t)(acc[d][1] * inv), (bf16_t)(acc[d][2] * inv), (bf16_t)(acc[d][3] * inv)};
+    }
+  }
+}
+
+// qkv: [B*T][3H] with q roped in place; kc / vc: [B][heads][Lmax][64] holding positions [0, pos0 + T); out [B*T][H].  bf16, head_dim 64
+// only (-1 otherwise, and for a chunk that does not fit the cache: nothing is launched)
+int launch_chunk_attn(const void* qkv, const void* kc, const void* vc, void* out, int B, int T, int heads, int hd, int Lmax, int pos0,
+                      DType dt, hipStream_t st) {
+  if (dt != BF16 || hd != 64 || B <= 0 || heads <= 0 || T < 1 || pos0 < 0 || (long)pos0 + T > Lmax) return -1;
+  if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7) || ((uintptr_t)kc & 15) || ((uintptr_t)vc & 15)) return -1;
+  const float scale = 1.0f / sqrtf((float)hd);
+  if (T > 16)   // 32 query rows per workgroup: a 17-token frame reads its K / V rows once
+    hipLaunchKernelGGL(chunk_attn_kernel<2>, dim3((unsigned)cdiv(T, 32), (unsigned)(B * heads)), dim3(256), 0, st, (const bf16_t*)qkv,
+                       (const bf16_t*)kc, (const bf16_t*)vc, (bf16_t*)out, T, pos0, heads, Lmax, scale);
+  else
+    hipLaunchKernelGGL(chunk_attn_kernel<1>, dim3(1u, (unsigned)(B * heads)), dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)kc,
+                       (const bf16_t*)vc, (bf16_t*)out, T, pos0, heads, Lmax, scale);
+  return (int)hipGetLastError();
+}
+
+static std::atomic<long long> g_kv_extend_rows[2] = {{0}, {0}};
+void kv_extend_note(int chunk_rows, int step_rows) { g_kv_extend_rows[0] += chunk_rows; g_kv_extend_rows[1] += step_rows; }
+long long kv_extend_rows(int stepwise) { return g_kv_extend_rows[stepwise ? 1 : 0].load(); }
+
 // ------------------------------------------------------------------------------------------------ tokenizer cross-attention
 // CrossAttentionBlock's multi-head attention (ivideogpt/vq_model/conditional_vae.py:38-55) in one pass, bf16:
 // every future frame's P = side^2 query tokens attend to the kv = ctx * P projected context tokens of ITS trajectory.  Replaces the
@@ -2009,14 +2204,9 @@ long long token_scores_launches() { return g_token_scores_launches.load(); }
 // Shifted cross-entropy of teacher-forced logits (HF ForCausalLM loss, train_gpt.py:356-376): row r = (b, l) of a chunk of logits
 // [rows][V] fp32 predicts labels[b][l + 1]; nll[r] = logsumexp(logits[r]) - logits[r][target], 0 where the target is -100 (or l is
 // the last position).  One workgroup per row, fixed-order reductions.
-__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long row0,
-                                                      int L, int V, float* __restrict__ nll) {
-  __shared__ float red[8];
-  const long r = row0 + blockIdx.x;
-  const int l = (int)(r % L), tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const long tgt = l + 1 < L ? labels[r + 1] : -100;
-  if (tgt < 0 || tgt >= V) { if (tid == 0) nll[r] = 0.f; return; }
-  const float* row = logits + (long)blockIdx.x * V;
+// nll of one logits row against `tgt`, by the whole workgroup (the value is valid in thread 0); red: 8 floats of LDS
+__device__ __forceinline__ float ce_row_nll(const float* __restrict__ row, long tgt, int V, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   float mx = -INFINITY;
   for (int i = tid; i < V; i += 256) mx = fmaxf(mx, row[i]);
   mx = wave_max(mx);
@@ -2028,7 +2218,39 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
   sum = wave_sum(sum);
   if (lane == 0) red[4 + wv] = sum;
   __syncthreads();
-  if (tid == 0) nll[r] = logf((red[4] + red[5]) + (red[6] + red[7])) + mx - row[tgt];
+  return logf((red[4] + red[5]) + (red[6] + red[7])) + mx - row[tgt];
+}
+
+__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, long row0,
+                                                      int L, int V, float* __restrict__ nll) {
+  __shared__ float red[8];
+  const long r = row0 + blockIdx.x;
+  const int l = (int)(r % L), tid = threadIdx.x;
+  const long tgt = l + 1 < L ? labels[r + 1] : -100;
+  if (tgt < 0 || tgt >= V) { if (tid == 0) nll[r] = 0.f; return; }
+  const float v = ce_row_nll(logits + (long)blockIdx.x * V, tgt, V, red);
+  if (tid == 0) nll[r] = v;
+}
+
+// The same per row of a chunk of teacher-forced rows whose targets are given ids (ivg_kv_extend): chunk row i is row r = row0 + i of
+// [B][Tc] rows, (b, c) = (r / Tc, r % Tc); its target is ids[b][c] (ids already points at the column after the row's own token) and its
+// nll goes to out[b * out_ld + c]
+__global__ __launch_bounds__(256) void token_nll_kernel(const float* __restrict__ logits, const int64_t* __restrict__ ids, long ids_stride,
+                                                        long row0, int Tc, int V, float* __restrict__ out, long out_ld) {
+  __shared__ float red[8];
+  const long r = row0 + blockIdx.x;
+  const long b = r / Tc, c = r - b * Tc;
+  const long tgt = ids[b * ids_stride + c];
+  if (tgt < 0 || tgt >= V) { if (threadIdx.x == 0) out[b * out_ld + c] = 0.f; return; }
+  const float v = ce_row_nll(logits + (long)blockIdx.x * V, tgt, V, red);
+  if (threadIdx.x == 0) out[b * out_ld + c] = v;
+}
+
+int launch_token_nll(const float* logits, const int64_t* ids, long ids_stride, long row0, int rows, int Tc, int V, float* out, long out_ld,
+                     hipStream_t st) {
+  if (rows <= 0) return 0;
+  hipLaunchKernelGGL(token_nll_kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, ids, ids_stride, row0, Tc, V, out, out_ld);
+  return (int)hipGetLastError();
 }
 
 int launch_ce_rows(const float* logits, const int64_t* labels, long row0, int rows, int L, int V, float* nll, hipStream_t st) {

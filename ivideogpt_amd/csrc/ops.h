@@ -68,6 +68,13 @@ int launch_rope_kv(void* qkv, void* kc, void* vc, void* vt, int ldvt, const floa
 // causal prompt attention in one kernel (bf16, head_dim 64); -1 = not covered, use the score GEMM / softmax / P.V path
 int launch_flash_prefill(const void* qkv, const void* kc, const void* vt, void* out, int B, int L, int Lp, int heads, int hd, int Lmax,
                          DType dt, hipStream_t st);
+// attention of T appended tokens per trajectory (ivg_kv_extend's chunk pass; bf16, head_dim 64): query row (b, t) at position pos0 + t
+// against cache rows [0, pos0 + t], after launch_rope_kv(.., vt = null, .., pos0) appended rows [pos0, pos0 + T).  V is read row-major from
+// the cache.  -1 = not covered / does not fit / misaligned (nothing launched)
+int launch_chunk_attn(const void* qkv, const void* kc, const void* vc, void* out, int B, int T, int heads, int hd, int Lmax, int pos0,
+                      DType dt, hipStream_t st);
+void kv_extend_note(int chunk_rows, int step_rows);   // B * T of an ivg_kv_extend by route (test hook, ivg_debug_counter("kv_extend_chunk_rows" / "_step_rows"))
+long long kv_extend_rows(int stepwise);
 // tokenizer attention in one pass (bf16): cross-attention, 4 heads of 32 / 64 / 128 / 192 channels, and the single-head
 // self-attention of the conditional mid blocks (512 / 768 channels; M frames attending to themselves: F = 1, B = M); -1 = not covered
 int launch_xattn(const void* q, const void* Kp, const void* VpT, void* out, int M, int F, int P, int kv, int C, int nh, DType dt, hipStream_t st);
@@ -146,6 +153,10 @@ void token_scores_note(int launches);   // the host's count of the launches abov
 long long token_scores_launches();
 // eval heads: shifted cross-entropy per row of a logits chunk, per-trajectory (sum, count), action reconstruction squared error
 int launch_ce_rows(const float* logits, const int64_t* labels, long row0, int rows, int L, int V, float* nll, hipStream_t st);
+// ce_rows_kernel's arithmetic for rows whose targets are given ids: chunk row i = row r = row0 + i of [B][Tc] rows, target
+// ids[(r / Tc) * ids_stride + r % Tc], nll to out[(r / Tc) * out_ld + r % Tc]
+int launch_token_nll(const float* logits, const int64_t* ids, long ids_stride, long row0, int rows, int Tc, int V, float* out, long out_ld,
+                     hipStream_t st);
 int launch_ce_reduce(const float* nll, const int64_t* labels, int B, int L, int V, float* out, hipStream_t st);
 int launch_action_recon(const void* hidden, const float* W, const float* bias, const float* act, int B, int L, int H, int A, int act_T,
                         int ctx, int prelude, float* out, DType dt, hipStream_t st);

@@ -23,6 +23,8 @@
 //   IVG_GEMM256X3            1        0: large dense split-bf16 ("x3") GEMMs on the generic implicit GEMM's X3 instance (1: 256 x 256 tiles)
 //   IVG_DG3                  1        0: decode GEMMs on the second-generation kernel (dgemm.hip)
 //   IVG_FLASH_PREFILL        1        0: prompt attention as score GEMM + softmax + P.V GEMM (what the fp32 engine mode runs)
+//   IVG_KV_EXTEND_CHUNK      1        0: ivg_kv_extend appends by decode steps with given inputs on every engine (1: one chunk pass over the
+//                                        given tokens where the cache is native bf16 at head_dim 64, transformer.cpp Run::extend)
 //   IVG_FLASH_XATT           1        0: tokenizer attention as score GEMM + softmax + P.V GEMM
 //   IVG_GN_FUSE              1        0: every GroupNorm computes its own statistics (1: reduced by the producing conv3x3's epilogue)
 //   IVG_GN_APPLY_FUSE        1        0: GroupNorm + SiLU as a separate apply pass (1: inside the consuming conv3x3's halo staging)
@@ -43,7 +45,7 @@
 namespace ivg {
 
 struct Switches {
-  int conv3x3 = 1, subpixel = 1, gemm256 = 1, dg3 = 1, flash_prefill = 1, flash_xatt = 1, gn_fuse = 1, gn_apply_fuse = 1, x3 = 1, gemm256x3 = 1, kv24 = 1;
+  int conv3x3 = 1, subpixel = 1, gemm256 = 1, dg3 = 1, flash_prefill = 1, flash_xatt = 1, gn_fuse = 1, gn_apply_fuse = 1, x3 = 1, gemm256x3 = 1, kv24 = 1, kv_extend_chunk = 1;
   int graph = 0, dg3_warm = 1, warm_gate_up = 0, conv_cap = 0, decode_lds_kb = 160, decode_w_shared = 1, inflight_warm = 0, dg2_mf_cap = 0, inflight_gemm256 = 1;
   int inflight_kb[5] = {0, 0, 0, 0, 0};
   bool operator==(const Switches& o) const;

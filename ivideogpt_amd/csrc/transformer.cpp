@@ -95,7 +95,10 @@ int Run::prefill(const PrefillReq& q) {
   char* qkv = (char*)e->ws.alloc((size_t)M * 3 * H * esz(dt));
   char* attn = (char*)e->ws.alloc((size_t)M * H * esz(dt));
   char* act = (char*)e->ws.alloc((size_t)M * I * esz(dt));
-  const bool flash = flash_prefill_covers(dt, hd);   // one-pass causal attention: no score matrix in HBM
+  // q.append: the rows are positions [pos0, pos0 + L) appended to the kept cache (ivg_kv_extend's chunk pass: a native bf16 cache at
+  // head_dim 64) -- RoPE at pos0, chunk_attn_kernel against cache rows [0, pos0 + l], and the kept state is the caller's to update
+  const bool append = q.append;
+  const bool flash = append || flash_prefill_covers(dt, hd);   // one-pass causal attention: no score matrix in HBM
   float* S = flash ? nullptr : (float*)e->ws.alloc((size_t)B * heads * L * Lp * 4);
   // a cache that is not in the engine's element type (24-bit planes, FP8): the pass itself is untouched -- RoPE writes one layer's K / V
   // rows here (the score GEMM reads K as a matrix) and the cache packs them into its own rows
@@ -103,13 +106,14 @@ int Run::prefill(const PrefillReq& q) {
   char* stage_v = kvc.staged() ? (char*)e->ws.alloc(kvc.stage_bytes(B)) : nullptr;
   char* Pm = flash ? nullptr : (char*)e->ws.alloc((size_t)B * heads * L * Lp * esz(dt));
   if (!planning) {
-    e->kvc.forget_kept();   // the cache rows are about to be overwritten (ivg_generate re-validates them at its end)
+    if (!append) e->kvc.forget_kept();   // the cache rows are about to be overwritten (ivg_generate re-validates them at its end)
     if (q.embeds) CK((int)hipMemcpyAsync(x, q.embeds, (size_t)M * H * esz(dt), hipMemcpyDeviceToDevice, st));
     else CK(launch_embed(q.ids, q.ids_stride, e->embed, x, dt, B, L, H, V, st));
     if (q.act_emb) {  // action embedding on the sdf slot(s): slot i (position 257*ctx - 1 + 17*i) gets action i + ctx - 1
       for (int i = 0;; ++i) {
-        const int pos = 257 * q.ctx - 1 + 17 * i;
+        const int pos = 257 * q.ctx - 1 + 17 * i - q.pos0;   // (row of the pass)
         if (pos >= L || i + q.ctx - 1 >= q.act_T) break;
+        if (pos < 0) continue;
         CK(launch_add_rows(x + (size_t)pos * H * esz(dt), (long)L * H, (const char*)q.act_emb + (size_t)(i + q.ctx - 1) * H * esz(dt),
                            (long)q.act_T * H, B, H, dt, st));
         if (!q.all_slots) break;
@@ -123,12 +127,16 @@ int Run::prefill(const PrefillReq& q) {
     IVG_TRY(linear(dt, xn, M, wq, qkv, nullptr, 0, 0));
     char* kl = stage_k ? stage_k : kvc.ptr(l, 0);   // where this layer's roped K / V rows are in the engine's element type
     char* vl = stage_v ? stage_v : kvc.ptr(l, 1);
-    if (!planning) {
+    if (append) {   // (no V^T image: chunk_attn_kernel reads V from the cache rows)
+      if (!planning) CK(launch_rope_kv(qkv, kl, vl, nullptr, 0, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, q.pos0, dt, st));
+    } else if (!planning) {
       CK(launch_rope_kv(qkv, kl, vl, e->vt, Lp, e->rope_cos, e->rope_sin, B, L, heads, hd, Lmax, nullptr, 0, dt, st));
       if (kv_amax) CK(launch_kv_absmax(kl, vl, B, heads, L, Lmax, kv_amax + (size_t)l * 2 * heads, st));
       CK(kvc.store_staged(l, stage_k, stage_v, B, L, st));
     }
-    if (flash) {
+    if (append) {
+      if (!planning) CK(launch_chunk_attn(qkv, kl, vl, attn, B, L, heads, hd, Lmax, q.pos0, dt, st));
+    } else if (flash) {
       if (!planning) CK(launch_flash_prefill(qkv, kl, e->vt, attn, B, L, Lp, heads, hd, Lmax, dt, st));
     } else {
     {  // S[b][h] = Q K^T / sqrt(hd)
@@ -187,7 +195,9 @@ int Run::prefill(const PrefillReq& q) {
     for (long r0 = 0; r0 < M; r0 += Rc) {
       const long rows = std::min(Rc, M - r0);
       IVG_TRY(linear(dt, xn + (size_t)r0 * H * esz(dt), rows, wl, chunk, nullptr, 0, 1));
-      if (!planning) CK(launch_ce_rows(chunk, q.labels, r0, (int)rows, L, V, q.token_nll, st));
+      if (planning) continue;
+      if (q.next_ids) CK(launch_token_nll(chunk, q.next_ids, q.ids_stride, r0, (int)rows, L, V, q.token_nll, L, st));
+      else CK(launch_ce_rows(chunk, q.labels, r0, (int)rows, L, V, q.token_nll, st));
     }
   }
   if (q.logits_last && !planning) {
@@ -361,7 +371,11 @@ int Run::generate(const GenerateReq& q) {
   GenBuf g;
   gen_layout(e, g, e->gen_buf);
   const long Ltot = (long)L0 + n_new;
-  const bool shared = group > 1;
+  // fanout (ivg_generate_fanout): the shared branch with the kept cache as the groups' prefix -- one chunk (the entry checks it), group
+  // s's prefix already in cache row s, no prompt pass; the kept state is put back at the end exactly as it was
+  const bool fanout = q.fanout;
+  const bool shared = group > 1 || fanout;
+  const int kept_act_T = e->kvc.last_act_T, kept_ctx = e->kvc.last_ctx;   // (what the fan-out restores)
   g.fr_rew = q.frame_rewards_out != nullptr; g.fr_hid = q.frame_hidden_out != nullptr;
   const bool frames = g.fr_rew || g.fr_hid;
   const int F_out = n_new / 17;   // frames whose 16th token, new token 17 i + 16, is fed (<= n_new - 1)
@@ -369,7 +383,7 @@ int Run::generate(const GenerateReq& q) {
   if (planning) {   // the prompt pass of the largest chunk (shared: of the most groups a chunk's rows can belong to)
     PrefillReq p; p.ctx = ctx; p.L = shared ? L0 - 1 : L0;
     p.B = shared ? std::min((std::min(B, g.Bc) + group - 1) / group + 1, std::min(B, g.Bc)) : std::min(B, g.Bc);
-    return reuse_kv && !shared ? 0 : prefill(p);
+    return (reuse_kv && !shared) || fanout ? 0 : prefill(p);
   }
   e->kvc.forget_kept();   // kept again once every launch of this call is queued
   const size_t es = esz(dt);
@@ -393,8 +407,10 @@ int Run::generate(const GenerateReq& q) {
       // (attending the prompt rows once per 16 trajectories on the matrix cores -- tools/ubench/prefix_attn_mfma.hip -- shortens the
       // attention launch but needs a launch of its own per layer: every call measured slower, profiles/r06_shared_prefix_mfma_ab.txt)
       CK(launch_expand_prompt_rows(q.prompt, q.prompt_stride, g.ids, g.ids_ld, Bc, L0, group, b0, st));
-      PrefillReq p; p.ids = q.prompt + (long)g_lo * q.prompt_stride; p.ids_stride = q.prompt_stride; p.B = g_hi - g_lo + 1; p.L = L0 - 1; p.ctx = ctx;
-      IVG_TRY(prefill(p));
+      if (!fanout) {
+        PrefillReq p; p.ids = q.prompt + (long)g_lo * q.prompt_stride; p.ids_stride = q.prompt_stride; p.B = g_hi - g_lo + 1; p.L = L0 - 1; p.ctx = ctx;
+        IVG_TRY(prefill(p));
+      }
     } else if (!embeds)
       CK((int)hipMemcpy2DAsync(g.ids, (size_t)g.ids_ld * 8, q.prompt + (long)b0 * q.prompt_stride, (size_t)q.prompt_stride * 8, (size_t)L0 * 8, Bc,
                                hipMemcpyDeviceToDevice, st));
@@ -403,7 +419,7 @@ int Run::generate(const GenerateReq& q) {
                                hipMemcpyDeviceToDevice, st));
     if (actions) {
       CK(launch_action_embed(actions + (long)b0 * act_T * c.action_dim, e->act_w, e->act_b, g.act_emb, dt, Bc * act_T, c.action_dim, H, st));
-      if (B <= g.Bc) CK((int)hipMemcpyAsync(g.last_act, actions, (size_t)B * act_T * c.action_dim * 4, hipMemcpyDeviceToDevice, st));
+      if (B <= g.Bc && !fanout) CK((int)hipMemcpyAsync(g.last_act, actions, (size_t)B * act_T * c.action_dim * 4, hipMemcpyDeviceToDevice, st));
     }
     if (!reuse_kv && !shared) {
       PrefillReq p; p.ids = g.ids; p.ids_stride = g.ids_ld; p.B = Bc; p.L = L0; p.act_emb = actions ? g.act_emb : nullptr; p.act_T = act_T; p.ctx = ctx;
@@ -511,6 +527,13 @@ int Run::generate(const GenerateReq& q) {
   }
   // the last new token is decided but never fed (a shared-context cache is not a per-trajectory cache: never kept)
   if (B <= g.Bc && !shared) e->kvc.keep(L0 + n_new - 1, B, embeds != nullptr, actions ? act_T : 0, ctx);
+  if (fanout) {
+    // the candidates' own rows lie at positions >= L0 - 1, outside the kept state; the id rows of the kept trajectories were overwritten
+    // by the expanded prompts (rows [0, B / group) of candidates), the action table was never touched
+    const int n_groups = B / group;
+    CK((int)hipMemcpy2DAsync(g.ids, (size_t)g.ids_ld * 8, q.prompt, (size_t)q.prompt_stride * 8, (size_t)L0 * 8, n_groups, hipMemcpyDeviceToDevice, st));
+    e->kvc.keep(L0 - 1, n_groups, false, kept_act_T, kept_ctx);
+  }
   return 0;
 }
 
@@ -523,22 +546,25 @@ static int read_flag(ivg_engine* e, const GenBuf& g, hipStream_t st, bool* ok) {
   return 0;
 }
 
-int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, const float* actions, int act_T,
-                          int ctx, hipStream_t st, bool* ok) {
+// positions [0, len) of the B kept trajectories against prompt[:, :len] and the action rows of the sdf slots among them
+// (ivg_generate_continue: len = the kept length; ivg_kv_extend: any prefix of it; ids_only, ivg_generate_fanout: the kept action table
+// defined the cache rows and the candidates' rows for those slots are not looked at)
+int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int len, const float* actions, int act_T,
+                          int ctx, hipStream_t st, bool* ok, bool ids_only) {
   *ok = false;
   GenBuf g;
   gen_layout(e, g, e->gen_buf);
-  if (!e->kvc.ids_valid || !e->kvc.holds(B, L0 - 1) || B > g.Bc) return 0;
+  if (!e->kvc.ids_valid || e->kvc.B != B || len < 1 || len > e->kvc.len || B > g.Bc) return 0;
   // the cache must have been built the same way: with / without actions, the same context length, the same action-table shape;
   // whatever cannot be compared row for row is a mismatch, never a silent "ok"
   if ((actions != nullptr) != (e->kvc.last_act_T > 0)) return 0;
   if (ctx != e->kvc.last_ctx) return 0;
-  if (actions && (e->kvc.last_act_T != act_T)) return 0;
+  if (actions && !ids_only && (e->kvc.last_act_T != act_T)) return 0;
   CK((int)hipMemsetAsync(g.flag, 0, sizeof(int), st));
-  CK(launch_compare_rows(prompt, prompt_stride * 8, g.ids, (long)g.ids_ld * 8, B, (long)(L0 - 1) * 8, g.flag, st));
-  if (actions) {   // the action rows already baked into the cached sdf slots: slot i (position 257*ctx - 1 + 17*i < kv_len) used row i + ctx - 1
+  CK(launch_compare_rows(prompt, prompt_stride * 8, g.ids, (long)g.ids_ld * 8, B, (long)len * 8, g.flag, st));
+  if (actions && !ids_only) {   // the action rows already baked into the cached sdf slots: slot i (position 257*ctx - 1 + 17*i < kv_len) used row i + ctx - 1
     const int A = e->cfg.action_dim;
-    const int slots = std::max(0, (e->kvc.len - (257 * ctx - 1) + 16) / 17);
+    const int slots = std::max(0, (len - (257 * ctx - 1) + 16) / 17);
     if (slots > 0 && ctx - 1 + slots > act_T) return 0;   // the cached slots used action rows the presented table does not have
     if (slots > 0)
       CK(launch_compare_rows(actions + (long)(ctx - 1) * A, (long)act_T * A * 4, g.last_act + (long)(ctx - 1) * A, (long)act_T * A * 4, B,
@@ -559,6 +585,55 @@ int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, h
   return read_flag(e, g, st, ok);
 }
 
+// ---------------------------------------------------------------------------------------- kept-cache extension (ivg_kv_extend)
+bool kv_extend_chunk_covers(const ivg_engine* e) {
+  return sw().kv_extend_chunk && e->kvc.format == KvFormat::Native && e->llm_dt == BF16 && e->hd == 64;   // IVG_KV_EXTEND_CHUNK=0: decode steps (A/B tests)
+}
+
+// Teacher-forces positions [keep_len, L0 - 1) onto the kept cache.  chunk: one pass over the B * T rows through Run::prefill's layers
+// (append mode: RoPE at keep_len, chunk_attn_kernel).  Otherwise T eager decode steps whose input rows are given instead of sampled --
+// exactly the launches generate's own steps make after the sampler, so the appended rows are bit for bit what a rollout that had
+// sampled these tokens would have appended, in every cache format.  Neither touches a captured step graph.
+int Run::extend(const ExtendReq& q) {
+  const ivg_config& c = e->cfg;
+  const DType dt = e->llm_dt;
+  const int H = c.hidden_size, V = c.vocab_size, B = q.B, T = q.L0 - 1 - q.keep_len, A = c.action_dim;
+  const size_t es = esz(dt);
+  GenBuf g;
+  gen_layout(e, g, e->gen_buf);
+  if (!planning) e->kvc.forget_kept();   // rows from keep_len on are about to be overwritten; kept again once every launch is queued
+  if (!planning && q.actions) CK(launch_action_embed(q.actions, e->act_w, e->act_b, g.act_emb, dt, B * q.act_T, A, H, st));
+  if (q.chunk) {
+    PrefillReq p; p.ids = q.prompt + q.keep_len; p.ids_stride = q.prompt_stride; p.B = B; p.L = T; p.ctx = q.ctx;
+    p.act_emb = q.actions ? g.act_emb : nullptr; p.act_T = q.act_T; p.all_slots = true;
+    p.append = true; p.pos0 = q.keep_len;
+    if (q.token_nll) { p.token_nll = q.token_nll; p.next_ids = q.prompt + q.keep_len + 1; }
+    IVG_TRY(prefill(p));
+  } else if (!planning) {
+    g.sh_P = 0; g.sh_G = 1; g.sh_row0 = 0;
+    CK(launch_state_set(g.state, q.keep_len, 0, st));   // (every step's lm_head advances the position)
+    const SampleArgs none{};                            // the sampler never runs
+    for (int t = 0; t < T; ++t) {
+      const int pos = q.keep_len + t;
+      CK(launch_embed(q.prompt + pos, q.prompt_stride, e->embed, g.x, dt, B, 1, H, V, st));
+      const int slot = pos - (257 * q.ctx - 1);
+      if (q.actions && slot >= 0 && slot % 17 == 0)   // sdf slot i = slot / 17 carries action row i + ctx - 1
+        CK(launch_add_rows(g.x, H, g.act_emb + (size_t)(slot / 17 + q.ctx - 1) * H * es, (long)q.act_T * H, B, H, dt, st));
+      IVG_TRY(step_body(e, st, g, B, none, true, true));
+      if (q.token_nll) CK(launch_token_nll(g.logits, q.prompt + pos + 1, q.prompt_stride, 0, B, 1, V, q.token_nll + t, T, st));
+    }
+  }
+  if (planning) return 0;
+  // the kept state: id columns [keep_len, L0 - 1] and the action table are the caller's
+  // (column L0 - 1, the token given but not yet fed, has no place in a cache extended to its last position)
+  CK((int)hipMemcpy2DAsync(g.ids + q.keep_len, (size_t)g.ids_ld * 8, q.prompt + q.keep_len, (size_t)q.prompt_stride * 8,
+                           (size_t)(std::min(q.L0, g.ids_ld) - q.keep_len) * 8, B, hipMemcpyDeviceToDevice, st));
+  if (q.actions) CK((int)hipMemcpyAsync(g.last_act, q.actions, (size_t)B * q.act_T * A * 4, hipMemcpyDeviceToDevice, st));
+  e->kvc.keep(q.L0 - 1, B, false, q.actions ? q.act_T : 0, q.ctx);
+  kv_extend_note(q.chunk ? B * T : 0, q.chunk ? 0 : B * T);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------- kept-cache row selection (ivg_kv_select)
 // the buffers whose rows belong to the kept trajectories: the K / V slabs in the cache's own format, and what the verification above
 // compares a caller's "same prefix" claim with -- the id rows, the action table, the embeddings snapshot
@@ -572,7 +647,7 @@ static void kv_select_bufs(const ivg_engine* e, const GenBuf& g, std::vector<KvS
   else c.bytes_a = (long)k.len * k.hd * eb;
   out.push_back(c);
   KvSelectBuf ids;
-  ids.base = (char*)g.ids; ids.row_stride = (long)g.ids_ld * 8; ids.bytes_a = (long)(k.len + 1) * 8; ids.vec = 4;   // (column len: decided, not yet fed)
+  ids.base = (char*)g.ids; ids.row_stride = (long)g.ids_ld * 8; ids.bytes_a = (long)std::min(k.len + 1, g.ids_ld) * 8; ids.vec = 4;   // (column len: decided, not yet fed)
   out.push_back(ids);
   if (k.last_act_T > 0) {
     KvSelectBuf a;

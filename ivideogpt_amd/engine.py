@@ -251,6 +251,33 @@ class Engine:
             self.check(self.lib.ivg_kv_select(self.h, p.ctypes.data_as(C.c_void_p), int(p.size), s), "kv_select")
         return self
 
+    def kv_extend(self, prompt, keep_len, actions=None, ctx=1, token_nll=None):
+        """``ivg_kv_extend``: positions [keep_len, L0 - 1) of ``prompt`` (B, L0) teacher-forced onto the kept K / V cache (``keep_len`` ==
+        L0 - 1: a rewind); ``token_nll`` (B, L0 - 1 - keep_len) float32 receives the model's surprise at each given token."""
+        B, L0 = prompt.shape
+        act_T = actions.shape[1] if actions is not None else 0
+        with self.stream() as s:
+            self.check(self.lib.ivg_kv_extend(self.h, _ptr(prompt), prompt.stride(0), B, int(keep_len), L0, _ptr(actions), act_T, int(ctx),
+                                              _ptr(token_nll), s), "kv_extend")
+            for t in (prompt, actions, token_nll):
+                if t is not None:
+                    t.record_stream(self._run)
+        return self
+
+    def generate_fanout(self, prompt, group_size, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, force_sdf=False, frame_rewards=None,
+                        frame_hidden=None, token_scores=None):
+        """``ivg_generate_fanout``: ``generate_scored`` with ``group_size`` candidates per row of ``prompt`` (n_groups, L0) whose shared
+        prefix is the kept K / V cache (no prompt pass; the kept cache is left as it was).  Rows of everything else: group-major."""
+        n_groups, L0 = prompt.shape
+        act_T = actions.shape[1] if actions is not None else 0
+        with self.stream() as s:
+            self.check(self.lib.ivg_generate_fanout(self.h, _ptr(prompt), prompt.stride(0), n_groups, int(group_size), L0, int(n_new), _ptr(actions),
+                                                    act_T, int(ctx), _ptr(uniforms), int(top_k), int(bool(force_sdf)), _ptr(out), _ptr(frame_rewards),
+                                                    _ptr(frame_hidden), _ptr(token_scores), s), "generate_fanout")
+            for t in (prompt, out, actions, uniforms, frame_rewards, frame_hidden, token_scores):
+                if t is not None:
+                    t.record_stream(self._run)
+
     def generate(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, reward=None, reuse_kv=False):
         B, L0 = prompt.shape
         act_T = actions.shape[1] if actions is not None else 0

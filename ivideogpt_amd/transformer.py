@@ -475,6 +475,99 @@ class LlamaForCausalLM:
             raise ValueError(f"select_kept_cache: {err}") from None
         return self
 
+    def extend_kept_cache(self, input_ids, keep, return_nll=False, _actions=None, _ctx=1):
+        """Appends GIVEN tokens to the KV cache the last ``generate`` call kept (include/ivg.h ivg_kv_extend): afterwards it holds
+        ``input_ids[:, :-1]``, of which positions [0, keep) are the kept rows as they were (verified on the device) and [keep, L0 - 1)
+        are teacher-forced by this call -- a following ``generate`` on the kept cache (``HeadModelWithAction.generate(reuse_cache=True)``),
+        ``select_kept_cache``, ``fan_out`` or another extend then accepts ``input_ids``.  ``keep == L0 - 1`` only rewinds the cache to
+        that length.  ``return_nll=True``: -> float32 (B, L0 - 1 - keep), ``-log p(input_ids[:, p + 1] | input_ids[:, :p + 1])`` for
+        p = keep .. L0 - 2, the model's surprise at each given token; else None.  ValueError, with the kept cache untouched, where the
+        engine refuses: no kept cache built from ids, another batch, ``keep`` outside [1, min(kept length, L0 - 1)], other tokens."""
+        if self._engine is None:
+            raise ValueError("extend_kept_cache: no kept cache (the model has not generated yet)")
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        B, L0 = ids.shape
+        T = L0 - 1 - int(keep)
+        nll = torch.empty(B, T, dtype=torch.float32, device=self.device) if return_nll and T > 0 else None
+        try:
+            self._engine.kv_extend(ids, keep, actions=_actions, ctx=_ctx, token_nll=nll)
+        except (AssertionError, _lib.IvgError) as err:
+            raise ValueError(f"extend_kept_cache: {err}") from None
+        if return_nll:
+            return nll if nll is not None else torch.empty(B, 0, dtype=torch.float32, device=self.device)
+        return None
+
+    def _fan_out(self, ids, samples, act, ctx, gk, force_sdf=False):
+        """``fan_out`` of both classes: ``ivg_generate_fanout`` under ``generate``'s keywords.  Rows b * samples + k throughout (the
+        engine's group-major order is the public one here)."""
+        known = {"do_sample", "temperature", "top_k", "max_new_tokens", "pad_token_id", "generator", "uniforms", "top_p", "output_token_scores",
+                 "return_reward", "output_frame_hidden_states"}
+        if set(gk) - known:
+            raise TypeError(f"fan_out: unexpected keyword(s) {sorted(set(gk) - known)}")
+        do_sample, temperature, top_k = gk.get("do_sample", True), gk.get("temperature", 1.0), gk.get("top_k", 100)
+        n, rr, want_h, want_s = gk.get("max_new_tokens"), gk.get("return_reward", False), gk.get("output_frame_hidden_states", False), \
+            gk.get("output_token_scores", False)
+        if not (isinstance(temperature, (int, float)) and temperature > 0):
+            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        top_p = _top_p_of(gk.get("top_p"), do_sample)
+        if not (isinstance(samples, int) and samples >= 1):
+            raise ValueError(f"fan_out: samples must be a positive integer, not {samples!r}")
+        if rr not in (False, "frames"):
+            raise ValueError("fan_out: return_reward must be False or 'frames' (candidates are ranked frame by frame)")
+        if rr == "frames" and not self._reward:
+            raise ValueError("return_reward='frames' needs a model with reward_prediction=True")
+        frames = rr == "frames" or want_h
+        F = _frames_of(n) if frames else 0
+        n_new = n + 1 if frames else n   # (as generate: one token more, the forced sdf that feeds the last frame's 16th token)
+        eng = self._engine
+        B0, L0 = ids.shape
+        B = B0 * samples
+        if eng is None:
+            raise ValueError("fan_out: no kept cache (the model has not generated yet)")
+        if B > eng.max_batch:
+            raise ValueError(f"fan_out: {B} candidates exceed the batch the engine was built for ({eng.max_batch}); run the model once at that batch first")
+        u = gk.get("uniforms")
+        if u is None:
+            u = self._uniforms(B, n, do_sample, gk.get("generator"))
+        if u is not None:
+            u = u.to(device=self.device, dtype=torch.float32)
+            if u.shape[1] < n_new:
+                u = torch.cat([u, u.new_zeros(B, n_new - u.shape[1])], 1)
+            u = u[:, :n_new].contiguous()
+        if act is not None and frames:
+            need = (L0 - 257 * ctx) // 17 + n_new // 17 + ctx
+            if act.shape[1] < need:
+                act = torch.cat([act, act.new_zeros(B, need - act.shape[1], act.shape[2])], 1)
+        out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=self.device)
+        fr = torch.empty(B, F, dtype=torch.float32, device=self.device) if rr == "frames" else None
+        fh = torch.empty(B, F, self._cfg["hidden_size"], dtype=self.torch_dtype, device=self.device) if want_h else None
+        ts = _token_scores_buffer(B, n_new, self.device) if want_s else None
+        eng.set_temperature(temperature).set_top_p(top_p)
+        try:
+            eng.generate_fanout(ids, samples, n_new, out, actions=act, ctx=ctx, uniforms=u, top_k=top_k or self._cfg["vocab_size"],
+                                force_sdf=act is None and (frames or force_sdf), frame_rewards=fr, frame_hidden=fh, token_scores=ts)
+        except (AssertionError, _lib.IvgError) as err:
+            raise ValueError(f"fan_out: {err}") from None
+        res = (out[:, :L0 + n].contiguous() if frames else out,)
+        if fr is not None:
+            res += (fr,)
+        if fh is not None:
+            res += (fh,)
+        if want_s:
+            res += (_token_scores_of(ts, n=n),)
+        return res if len(res) > 1 else res[0]
+
+    @torch.no_grad()
+    def fan_out(self, input_ids, samples, **generate_kwargs):
+        """``samples`` candidate continuations of every row of the kept KV cache (include/ivg.h ivg_generate_fanout): ``input_ids``
+        (B, L0) is what the kept cache was built from plus the token to feed next, and row ``b * samples + k`` of every result is
+        candidate k of row b.  No prompt pass: the candidates read the kept rows in place, and the kept cache is afterwards exactly
+        what it was -- fan out again, continue, or ``extend_kept_cache``.  ``generate``'s keywords (``do_sample``, ``temperature``,
+        ``top_k``, ``top_p``, ``max_new_tokens``, ``uniforms`` (B * samples, n), ``generator``, ``output_token_scores``); results as
+        ``generate``'s.  ValueError where the engine refuses (no such kept cache, more candidates than the engine holds)."""
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        return self._fan_out(ids, samples, None, 1, generate_kwargs)
+
     # ------------------------------------------------------------------ hot path
     def _uniforms(self, B, n, do_sample, generator):
         if not do_sample:
@@ -691,6 +784,26 @@ class HeadModelWithAction:
         ``parents``; continue with ``reuse_cache=True`` on ``inputs_token[parents]`` and ``action[parents]``."""
         self.llm.select_kept_cache(parents)
         return self
+
+    def extend_kept_cache(self, inputs_token, action=None, keep=None, return_nll=False):
+        """``LlamaForCausalLM.extend_kept_cache`` with ``action_linear(action[:, i + context - 1])`` added on the i-th sdf slot among
+        the appended positions, as ``generate`` does; ``action`` (B, T, D) becomes the kept action table, and its rows of the slots
+        before ``keep`` must equal the kept ones.  ``keep`` is required.  Continue with ``generate(inputs_token, action=action,
+        reuse_cache=True)``."""
+        if keep is None:
+            raise ValueError("extend_kept_cache: keep (the number of kept positions to keep) is required")
+        act = action.to(device=self.llm.device, dtype=torch.float32).contiguous() if action is not None else None
+        return self.llm.extend_kept_cache(inputs_token, keep, return_nll=return_nll, _actions=act, _ctx=self.context)
+
+    @torch.no_grad()
+    def fan_out(self, inputs_token, samples, action=None, **generate_kwargs):
+        """``LlamaForCausalLM.fan_out`` under this wrapper's forced-sdf schedule: ``action`` (B * samples, T, D), one table per
+        candidate in row order ``b * samples + k`` (``rollout_actions``' order); its rows of sdf slots already in the kept cache are
+        not looked at.  Also takes ``return_reward="frames"`` and ``output_frame_hidden_states``, as ``generate``."""
+        llm = self.llm
+        ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
+        act = action.to(device=llm.device, dtype=torch.float32).contiguous() if action is not None else None
+        return llm._fan_out(ids, samples, act, self.context, generate_kwargs, force_sdf=True)   # (without actions: generate_without_action's schedule)
 
     def calibrate_kv_cache(self, input_ids, action=None, headroom=1, reset=True):
         """``LlamaForCausalLM.calibrate_kv_cache`` with the action embeddings added on every sdf slot (as ``logits``) at this wrapper's
