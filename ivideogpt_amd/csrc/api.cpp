@@ -650,13 +650,68 @@ static int check_generate(ivg_engine* e, GenEntry entry, const char* own_err, in
   return 0;
 }
 
+// What an id-prompt entry adds to the checks they all share (generate_checked tries them in the order of the fields)
+struct GenRules {
+  GenEntry kind = GEN_PLAIN; const char* own_err = nullptr;   // check_generate's entry kind and the entry's own argument error
+  bool need_frames = false;        // ivg_generate_frames' conditions on the schedule and the lengths
+  bool kept = false;               // the prefix [0, L0 - 1) is the kept cache of the same B trajectories (ivg_generate_continue) ...
+  bool fanout = false;             // ... or of the B / group trajectories the candidates fan out of (ivg_generate_fanout)
+};
+
+static GenerateReq id_request(const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T, int ctx,
+                              const float* uniforms, int top_k, int64_t* ids_out) {
+  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
+  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out;
+  return q;
+}
+
+static int run_generate(ivg_engine* e, const GenerateReq& q, ivg_stream stream) {
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+}
+
+// Every id-prompt entry: the checks in the order they have always been tried, then the rollout
+static int generate_checked(ivg_engine* e, const GenerateReq& q, const GenRules& r, ivg_stream stream) {
+  const int B = q.B, L0 = q.L0;
+  IVG_TRY(check_generate(e, r.kind, r.own_err, B, L0, q.n_new, q.actions, q.act_T, q.ctx));
+  if (r.need_frames && q.n_new < 17) return e->fail(IVG_ERR_INVALID, "generate_frames: a frame needs 17 new tokens (its 16th must be fed)");
+  if (r.need_frames && (q.ctx < 1 || L0 < 257 * q.ctx || (L0 - 257 * q.ctx) % 17 != 0))
+    return e->fail(IVG_ERR_INVALID, "generate_frames: the prompt must hold 257*ctx + 17*t tokens (frames count from the first new token)");
+  if (q.frame_rewards_out && !e->rew_w) return e->fail(IVG_ERR_MISSING, "generate_frames: rewards requested but reward_linear is not loaded");
+  if (q.frame_hidden_out && !e->final_norm) return e->fail(IVG_ERR_MISSING, "generate_frames: hidden states requested but 'llm.norm' is not in the weight table");
+  if (r.kept) {
+    if (!e->kvc.holds(B, L0 - 1))
+      return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
+                                          " trajectories, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(B));
+    // same (batch, length) is not enough: another caller may have used the model in between.  Compare the cached prefix
+    // (token ids + the action rows baked into its sdf slots) with the prompt on the device (one stream synchronisation).
+    bool same = false;
+    IVG_TRY(kv_prefix_matches_ids(e, q.prompt, q.prompt_stride, B, L0 - 1, q.actions, q.act_T, q.ctx, (hipStream_t)stream, &same));
+    if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
+  }
+  if (r.fanout) {
+    const int n_groups = B / q.group;
+    if (B > e->kvc.chunk)
+      return e->fail(IVG_ERR_CAPACITY, "generate_fanout: " + std::to_string(B) + " candidates exceed the KV-cache chunk (" + std::to_string(e->kvc.chunk) + ")");
+    if (!e->kvc.ids_valid || !e->kvc.holds(n_groups, L0 - 1))
+      return e->fail(IVG_ERR_INVALID, "generate_fanout: the kept KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
+                                          " trajectories built from ids, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(n_groups));
+    bool same = false;
+    IVG_TRY(kv_prefix_matches_ids(e, q.prompt, q.prompt_stride, n_groups, L0 - 1, q.actions, q.act_T, q.ctx, (hipStream_t)stream, &same, true));
+    if (!same) return e->fail(IVG_ERR_INVALID, "generate_fanout: the kept KV cache was built from a different prefix (tokens, context length or action conditioning differ)");
+  }
+  return run_generate(e, q, stream);
+}
+
+static const char* continue_err(const ivg_engine* e, const float* actions) {
+  return actions && e->cfg.action_dim > 0 && e->act_w ? nullptr : "generate_continue: action-conditioned models only";
+}
+
 int ivg_generate(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
                  int ctx, const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  IVG_TRY(check_generate(e, GEN_PLAIN, nullptr, B, L0, n_new, actions, act_T, ctx));
-  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
-  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out;
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+  GenerateReq q = id_request(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
+  q.reward_out = reward_out;
+  return generate_checked(e, q, GenRules(), stream);
 }
 
 int ivg_generate_shared(ivg_engine* e, const int64_t* prompts, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
@@ -664,40 +719,28 @@ int ivg_generate_shared(ivg_engine* e, const int64_t* prompts, int64_t prompt_st
                         ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   const bool sized = n_groups > 0 && group_size > 0;
-  const int B = sized ? n_groups * group_size : 1;
-  IVG_TRY(check_generate(e, GEN_SHARED, sized ? nullptr : "generate_shared: n_groups and group_size must be positive", B, L0, n_new, actions, act_T, ctx));
-  GenerateReq q; q.prompt = prompts; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
-  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out; q.force_sdf = force_sdf != 0;
+  GenerateReq q = id_request(prompts, prompt_stride, sized ? n_groups * group_size : 1, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
+  q.reward_out = reward_out; q.force_sdf = force_sdf != 0;
   q.group = group_size;   // 1: nothing to share -- the plain entry (one prefill over all rows)
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+  GenRules r; r.kind = GEN_SHARED; r.own_err = sized ? nullptr : "generate_shared: n_groups and group_size must be positive";
+  return generate_checked(e, q, r, stream);
 }
 
 int ivg_generate_forced_sdf(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, int ctx, const float* uniforms,
                             int top_k, int64_t* ids_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  IVG_TRY(check_generate(e, GEN_PLAIN, nullptr, B, L0, n_new, nullptr, 0, ctx));
-  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.ctx = ctx;
-  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = true;
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+  GenerateReq q = id_request(prompt, prompt_stride, B, L0, n_new, nullptr, 0, ctx, uniforms, top_k, ids_out);
+  q.force_sdf = true;
+  return generate_checked(e, q, GenRules(), stream);
 }
 
 int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions,
                           int act_T, int ctx, const float* uniforms, int top_k, int64_t* ids_out, float* reward_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  const bool act_ok = actions && e->cfg.action_dim > 0 && e->act_w;
-  IVG_TRY(check_generate(e, GEN_CONTINUE, act_ok ? nullptr : "generate_continue: action-conditioned models only", B, L0, n_new, actions, act_T, ctx));
-  if (!e->kvc.holds(B, L0 - 1))
-    return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
-                                        " trajectories, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(B));
-  {  // same (batch, length) is not enough: another caller may have used the model in between.  Compare the cached prefix
-     // (token ids + the action rows baked into its sdf slots) with the prompt on the device (one stream synchronisation).
-    bool same = false;
-    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0 - 1, actions, act_T, ctx, (hipStream_t)stream, &same));
-    if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
-  }
-  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
-  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.reward_out = reward_out; q.reuse_kv = true;
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+  GenerateReq q = id_request(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
+  q.reward_out = reward_out; q.reuse_kv = true;
+  GenRules r; r.kind = GEN_CONTINUE; r.own_err = continue_err(e, actions); r.kept = true;
+  return generate_checked(e, q, r, stream);
 }
 
 int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream stream) {
@@ -712,8 +755,7 @@ int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, i
   if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "kv_extend: engine was created without a transformer");
   const KvCache& k = e->kvc;
   if (!prompt) return e->fail(IVG_ERR_INVALID, "kv_extend: null prompt");
-  if (k.len <= 0 || k.B <= 0 || !(k.ids_valid || k.snap_valid))
-    return e->fail(IVG_ERR_INVALID, "kv_extend: the engine holds no kept cache (the last call was not a per-trajectory generate within the cache chunk, or the format or scales changed since)");
+  IVG_TRY(need_kept_cache(e, "kv_extend"));
   if (!k.ids_valid) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache was built from input embeddings (only caches built from ids are extended)");
   if (L0 - 1 > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "kv_extend: " + std::to_string(L0 - 1) + " positions exceed the KV cache (" + std::to_string(e->Lmax) + ")");
   if (B != k.B) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache holds " + std::to_string(k.B) + " trajectories, the call presents " + std::to_string(B));
@@ -737,74 +779,49 @@ int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, i
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.extend(q); });
 }
 
-// ivg_generate_frames (need_frames: its conditions on the schedule and the lengths always hold) and ivg_generate_scored (they hold only
-// when a frame output is asked for: without one the entry also stands for the action-free ivg_generate)
-static int generate_frames_scored(ivg_engine* e, bool need_frames, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new,
-                                  const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int group_size, int kept_cache,
-                                  int force_sdf, int64_t* ids_out, float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out,
-                                  ivg_stream stream, bool fanout = false) {
-  if (!e) return IVG_ERR_INVALID;
-  // fanout (ivg_generate_fanout): B = n_groups * group_size candidates whose groups' prefixes are the kept cache's rows -- the lengths
-  // and the action table are checked as for a kept-cache call (the prompt may hold generated frames), the rows as for a shared one
+// ivg_generate_frames, ivg_generate_scored and ivg_generate_fanout each stand for several rollouts: which one, from group_size / kept_cache /
+// fanout.  need_frames: always for ivg_generate_frames, for the others only when a frame output is asked for (without one
+// ivg_generate_scored also stands for the action-free ivg_generate).  fanout: B = n_groups * group_size candidates whose groups' prefixes
+// are the kept cache's rows -- lengths and action table checked as for a kept-cache call (the prompt may hold generated frames)
+static GenRules frames_rules(const ivg_engine* e, GenerateReq& q, bool need_frames, int group_size, int kept_cache, int force_sdf, bool fanout) {
+  const int B = q.B;
   const bool shared = group_size > 1 && !fanout, cont = kept_cache != 0;
-  const char* own = nullptr;
-  if (group_size < 1 || (shared && (B <= 0 || B % group_size != 0))) own = "generate_frames: B must be a positive multiple of a positive group_size";
-  else if (fanout && (group_size < 1 || B <= 0 || B % group_size != 0)) own = "generate_fanout: n_groups and group_size must be positive";
-  else if (cont && shared) own = "generate_frames: a kept cache is per trajectory (group_size must be 1)";
-  else if (need_frames && !actions && !force_sdf) own = "generate_frames: frames exist under the forced-sdf schedule only (actions or force_sdf)";
-  else if (cont && !(actions && e->cfg.action_dim > 0 && e->act_w)) own = "generate_continue: action-conditioned models only";
-  IVG_TRY(check_generate(e, shared ? GEN_SHARED : (cont || fanout) ? GEN_CONTINUE : GEN_PLAIN, own, B, L0, n_new, actions, act_T, ctx));
-  if (need_frames && n_new < 17) return e->fail(IVG_ERR_INVALID, "generate_frames: a frame needs 17 new tokens (its 16th must be fed)");
-  if (need_frames && (ctx < 1 || L0 < 257 * ctx || (L0 - 257 * ctx) % 17 != 0))
-    return e->fail(IVG_ERR_INVALID, "generate_frames: the prompt must hold 257*ctx + 17*t tokens (frames count from the first new token)");
-  if (frame_rewards_out && !e->rew_w) return e->fail(IVG_ERR_MISSING, "generate_frames: rewards requested but reward_linear is not loaded");
-  if (frame_hidden_out && !e->final_norm) return e->fail(IVG_ERR_MISSING, "generate_frames: hidden states requested but 'llm.norm' is not in the weight table");
-  if (cont) {   // as ivg_generate_continue
-    if (!e->kvc.holds(B, L0 - 1))
-      return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
-                                          " trajectories, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(B));
-    bool same = false;
-    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, L0 - 1, actions, act_T, ctx, (hipStream_t)stream, &same));
-    if (!same) return e->fail(IVG_ERR_INVALID, "generate_continue: the KV cache was built from a different prefix (tokens or actions differ)");
-  }
-  if (fanout) {
-    const int n_groups = B / group_size;
-    if (B > e->kvc.chunk)
-      return e->fail(IVG_ERR_CAPACITY, "generate_fanout: " + std::to_string(B) + " candidates exceed the KV-cache chunk (" + std::to_string(e->kvc.chunk) + ")");
-    if (!e->kvc.ids_valid || !e->kvc.holds(n_groups, L0 - 1))
-      return e->fail(IVG_ERR_INVALID, "generate_fanout: the kept KV cache holds " + std::to_string(e->kvc.len) + " positions of " + std::to_string(e->kvc.B) +
-                                          " trajectories built from ids, the call needs " + std::to_string(L0 - 1) + " of " + std::to_string(n_groups));
-    bool same = false;
-    IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, n_groups, L0 - 1, actions, act_T, ctx, (hipStream_t)stream, &same, true));
-    if (!same) return e->fail(IVG_ERR_INVALID, "generate_fanout: the kept KV cache was built from a different prefix (tokens, context length or action conditioning differ)");
-  }
-  GenerateReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.L0 = L0; q.n_new = n_new; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
-  q.uniforms = uniforms; q.top_k = top_k; q.ids_out = ids_out; q.force_sdf = force_sdf != 0; q.group = group_size; q.reuse_kv = cont; q.fanout = fanout;
-  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+  q.force_sdf = force_sdf != 0; q.group = group_size; q.reuse_kv = cont; q.fanout = fanout;
+  GenRules r; r.kind = shared ? GEN_SHARED : (cont || fanout) ? GEN_CONTINUE : GEN_PLAIN; r.need_frames = need_frames; r.kept = cont; r.fanout = fanout;
+  if (group_size < 1 || (shared && (B <= 0 || B % group_size != 0))) r.own_err = "generate_frames: B must be a positive multiple of a positive group_size";
+  else if (fanout && (B <= 0 || B % group_size != 0)) r.own_err = "generate_fanout: n_groups and group_size must be positive";
+  else if (cont && shared) r.own_err = "generate_frames: a kept cache is per trajectory (group_size must be 1)";
+  else if (need_frames && !q.actions && !force_sdf) r.own_err = "generate_frames: frames exist under the forced-sdf schedule only (actions or force_sdf)";
+  else if (cont) r.own_err = continue_err(e, q.actions);
+  return r;
 }
 
 int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
                         int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
                         float* frame_rewards_out, void* frame_hidden_out, ivg_stream stream) {
-  return generate_frames_scored(e, true, prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, group_size, kept_cache, force_sdf,
-                                ids_out, frame_rewards_out, frame_hidden_out, nullptr, stream);
+  if (!e) return IVG_ERR_INVALID;
+  GenerateReq q = id_request(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
+  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out;
+  return generate_checked(e, q, frames_rules(e, q, true, group_size, kept_cache, force_sdf, false), stream);
 }
 
 int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
                         int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
                         float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
-  return generate_frames_scored(e, frame_rewards_out || frame_hidden_out, prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k,
-                                group_size, kept_cache, force_sdf, ids_out, frame_rewards_out, frame_hidden_out, token_scores_out, stream);
+  if (!e) return IVG_ERR_INVALID;
+  GenerateReq q = id_request(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
+  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
+  return generate_checked(e, q, frames_rules(e, q, frame_rewards_out || frame_hidden_out, group_size, kept_cache, force_sdf, false), stream);
 }
 
 int ivg_generate_fanout(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
                         const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out,
                         float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
   const bool sized = n_groups > 0 && group_size > 0 && (long)n_groups * group_size <= INT32_MAX;
-  return generate_frames_scored(e, frame_rewards_out || frame_hidden_out, prompt, prompt_stride, sized ? n_groups * group_size : 0, L0, n_new, actions, act_T,
-                                ctx, uniforms, top_k, sized ? group_size : 0, 0, force_sdf, ids_out, frame_rewards_out, frame_hidden_out, token_scores_out,
-                                stream, true);
+  GenerateReq q = id_request(prompt, prompt_stride, sized ? n_groups * group_size : 0, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
+  q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
+  return generate_checked(e, q, frames_rules(e, q, frame_rewards_out || frame_hidden_out, sized ? group_size : 0, 0, force_sdf, true), stream);
 }
 
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
@@ -822,7 +839,7 @@ int ivg_generate_embeds_scored(ivg_engine* e, const void* embeds, int B, int L0,
   if (reused_out) *reused_out = reuse ? 1 : 0;
   GenerateReq q; q.B = B; q.L0 = L0; q.n_new = n_new; q.uniforms = uniforms; q.top_k = top_k;
   q.reuse_kv = reuse; q.embeds = embeds; q.new_ids_out = new_ids_out; q.hidden_out = hidden_out; q.token_scores_out = token_scores_out;
-  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.generate(q); });
+  return run_generate(e, q, stream);
 }
 
 int ivg_embed_tokens(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, void* out, ivg_stream stream) {

@@ -110,6 +110,7 @@ int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
                           int ctx, hipStream_t st, bool* ok, bool ids_only = false);
 bool kv_extend_chunk_covers(const ivg_engine* e);   // ivg_kv_extend takes the chunk pass on this engine (format, element type, head dim, switch)
 int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, hipStream_t st, bool* ok);
+int need_kept_cache(ivg_engine* e, const char* entry);   // 0, or the refusal of an entry that works on a kept cache where the engine holds none
 // ivg_kv_select: the kept cache's rows, and everything the verification above compares them with, gathered by `parents`
 int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st);
 size_t kv_select_scratch_bytes(const ivg_engine* e);   // workspace that stages one slab of any buffer ivg_kv_select gathers, all rows staged

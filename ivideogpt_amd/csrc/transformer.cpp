@@ -31,17 +31,21 @@ struct GenBuf {  // persistent decode-step buffers (fixed addresses so the captu
   int64_t* ids; float* uni; char* act_emb; int Bc, ids_ld;
   float* last_act;   // [Bc][max_frames][action_dim]: the action table of the call that built the kept KV cache
   int* flag;         // mismatch counter of the prefix verification
-  // shared-context rollout (ivg_generate_shared; set per chunk by Run::generate): rows of the chunk in groups of sh_G sharing the cache
-  // rows of their prompt -- see decode_attn_kernel SHARED.  sh_G = 1: off
-  int sh_P = 0, sh_G = 1, sh_row0 = 0;
   // per-frame heads (ivg_generate_frames): [Bc][F_max] rewards and [Bc][F_max][H] post-norm hidden rows, written by frame_heads_kernel
-  // inside the steps and copied to the caller per chunk, like ids.  fr_rew / fr_hid: which of them this call's steps write
+  // inside the steps and copied to the caller per chunk, like ids
   float* frame_rew; char* frame_hid; int F_max;
-  bool fr_rew = false, fr_hid = false;
   // token scores (ivg_generate_scored): [Bc][ids_ld][3] floats, column j - 1 written by token_scores_kernel right after the sampler
-  // decided new token j; copied to the caller per chunk.  scored: this call's steps carry that kernel
+  // decided new token j; copied to the caller per chunk
   float* tok_scores;
-  bool scored = false;
+};
+
+// What the decode steps of one chunk of a call do beyond the fixed sequence (step_key names every field)
+struct StepOpts {
+  // shared-context rollout (ivg_generate_shared, ivg_generate_fanout): rows of the chunk in groups of sh_G sharing the cache rows
+  // [0, sh_P) of their prompt -- see decode_attn_kernel SHARED.  sh_P = 0: off
+  int sh_P = 0, sh_G = 1, sh_row0 = 0;
+  bool fr_rew = false, fr_hid = false;   // the steps carry frame_heads_kernel, writing GenBuf::frame_rew / frame_hid
+  bool scored = false;                   // the steps carry token_scores_kernel
 };
 
 static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base = null: only the size
@@ -73,6 +77,12 @@ static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base
 size_t gen_buffer_bytes(const ivg_engine* e) {
   GenBuf g;
   return gen_layout(e, g, nullptr);
+}
+
+static GenBuf gen_buf(const ivg_engine* e) {   // the layout over the engine's buffer
+  GenBuf g;
+  gen_layout(e, g, e->gen_buf);
+  return g;
 }
 
 // -------------------------------------------------------------------------------------------- prefill
@@ -219,7 +229,7 @@ int Run::prefill(const PrefillReq& q) {
 // logits for token j+1, advance the device-side state.
 // (Splitting the rows into several concurrent chains on side streams was measured twice -- rounds 2 and 3, also on CU-masked
 // streams -- without gain: every launch is bound by what one CU ingests, half-batch GEMMs cost what full-batch ones do.  Removed.)
-static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, const SampleArgs& sa, bool forward, bool skip_sample = false) {
+static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, const StepOpts& o, int B, const SampleArgs& sa, bool forward, bool skip_sample = false) {
   const ivg_config& c = e->cfg;
   const DType dt = e->llm_dt;
   const int H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size;
@@ -228,7 +238,7 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
   char* x = g.x; char* qkv = g.qkv; char* attn = g.attn; char* act = g.act; float* logits = g.logits;
   if (!skip_sample) CK(launch_sample_embed(sa, B, dt, st));   // skip: x already holds the input row (embeds path, kept KV cache)
   // token scores: the row the sampler just read is still whole (this step's lm_head overwrites it), the id it stored is in the id row
-  if (!skip_sample && g.scored)
+  if (!skip_sample && o.scored)
     CK(launch_token_scores(sa.logits, V, state, sa.ids_out, sa.ids_stride, sa.L0, sa.forced_period, g.tok_scores, g.ids_ld, B, st));
   if (!forward) return 0;
   // 5 launches per layer: RMSNorms are fused into the consuming GEMMs (weights pre-multiplied by the norm weight,
@@ -292,7 +302,7 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
     gprof(cur[0], 4 * l + 0);
     CK(launch_skinny(cur[0], dt, st));
     unsigned long long* aprof = e->attn_prof_on ? e->attn_prof + (size_t)l * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax : nullptr;
-    CK(e->kvc.decode_attn(l, qkv, attn, e->rope_cos, e->rope_sin, B, state, aprof, st, g.sh_P, g.sh_G, g.sh_row0));
+    CK(e->kvc.decode_attn(l, qkv, attn, e->rope_cos, e->rope_sin, B, state, aprof, st, o.sh_P, o.sh_G, o.sh_row0));
     gprof(cur[1], 4 * l + 1);
     CK(launch_skinny(cur[1], dt, st));
     gprof(cur[2], 4 * l + 2);
@@ -308,12 +318,36 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, int B, cons
   }
   // per-frame heads: x is final here (the last down-projection is done, the next sampler has not run) and the state still names the
   // token this step fed (lm_head advances it)
-  if (g.fr_rew || g.fr_hid)
-    CK(launch_frame_heads(x, state, e->rew_w, e->rew_b, e->final_norm, g.fr_rew ? g.frame_rew : nullptr, g.fr_hid ? g.frame_hid : nullptr, B, H,
+  if (o.fr_rew || o.fr_hid)
+    CK(launch_frame_heads(x, state, e->rew_w, e->rew_b, e->final_norm, o.fr_rew ? g.frame_rew : nullptr, o.fr_hid ? g.frame_hid : nullptr, B, H,
                           g.F_max, c.rms_norm_eps, dt, st));
   gprof(lm, 4 * c.num_layers);
   CK(launch_skinny(lm, dt, st));
   return 0;
+}
+
+// The key of a captured step graph: everything step_body bakes into the launches of a step, so that a replay is the step the call would
+// have launched.  A step feature that changes what step_body launches or passes by value adds its component HERE.
+static std::string step_key(const ivg_engine* e, const StepOpts& o, const SampleArgs& sa, int B) {
+  uint32_t t_bits; memcpy(&t_bits, &sa.temperature, 4);   // (by their BIT PATTERNS: to_string keeps six decimals)
+  uint32_t p_bits; memcpy(&p_bits, &sa.top_p, 4);
+  std::string k = std::to_string(B);                        // the rows of every launch
+  k += ":" + std::to_string(t_bits);                        // sampler: logits / temperature
+  k += ":" + std::to_string(p_bits);                        // sampler: nucleus filter
+  k += ":" + std::to_string(e->decode_lds_kb);              // decode GEMMs: the LDS budget picks kernel generation and tiling
+  k += ":" + std::to_string(switches_generation());         // every launcher: the kernel-selection switches a replay would keep ignoring
+  k += sa.uniforms ? ":s" : ":g";                           // sampler: draws from the uniforms buffer, or greedy
+  k += ":" + std::to_string(sa.top_k);                      // sampler: top-k filter
+  k += ":" + std::to_string(sa.forced_period);              // sampler: the forced-sdf schedule
+  k += ":" + std::to_string(sa.ctx);                        // sampler: action row of a forced slot (with slot0 = (L0 - 257 ctx) / 17)
+  k += ":" + std::to_string(sa.act_T);                      // sampler: row stride of the embedded action table
+  k += ":" + std::to_string(sa.L0);                         // sampler: column of new token j; shared: the prefix length sh_P = L0 - 1
+  if (e->attn_prof_on) k += ":p";                           // decode attention: launch-window stamps
+  if (e->gemm_prof_on) k += ":q";                           // decode GEMMs: launch-window stamps
+  if (o.sh_P > 0) k += ":sh" + std::to_string(o.sh_G) + ":" + std::to_string(o.sh_row0);   // decode attention: the groups' shared rows
+  if (o.fr_rew || o.fr_hid) k += std::string(":f") + (o.fr_rew ? "r" : "") + (o.fr_hid ? "h" : "");   // frame_heads_kernel and its outputs
+  if (o.scored) k += ":ts";                                 // token_scores_kernel after the sampler
+  return k + e->kvc.graph_key();                            // decode attention: the cache format and its scales
 }
 
 // ---------------------------------------------------------------------------------------- captured step graphs (ivg_engine::graphs)
@@ -327,7 +361,8 @@ static int drop_graphs(ivg_engine* e, hipStream_t st) {
 
 // the graph of n_steps consecutive steps under `key`, captured on first use.  *out = null: no graph (IVG_GRAPH off, the null stream, or
 // the capture failed) -- the caller launches eagerly
-static int step_graph(ivg_engine* e, hipStream_t st, const std::string& key, int n_steps, const GenBuf& g, int Bc, const SampleArgs& sa, hipGraphExec_t* out) {
+static int step_graph(ivg_engine* e, hipStream_t st, const std::string& key, int n_steps, const GenBuf& g, const StepOpts& o, int Bc, const SampleArgs& sa,
+                      hipGraphExec_t* out) {
   *out = nullptr;
   if (!(e->use_graph && st != nullptr)) return 0;
   if (e->graphs_gen != switches_generation()) {   // the switch table changed: no captured step of the old table can be replayed again
@@ -341,7 +376,7 @@ static int step_graph(ivg_engine* e, hipStream_t st, const std::string& key, int
   hipGraphExec_t ex = nullptr;
   if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     int rc = 0;
-    for (int i = 0; i < n_steps && rc == 0; ++i) rc = step_body(e, st, g, Bc, sa, true);
+    for (int i = 0; i < n_steps && rc == 0; ++i) rc = step_body(e, st, g, o, Bc, sa, true);
     const hipError_t ce = hipStreamEndCapture(st, &graph);
     if (rc == 0 && ce == hipSuccess && graph && hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) == hipSuccess) {
       if (e->graphs.size() >= 64) IVG_TRY(drop_graphs(e, st));   // bound the cache (a server fed ever new prompt lengths): drop all, recapture on demand
@@ -357,176 +392,196 @@ static int step_graph(ivg_engine* e, hipStream_t st, const std::string& key, int
   return 0;
 }
 
+struct Chunk { int b0, Bc; StepOpts o; };   // rows [b0, b0 + Bc) of a call, and what their steps carry
+
+// The chunk's inputs into the step buffers, and the cache rows of its prompt: id rows (shared: expanded per group, and the groups' prompt
+// pass), uniforms, the embedded action table, the prompt pass, the embeddings snapshot
+static int stage_chunk(Run& r, const GenerateReq& q, const GenBuf& g, const Chunk& k) {
+  ivg_engine* e = r.e; hipStream_t st = r.st;
+  const ivg_config& c = e->cfg;
+  const DType dt = e->llm_dt;
+  const int b0 = k.b0, Bc = k.Bc, L0 = q.L0, n_new = q.n_new, act_T = q.act_T, group = q.group, H = c.hidden_size;
+  const size_t es = esz(dt);
+  const bool shared = k.o.sh_P > 0;
+  if (e->gemm_prof_on && e->gemm_prof) {
+    CK((int)hipMemsetAsync(e->gemm_prof, 0, (size_t)(4 * c.num_layers + 1) * IVG_GEMM_PROF_SLOTS * 2 * e->Lmax * 8, st));
+    e->gemm_prof_B = Bc;
+  }
+  if (e->attn_prof_on) {  // fresh launch windows for this call: every stamp slot back to 0 (= not stamped)
+    CK((int)hipMemsetAsync(e->attn_prof, 0, (size_t)c.num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8, st));
+    e->attn_prof_B = Bc; e->kvc.prof_eb = (int)e->kvc.elem_bytes();
+  }
+  if (shared) {   // every trajectory starts from a copy of its group's prompt; groups g_lo .. g_hi have rows in this chunk
+    const int g_lo = b0 / group, g_hi = (b0 + Bc - 1) / group;
+    // (attending the prompt rows once per 16 trajectories on the matrix cores -- tools/ubench/prefix_attn_mfma.hip -- shortens the
+    // attention launch but needs a launch of its own per layer: every call measured slower, profiles/r06_shared_prefix_mfma_ab.txt)
+    CK(launch_expand_prompt_rows(q.prompt, q.prompt_stride, g.ids, g.ids_ld, Bc, L0, group, b0, st));
+    if (!q.fanout) {
+      PrefillReq p; p.ids = q.prompt + (long)g_lo * q.prompt_stride; p.ids_stride = q.prompt_stride; p.B = g_hi - g_lo + 1; p.L = L0 - 1; p.ctx = q.ctx;
+      IVG_TRY(r.prefill(p));
+    }
+  } else if (!q.embeds)
+    CK((int)hipMemcpy2DAsync(g.ids, (size_t)g.ids_ld * 8, q.prompt + (long)b0 * q.prompt_stride, (size_t)q.prompt_stride * 8, (size_t)L0 * 8, Bc,
+                             hipMemcpyDeviceToDevice, st));
+  if (q.uniforms)
+    CK((int)hipMemcpy2DAsync(g.uni, (size_t)g.ids_ld * 4, q.uniforms + (long)b0 * n_new, (size_t)n_new * 4, (size_t)n_new * 4, Bc,
+                             hipMemcpyDeviceToDevice, st));
+  if (q.actions) {
+    CK(launch_action_embed(q.actions + (long)b0 * act_T * c.action_dim, e->act_w, e->act_b, g.act_emb, dt, Bc * act_T, c.action_dim, H, st));
+    if (q.B <= g.Bc && !q.fanout) CK((int)hipMemcpyAsync(g.last_act, q.actions, (size_t)q.B * act_T * c.action_dim * 4, hipMemcpyDeviceToDevice, st));
+  }
+  if (!q.reuse_kv && !shared) {
+    PrefillReq p; p.ids = g.ids; p.ids_stride = g.ids_ld; p.B = Bc; p.L = L0; p.act_emb = q.actions ? g.act_emb : nullptr; p.act_T = act_T; p.ctx = q.ctx;
+    p.all_slots = true; p.logits_last = g.logits; p.hidden_last = g.x; p.embeds = q.embeds;
+    IVG_TRY(r.prefill(p));
+  }
+  if (q.embeds) {   // keep what the cache is (being) built from: the whole prompt after a prefill, its last row on the kept-cache path
+    const int p0 = q.reuse_kv ? L0 - 1 : 0;
+    CK((int)hipMemcpy2DAsync(e->emb_snap + (size_t)p0 * H * es, (size_t)e->Lmax * H * es, (const char*)q.embeds + (size_t)p0 * H * es,
+                             (size_t)L0 * H * es, (size_t)(L0 - p0) * H * es, Bc, hipMemcpyDeviceToDevice, st));
+    if (q.reuse_kv)   // the input row of the first forward pass comes straight from the caller
+      CK((int)hipMemcpy2DAsync(g.x, (size_t)H * es, (const char*)q.embeds + (size_t)(L0 - 1) * H * es, (size_t)L0 * H * es, (size_t)H * es, Bc,
+                               hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+
+// The chunk's n_new decisions: the first step(s) eagerly, the rest as replays of the captured step graphs; the heads that read the last
+// forward pass (reward_out, hidden_out) before the final decide-only step
+static int run_steps(Run& r, const GenerateReq& q, const GenBuf& g, const Chunk& k) {
+  ivg_engine* e = r.e; hipStream_t st = r.st;
+  const ivg_config& c = e->cfg;
+  const DType dt = e->llm_dt;
+  const int b0 = k.b0, Bc = k.Bc, L0 = q.L0, n_new = q.n_new, H = c.hidden_size, V = c.vocab_size;
+  const StepOpts& o = k.o;
+  // reuse_kv: the cache already holds positions [0, L0 - 1); the step counter starts at j = 0, whose "decision" is the
+  // forced sdf the prompt ends with (0 % 17 == 0): the sampler re-embeds it with the new action and the forward pass of
+  // that step appends position L0 - 1 and yields the logits of new token 1 -- exactly what the prefill would have left
+  const bool feed_last = q.reuse_kv || o.sh_P > 0;   // the cache holds [0, L0 - 1): step j = 0 feeds the prompt's last token
+  CK(launch_state_set(g.state, feed_last ? L0 - 1 : L0, feed_last ? 0 : 1, st));
+  SampleArgs sa{};
+  sa.logits = g.logits; sa.V = V;
+  sa.uniforms = q.uniforms ? g.uni : nullptr; sa.n_uni = g.ids_ld;
+  sa.top_k = q.top_k;
+  sa.ids_out = g.ids; sa.ids_stride = g.ids_ld; sa.L0 = L0;
+  sa.forced_period = (q.actions || q.force_sdf) ? 17 : 0; sa.forced_token = V - 1;   // (no action embedding is added without actions: sa.act == null)
+  sa.E = e->embed; sa.x = g.x; sa.H = H;
+  sa.act = q.actions ? g.act_emb : nullptr; sa.act_T = q.act_T; sa.ctx = q.ctx;
+  sa.slot0 = q.actions ? (L0 - 257 * q.ctx) / 17 : 0;  // a prompt that already holds t generated frames (MBRL step-wise rollout)
+  sa.state = g.state;
+  sa.temperature = e->temperature;
+  sa.top_p = e->top_p;
+  // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
+  // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
+  auto reward = [&]() -> int {
+    if (q.hidden_out) {   // hidden_states[-1][-1] of HF generate: the last forward pass, after the final norm
+      if (!e->final_norm) return e->fail(IVG_ERR_MISSING, "generate: hidden state requested but 'llm.norm' is not in the weight table");
+      CK(launch_final_hidden(g.x, e->final_norm, (char*)q.hidden_out + (size_t)b0 * H * esz(dt), Bc, H, c.rms_norm_eps, dt, st));
+    }
+    if (!q.reward_out) return 0;
+    if (!e->rew_w) return e->fail(IVG_ERR_MISSING, "generate: reward requested but reward_linear is not loaded");
+    CK(launch_rowdot(g.x, e->rew_w, e->rew_b, q.reward_out + b0, Bc, H, c.rms_norm_eps, dt, st));
+    return 0;
+  };
+  // steps of this call that feed new tokens [j0, j0 + n) and carry frame_heads_kernel: those that hit a frame (test hook)
+  auto note_frames = [&](int j0, int n) {
+    if (!(o.fr_rew || o.fr_hid)) return;
+    int hits = 0;
+    for (int t = j0; t < j0 + n; ++t) hits += t % 17 == 16 && t / 17 < g.F_max;
+    frame_heads_note(hits);
+  };
+  // steps of this call that ran the sampler, and token_scores_kernel after it (test hook)
+  auto note_scores = [&](int n) { if (o.scored) token_scores_note(n); };
+  int j = 1;
+  // step 1 eagerly (also performs every kernel's one-time attribute setup), then replay a captured step graph
+  if (feed_last) { IVG_TRY(step_body(e, st, g, o, Bc, sa, true, q.embeds != nullptr)); if (!q.embeds) note_scores(1); }   // j = 0: feed the prompt's last token
+  if (n_new == 1) IVG_TRY(reward());
+  if (n_new >= 1) { IVG_TRY(step_body(e, st, g, o, Bc, sa, j < n_new)); note_scores(1); if (j < n_new) note_frames(j, 1); ++j; }
+  // the step sequence is position-independent (all step-dependent scalars live in StepState): it is captured once as a graph of
+  // ONE step and once as a graph of `multi` consecutive steps -- the long rollouts replay the multi-step graph (a graph launch
+  // costs the host ~10-16 us and leaves a bubble on the device; 8 steps per launch amortise it), the tail the single-step one
+  // (the same step graph serves both entry modes)
+  constexpr int multi = 8;
+  hipGraphExec_t exec = nullptr, exec_multi = nullptr;
+  const std::string key = j < n_new ? step_key(e, o, sa, Bc) : std::string();
+  if (j < n_new) IVG_TRY(step_graph(e, st, key, 1, g, o, Bc, sa, &exec));
+  if (exec && multi > 1 && n_new - j >= 2 * multi) IVG_TRY(step_graph(e, st, key, multi, g, o, Bc, sa, &exec_multi));
+  while (j < n_new) {
+    if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); note_frames(j, multi); note_scores(multi); j += multi; }
+    else if (exec) { CK((int)hipGraphLaunch(exec, st)); note_frames(j, 1); note_scores(1); ++j; }
+    else { IVG_TRY(step_body(e, st, g, o, Bc, sa, true)); note_frames(j, 1); note_scores(1); ++j; }
+  }
+  if (j == n_new && n_new > 1) {
+    IVG_TRY(reward());
+    IVG_TRY(step_body(e, st, g, o, Bc, sa, false));  // decide the last token (no forward)
+    note_scores(1);
+  }
+  return 0;
+}
+
+// The chunk's rows of every output the call asked for, out of the step buffers
+static int copy_chunk_out(Run& r, const GenerateReq& q, const GenBuf& g, const Chunk& k) {
+  ivg_engine* e = r.e; hipStream_t st = r.st;
+  const DType dt = e->llm_dt;
+  const int b0 = k.b0, Bc = k.Bc, L0 = q.L0, n_new = q.n_new, H = e->cfg.hidden_size;
+  const size_t es = esz(dt);
+  const long Ltot = (long)L0 + n_new;
+  const int F_out = n_new / 17;   // frames whose 16th token, new token 17 i + 16, is fed (<= n_new - 1)
+  if (q.embeds) {
+    CK((int)hipMemcpy2DAsync(q.new_ids_out + (long)b0 * n_new, (size_t)n_new * 8, g.ids + L0, (size_t)g.ids_ld * 8, (size_t)n_new * 8, Bc,
+                             hipMemcpyDeviceToDevice, st));
+    if (n_new > 1)   // inputs of the positions the steps appended: the embeddings of the fed new tokens
+      CK(launch_embed(g.ids + L0, g.ids_ld, e->embed, e->emb_snap + (size_t)L0 * H * es, dt, Bc, n_new - 1, H, e->cfg.vocab_size, st, (long)e->Lmax * H));
+  } else {
+    CK((int)hipMemcpy2DAsync(q.ids_out + (long)b0 * Ltot, (size_t)Ltot * 8, g.ids, (size_t)g.ids_ld * 8, (size_t)Ltot * 8, Bc,
+                             hipMemcpyDeviceToDevice, st));
+  }
+  if (k.o.fr_rew)
+    CK((int)hipMemcpy2DAsync(q.frame_rewards_out + (long)b0 * F_out, (size_t)F_out * 4, g.frame_rew, (size_t)g.F_max * 4, (size_t)F_out * 4, Bc,
+                             hipMemcpyDeviceToDevice, st));
+  if (k.o.scored)
+    CK((int)hipMemcpy2DAsync(q.token_scores_out + (long)b0 * n_new * 3, (size_t)n_new * 12, g.tok_scores, (size_t)g.ids_ld * 12, (size_t)n_new * 12, Bc,
+                             hipMemcpyDeviceToDevice, st));
+  if (k.o.fr_hid)
+    CK((int)hipMemcpy2DAsync((char*)q.frame_hidden_out + (size_t)b0 * F_out * H * es, (size_t)F_out * H * es, g.frame_hid, (size_t)g.F_max * H * es,
+                             (size_t)F_out * H * es, Bc, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 // group > 1 (ivg_generate_shared): `prompt` holds one row per GROUP of `group` consecutive trajectories (B = groups x group rows of
 // actions / uniforms / ids_out).  Per chunk: the prompts of the groups the chunk's rows belong to are prefilled ONCE each -- positions
 // [0, L0 - 1), into cache rows 0 .. n_groups-1 -- and every trajectory then feeds the prompt's last token itself (step j = 0, exactly the
 // kept-cache entry of the step-wise callers: that slot carries the row's own action), appending from position L0 - 1 on in its own
 // cache row; the decode attention reads key rows < L0 - 1 from the group's row (decode_attn_kernel SHARED).
 int Run::generate(const GenerateReq& q) {
-  const int B = q.B, L0 = q.L0, n_new = q.n_new, act_T = q.act_T, ctx = q.ctx, group = q.group;
-  const float* actions = q.actions; const float* uniforms = q.uniforms; const void* embeds = q.embeds; const bool reuse_kv = q.reuse_kv;
-  const ivg_config& c = e->cfg;
-  const DType dt = e->llm_dt;
-  const int H = c.hidden_size, V = c.vocab_size;
-  GenBuf g;
-  gen_layout(e, g, e->gen_buf);
-  const long Ltot = (long)L0 + n_new;
+  const int B = q.B, L0 = q.L0, group = q.group;
+  const GenBuf g = gen_buf(e);
   // fanout (ivg_generate_fanout): the shared branch with the kept cache as the groups' prefix -- one chunk (the entry checks it), group
   // s's prefix already in cache row s, no prompt pass; the kept state is put back at the end exactly as it was
   const bool fanout = q.fanout;
   const bool shared = group > 1 || fanout;
   const int kept_act_T = e->kvc.last_act_T, kept_ctx = e->kvc.last_ctx;   // (what the fan-out restores)
-  g.fr_rew = q.frame_rewards_out != nullptr; g.fr_hid = q.frame_hidden_out != nullptr;
-  const bool frames = g.fr_rew || g.fr_hid;
-  const int F_out = n_new / 17;   // frames whose 16th token, new token 17 i + 16, is fed (<= n_new - 1)
-  g.scored = q.token_scores_out != nullptr;
   if (planning) {   // the prompt pass of the largest chunk (shared: of the most groups a chunk's rows can belong to)
-    PrefillReq p; p.ctx = ctx; p.L = shared ? L0 - 1 : L0;
+    PrefillReq p; p.ctx = q.ctx; p.L = shared ? L0 - 1 : L0;
     p.B = shared ? std::min((std::min(B, g.Bc) + group - 1) / group + 1, std::min(B, g.Bc)) : std::min(B, g.Bc);
-    return (reuse_kv && !shared) || fanout ? 0 : prefill(p);
+    return (q.reuse_kv && !shared) || fanout ? 0 : prefill(p);
   }
   e->kvc.forget_kept();   // kept again once every launch of this call is queued
-  const size_t es = esz(dt);
-  if (embeds && B > g.Bc) return e->fail(IVG_ERR_CAPACITY, "generate (inputs_embeds): batch exceeds the KV-cache chunk");
-  if (embeds && !e->emb_snap) {   // one-time: copy of the inputs the cache is built from (verifies later "same prefix" claims)
-    if (hipMalloc((void**)&e->emb_snap, (size_t)g.Bc * e->Lmax * H * es) != hipSuccess) return e->fail(IVG_ERR_HIP, "hipMalloc of the embeddings snapshot failed");
+  if (q.embeds && B > g.Bc) return e->fail(IVG_ERR_CAPACITY, "generate (inputs_embeds): batch exceeds the KV-cache chunk");
+  if (q.embeds && !e->emb_snap) {   // one-time: copy of the inputs the cache is built from (verifies later "same prefix" claims)
+    if (hipMalloc((void**)&e->emb_snap, (size_t)g.Bc * e->Lmax * e->cfg.hidden_size * esz(e->llm_dt)) != hipSuccess)
+      return e->fail(IVG_ERR_HIP, "hipMalloc of the embeddings snapshot failed");
   }
   for (int b0 = 0; b0 < B; b0 += g.Bc) {
-    const int Bc = std::min(g.Bc, B - b0);
-    if (e->gemm_prof_on && e->gemm_prof) {
-      CK((int)hipMemsetAsync(e->gemm_prof, 0, (size_t)(4 * c.num_layers + 1) * IVG_GEMM_PROF_SLOTS * 2 * e->Lmax * 8, st));
-      e->gemm_prof_B = Bc;
-    }
-    if (e->attn_prof_on) {  // fresh launch windows for this call: every stamp slot back to 0 (= not stamped)
-      CK((int)hipMemsetAsync(e->attn_prof, 0, (size_t)c.num_layers * IVG_ATTN_PROF_SLOTS * 2 * e->Lmax * 8, st));
-      e->attn_prof_B = Bc; e->kvc.prof_eb = (int)e->kvc.elem_bytes();
-    }
-    if (shared) {   // every trajectory starts from a copy of its group's prompt; groups g_lo .. g_hi have rows in this chunk
-      const int g_lo = b0 / group, g_hi = (b0 + Bc - 1) / group;
-      g.sh_P = L0 - 1; g.sh_G = group; g.sh_row0 = g_lo * group - b0;
-      // (attending the prompt rows once per 16 trajectories on the matrix cores -- tools/ubench/prefix_attn_mfma.hip -- shortens the
-      // attention launch but needs a launch of its own per layer: every call measured slower, profiles/r06_shared_prefix_mfma_ab.txt)
-      CK(launch_expand_prompt_rows(q.prompt, q.prompt_stride, g.ids, g.ids_ld, Bc, L0, group, b0, st));
-      if (!fanout) {
-        PrefillReq p; p.ids = q.prompt + (long)g_lo * q.prompt_stride; p.ids_stride = q.prompt_stride; p.B = g_hi - g_lo + 1; p.L = L0 - 1; p.ctx = ctx;
-        IVG_TRY(prefill(p));
-      }
-    } else if (!embeds)
-      CK((int)hipMemcpy2DAsync(g.ids, (size_t)g.ids_ld * 8, q.prompt + (long)b0 * q.prompt_stride, (size_t)q.prompt_stride * 8, (size_t)L0 * 8, Bc,
-                               hipMemcpyDeviceToDevice, st));
-    if (uniforms)
-      CK((int)hipMemcpy2DAsync(g.uni, (size_t)g.ids_ld * 4, uniforms + (long)b0 * n_new, (size_t)n_new * 4, (size_t)n_new * 4, Bc,
-                               hipMemcpyDeviceToDevice, st));
-    if (actions) {
-      CK(launch_action_embed(actions + (long)b0 * act_T * c.action_dim, e->act_w, e->act_b, g.act_emb, dt, Bc * act_T, c.action_dim, H, st));
-      if (B <= g.Bc && !fanout) CK((int)hipMemcpyAsync(g.last_act, actions, (size_t)B * act_T * c.action_dim * 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (!reuse_kv && !shared) {
-      PrefillReq p; p.ids = g.ids; p.ids_stride = g.ids_ld; p.B = Bc; p.L = L0; p.act_emb = actions ? g.act_emb : nullptr; p.act_T = act_T; p.ctx = ctx;
-      p.all_slots = true; p.logits_last = g.logits; p.hidden_last = g.x; p.embeds = embeds;
-      IVG_TRY(prefill(p));
-    }
-    if (embeds) {   // keep what the cache is (being) built from: the whole prompt after a prefill, its last row on the kept-cache path
-      const int p0 = reuse_kv ? L0 - 1 : 0;
-      CK((int)hipMemcpy2DAsync(e->emb_snap + (size_t)p0 * H * es, (size_t)e->Lmax * H * es, (const char*)embeds + (size_t)p0 * H * es,
-                               (size_t)L0 * H * es, (size_t)(L0 - p0) * H * es, Bc, hipMemcpyDeviceToDevice, st));
-      if (reuse_kv)   // the input row of the first forward pass comes straight from the caller
-        CK((int)hipMemcpy2DAsync(g.x, (size_t)H * es, (const char*)embeds + (size_t)(L0 - 1) * H * es, (size_t)L0 * H * es, (size_t)H * es, Bc,
-                                 hipMemcpyDeviceToDevice, st));
-    }
-    // reuse_kv: the cache already holds positions [0, L0 - 1); the step counter starts at j = 0, whose "decision" is the
-    // forced sdf the prompt ends with (0 % 17 == 0): the sampler re-embeds it with the new action and the forward pass of
-    // that step appends position L0 - 1 and yields the logits of new token 1 -- exactly what the prefill would have left
-    const bool feed_last = reuse_kv || shared;   // the cache holds [0, L0 - 1): step j = 0 feeds the prompt's last token
-    CK(launch_state_set(g.state, feed_last ? L0 - 1 : L0, feed_last ? 0 : 1, st));
-    SampleArgs sa{};
-    sa.logits = g.logits; sa.V = V;
-    sa.uniforms = uniforms ? g.uni : nullptr; sa.n_uni = g.ids_ld;
-    sa.top_k = q.top_k;
-    sa.ids_out = g.ids; sa.ids_stride = g.ids_ld; sa.L0 = L0;
-    sa.forced_period = (actions || q.force_sdf) ? 17 : 0; sa.forced_token = V - 1;   // (no action embedding is added without actions: sa.act == null)
-    sa.E = e->embed; sa.x = g.x; sa.H = H;
-    sa.act = actions ? g.act_emb : nullptr; sa.act_T = act_T; sa.ctx = ctx;
-    sa.slot0 = actions ? (L0 - 257 * ctx) / 17 : 0;  // a prompt that already holds t generated frames (MBRL step-wise rollout)
-    sa.state = g.state;
-    sa.temperature = e->temperature;
-    sa.top_p = e->top_p;
-    // step 1 eagerly (also performs every kernel's one-time attribute setup), then replay a captured step graph
-    // (everything a captured step bakes in: the temperature and top_p by their BIT PATTERNS -- to_string keeps six decimals --, this
-    // engine's LDS budget and the generation of the switch table, whose kernel-selection switches a replayed graph would otherwise keep ignoring)
-    uint32_t t_bits; memcpy(&t_bits, &e->temperature, 4);
-    uint32_t p_bits; memcpy(&p_bits, &e->top_p, 4);
-    const std::string key = std::to_string(Bc) + ":" + std::to_string(t_bits) + ":" + std::to_string(p_bits) + ":" + std::to_string(e->decode_lds_kb) + ":" + std::to_string(switches_generation()) +
-                            ":" + (uniforms ? "s" : "g") + ":" + std::to_string(q.top_k) + ":" +
-                            std::to_string(sa.forced_period) + ":" + std::to_string(ctx) + ":" + std::to_string(act_T) + ":" +
-                            std::to_string(L0) + (e->attn_prof_on ? ":p" : "") + (e->gemm_prof_on ? ":q" : "") +   // (the same step graph serves both entry modes)
-                            (shared ? ":sh" + std::to_string(group) + ":" + std::to_string(g.sh_row0) : "") +
-                            (frames ? std::string(":f") + (g.fr_rew ? "r" : "") + (g.fr_hid ? "h" : "") : "") +   // (the steps carry frame_heads_kernel)
-                            (g.scored ? ":ts" : "") +   // (the steps carry token_scores_kernel)
-                            e->kvc.graph_key();   // (the cache format and its scales)
-    // reward head: reads the residual stream left by the LAST forward pass, i.e. before the final decide-only step
-    // overwrites it with the embedding of the last token (mbrl/video_predictor.py:311-313: hidden state of the last step)
-    auto reward = [&]() -> int {
-      if (q.hidden_out) {   // hidden_states[-1][-1] of HF generate: the last forward pass, after the final norm
-        if (!e->final_norm) return e->fail(IVG_ERR_MISSING, "generate: hidden state requested but 'llm.norm' is not in the weight table");
-        CK(launch_final_hidden(g.x, e->final_norm, (char*)q.hidden_out + (size_t)b0 * H * es, Bc, H, c.rms_norm_eps, dt, st));
-      }
-      if (!q.reward_out) return 0;
-      if (!e->rew_w) return e->fail(IVG_ERR_MISSING, "generate: reward requested but reward_linear is not loaded");
-      CK(launch_rowdot(g.x, e->rew_w, e->rew_b, q.reward_out + b0, Bc, H, c.rms_norm_eps, dt, st));
-      return 0;
-    };
-    // steps of this call that feed new tokens [j0, j0 + n) and carry frame_heads_kernel: those that hit a frame (test hook)
-    auto note_frames = [&](int j0, int n) {
-      if (!frames) return;
-      int hits = 0;
-      for (int t = j0; t < j0 + n; ++t) hits += t % 17 == 16 && t / 17 < g.F_max;
-      frame_heads_note(hits);
-    };
-    // steps of this call that ran the sampler, and token_scores_kernel after it (test hook)
-    auto note_scores = [&](int n) { if (g.scored) token_scores_note(n); };
-    int j = 1;
-    if (feed_last) { IVG_TRY(step_body(e, st, g, Bc, sa, true, embeds != nullptr)); if (!embeds) note_scores(1); }   // j = 0: feed the prompt's last token
-    if (n_new == 1) IVG_TRY(reward());
-    if (n_new >= 1) { IVG_TRY(step_body(e, st, g, Bc, sa, j < n_new)); note_scores(1); if (j < n_new) note_frames(j, 1); ++j; }
-    // the step sequence is position-independent (all step-dependent scalars live in StepState): it is captured once as a graph of
-    // ONE step and once as a graph of `multi` consecutive steps -- the long rollouts replay the multi-step graph (a graph launch
-    // costs the host ~10-16 us and leaves a bubble on the device; 8 steps per launch amortise it), the tail the single-step one
-    constexpr int multi = 8;
-    hipGraphExec_t exec = nullptr, exec_multi = nullptr;
-    if (j < n_new) IVG_TRY(step_graph(e, st, key, 1, g, Bc, sa, &exec));
-    if (exec && multi > 1 && n_new - j >= 2 * multi) IVG_TRY(step_graph(e, st, key, multi, g, Bc, sa, &exec_multi));
-    while (j < n_new) {
-      if (exec_multi && n_new - j >= multi) { CK((int)hipGraphLaunch(exec_multi, st)); note_frames(j, multi); note_scores(multi); j += multi; }
-      else if (exec) { CK((int)hipGraphLaunch(exec, st)); note_frames(j, 1); note_scores(1); ++j; }
-      else { IVG_TRY(step_body(e, st, g, Bc, sa, true)); note_frames(j, 1); note_scores(1); ++j; }
-    }
-    if (j == n_new && n_new > 1) {
-      IVG_TRY(reward());
-      IVG_TRY(step_body(e, st, g, Bc, sa, false));  // decide the last token (no forward)
-      note_scores(1);
-    }
-    if (embeds) {
-      CK((int)hipMemcpy2DAsync(q.new_ids_out + (long)b0 * n_new, (size_t)n_new * 8, g.ids + L0, (size_t)g.ids_ld * 8, (size_t)n_new * 8, Bc,
-                               hipMemcpyDeviceToDevice, st));
-      if (n_new > 1)   // inputs of the positions the steps appended: the embeddings of the fed new tokens
-        CK(launch_embed(g.ids + L0, g.ids_ld, e->embed, e->emb_snap + (size_t)L0 * H * es, dt, Bc, n_new - 1, H, V, st, (long)e->Lmax * H));
-    } else {
-      CK((int)hipMemcpy2DAsync(q.ids_out + (long)b0 * Ltot, (size_t)Ltot * 8, g.ids, (size_t)g.ids_ld * 8, (size_t)Ltot * 8, Bc,
-                               hipMemcpyDeviceToDevice, st));
-    }
-    if (g.fr_rew)
-      CK((int)hipMemcpy2DAsync(q.frame_rewards_out + (long)b0 * F_out, (size_t)F_out * 4, g.frame_rew, (size_t)g.F_max * 4, (size_t)F_out * 4, Bc,
-                               hipMemcpyDeviceToDevice, st));
-    if (g.scored)
-      CK((int)hipMemcpy2DAsync(q.token_scores_out + (long)b0 * n_new * 3, (size_t)n_new * 12, g.tok_scores, (size_t)g.ids_ld * 12, (size_t)n_new * 12, Bc,
-                               hipMemcpyDeviceToDevice, st));
-    if (g.fr_hid)
-      CK((int)hipMemcpy2DAsync((char*)q.frame_hidden_out + (size_t)b0 * F_out * H * es, (size_t)F_out * H * es, g.frame_hid, (size_t)g.F_max * H * es,
-                               (size_t)F_out * H * es, Bc, hipMemcpyDeviceToDevice, st));
+    Chunk k{b0, std::min(g.Bc, B - b0), StepOpts()};
+    if (shared) { k.o.sh_P = L0 - 1; k.o.sh_G = group; k.o.sh_row0 = b0 / group * group - b0; }
+    k.o.fr_rew = q.frame_rewards_out != nullptr; k.o.fr_hid = q.frame_hidden_out != nullptr; k.o.scored = q.token_scores_out != nullptr;
+    IVG_TRY(stage_chunk(*this, q, g, k));
+    IVG_TRY(run_steps(*this, q, g, k));
+    IVG_TRY(copy_chunk_out(*this, q, g, k));
   }
   // the last new token is decided but never fed (a shared-context cache is not a per-trajectory cache: never kept)
-  if (B <= g.Bc && !shared) e->kvc.keep(L0 + n_new - 1, B, embeds != nullptr, actions ? act_T : 0, ctx);
+  if (B <= g.Bc && !shared) e->kvc.keep(L0 + q.n_new - 1, B, q.embeds != nullptr, q.actions ? q.act_T : 0, q.ctx);
   if (fanout) {
     // the candidates' own rows lie at positions >= L0 - 1, outside the kept state; the id rows of the kept trajectories were overwritten
     // by the expanded prompts (rows [0, B / group) of candidates), the action table was never touched
@@ -552,8 +607,7 @@ static int read_flag(ivg_engine* e, const GenBuf& g, hipStream_t st, bool* ok) {
 int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int len, const float* actions, int act_T,
                           int ctx, hipStream_t st, bool* ok, bool ids_only) {
   *ok = false;
-  GenBuf g;
-  gen_layout(e, g, e->gen_buf);
+  const GenBuf g = gen_buf(e);
   if (!e->kvc.ids_valid || e->kvc.B != B || len < 1 || len > e->kvc.len || B > g.Bc) return 0;
   // the cache must have been built the same way: with / without actions, the same context length, the same action-table shape;
   // whatever cannot be compared row for row is a mismatch, never a silent "ok"
@@ -575,8 +629,7 @@ int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
 
 int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, hipStream_t st, bool* ok) {
   *ok = false;
-  GenBuf g;
-  gen_layout(e, g, e->gen_buf);
+  const GenBuf g = gen_buf(e);
   if (!e->kvc.snap_valid || !e->emb_snap || !e->kvc.holds(B, L0 - 1) || B > g.Bc) return 0;
   const size_t es = esz(e->llm_dt);
   const long H = e->cfg.hidden_size;
@@ -599,8 +652,7 @@ int Run::extend(const ExtendReq& q) {
   const DType dt = e->llm_dt;
   const int H = c.hidden_size, V = c.vocab_size, B = q.B, T = q.L0 - 1 - q.keep_len, A = c.action_dim;
   const size_t es = esz(dt);
-  GenBuf g;
-  gen_layout(e, g, e->gen_buf);
+  const GenBuf g = gen_buf(e);
   if (!planning) e->kvc.forget_kept();   // rows from keep_len on are about to be overwritten; kept again once every launch is queued
   if (!planning && q.actions) CK(launch_action_embed(q.actions, e->act_w, e->act_b, g.act_emb, dt, B * q.act_T, A, H, st));
   if (q.chunk) {
@@ -610,16 +662,16 @@ int Run::extend(const ExtendReq& q) {
     if (q.token_nll) { p.token_nll = q.token_nll; p.next_ids = q.prompt + q.keep_len + 1; }
     IVG_TRY(prefill(p));
   } else if (!planning) {
-    g.sh_P = 0; g.sh_G = 1; g.sh_row0 = 0;
     CK(launch_state_set(g.state, q.keep_len, 0, st));   // (every step's lm_head advances the position)
     const SampleArgs none{};                            // the sampler never runs
+    const StepOpts plain;                               // per-trajectory rows, no frame heads, no token scores
     for (int t = 0; t < T; ++t) {
       const int pos = q.keep_len + t;
       CK(launch_embed(q.prompt + pos, q.prompt_stride, e->embed, g.x, dt, B, 1, H, V, st));
       const int slot = pos - (257 * q.ctx - 1);
       if (q.actions && slot >= 0 && slot % 17 == 0)   // sdf slot i = slot / 17 carries action row i + ctx - 1
         CK(launch_add_rows(g.x, H, g.act_emb + (size_t)(slot / 17 + q.ctx - 1) * H * es, (long)q.act_T * H, B, H, dt, st));
-      IVG_TRY(step_body(e, st, g, B, none, true, true));
+      IVG_TRY(step_body(e, st, g, plain, B, none, true, true));
       if (q.token_nll) CK(launch_token_nll(g.logits, q.prompt + pos + 1, q.prompt_stride, 0, B, 1, V, q.token_nll + t, T, st));
     }
   }
@@ -666,20 +718,23 @@ size_t kv_select_scratch_bytes(const ivg_engine* e) {   // (a native K / V slab 
   return (size_t)e->kvc.chunk * e->Lmax * std::max<size_t>((size_t)e->cfg.hidden_size * esz(e->llm_dt), 8);
 }
 
+int need_kept_cache(ivg_engine* e, const char* entry) {
+  const KvCache& k = e->kvc;
+  if (k.len > 0 && k.B > 0 && (k.ids_valid || k.snap_valid)) return 0;
+  return e->fail(IVG_ERR_INVALID, std::string(entry) + ": the engine holds no kept cache (the last call was not a per-trajectory generate within the cache chunk, or the format or scales changed since)");
+}
+
 int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st) {
   KvCache& k = e->kvc;
-  if (k.len <= 0 || k.B <= 0 || !(k.ids_valid || k.snap_valid))
-    return e->fail(IVG_ERR_INVALID, "kv_select: the engine holds no kept cache (the last call was not a per-trajectory generate within the cache chunk, or the format or scales changed since)");
+  IVG_TRY(need_kept_cache(e, "kv_select"));
   if (!parents || n <= 0) return e->fail(IVG_ERR_INVALID, "kv_select: parents must hold at least one row");
   KvSelectPlan plan;
   const int prc = kv_select_plan(parents, n, k.B, k.chunk, &plan);
   if (prc == KV_PLAN_CAPACITY) return e->fail(IVG_ERR_CAPACITY, "kv_select: " + std::to_string(n) + " rows exceed the KV-cache chunk (" + std::to_string(k.chunk) + ")");
   if (prc != KV_PLAN_OK) return e->fail(IVG_ERR_INVALID, "kv_select: every parent must be a row of the kept cache, [0, " + std::to_string(k.B) + ")");
   if (plan.n_direct + plan.n_staged > 0) {
-    GenBuf g;
-    gen_layout(e, g, e->gen_buf);
     std::vector<KvSelectBuf> bufs;
-    kv_select_bufs(e, g, bufs);
+    kv_select_bufs(e, gen_buf(e), bufs);
     for (const KvSelectBuf& b : bufs)   // refused before the first launch: a select never leaves the buffers half gathered
       if (plan.n_staged > 0 && (!e->ws.base || b.staged_bytes_per_slab(plan.n_staged) > e->ws.cap))
         return e->fail(IVG_ERR_CAPACITY, "kv_select: the workspace does not hold one slab's staged rows");

@@ -13,6 +13,33 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+# The id-prompt rollout entries of include/ivg.h in the order they are tried: (entry, the input that selects it, the inputs it has no
+# parameter for).  The entries differ in their checks, so which one a call reaches is part of its behaviour.
+_ROLLOUT_ENTRIES = (
+    ("ivg_generate_fanout", "fanout", ("reuse_kv", "reward")),
+    ("ivg_generate_scored", "token_scores", ("reward",)),
+    ("ivg_generate_frames", "frame_outputs", ("reward",)),
+    ("ivg_generate_shared", "shared", ("reuse_kv",)),
+    ("ivg_generate_continue", "reuse_kv", ("force_sdf",)),
+    ("ivg_generate_forced_sdf", "force_sdf", ("reward", "actions")),
+    ("ivg_generate", None, ()),
+)
+
+
+def rollout_entry(fanout=False, token_scores=False, frame_outputs=False, group_size=1, reuse_kv=False, force_sdf=False, reward=False,
+                  actions=False):
+    """The libivg entry that serves a rollout with these inputs (each but ``group_size`` a truth value: asked for / present).
+    ValueError when the entry the inputs select cannot take one of them -- never a neighbouring entry that would drop it."""
+    given = dict(fanout=fanout, token_scores=token_scores, frame_outputs=frame_outputs, shared=group_size > 1, reuse_kv=reuse_kv,
+                 force_sdf=force_sdf, reward=reward, actions=actions)
+    for name, when, lacks in _ROLLOUT_ENTRIES:
+        if when is None or given[when]:
+            bad = [k for k in lacks if given[k]]
+            if bad:
+                raise ValueError(f"rollout: {name} takes no {' / '.join(bad)}")
+            return name
+
+
 class Engine:
     def __init__(self, device, tensors, tok_cfg=None, llm_cfg=None, action_dim=0, reward_head=False,
                  encode_dtype="fp32", decode_dtype="bf16", llm_dtype="bf16", max_batch=1, max_frames=16, max_seq=0,
@@ -121,6 +148,12 @@ class Engine:
     def check(self, rc, what):
         _lib.check(rc, self.h, what)
 
+    def _record(self, *tensors):
+        """The caller's tensors a call reads or writes are in use on the stream it ran on."""
+        for t in tensors:
+            if t is not None:
+                t.record_stream(self._run)
+
     # ---- entry points
     def set_temperature(self, t):
         """``temperature`` of the reference's generate calls (engine state: rarely anything but 1.0)."""
@@ -176,9 +209,7 @@ class Engine:
         act_T = actions.shape[1] if actions is not None else 0
         with self.stream() as s:
             self.check(self.lib.ivg_kv_calibrate(self.h, _ptr(ids), ids.stride(0), B, L, _ptr(actions), act_T, int(ctx), s), "kv_calibrate")
-            for t in (ids, actions):
-                if t is not None:
-                    t.record_stream(self._run)
+            self._record(ids, actions)
         return self
 
     def kv_calibration_finish(self, headroom=1):
@@ -194,9 +225,7 @@ class Engine:
         B, T = pixels.shape[:2]
         with self.stream() as s:
             self.check(self.lib.ivg_tokenize(self.h, _ptr(pixels), dtype_code(pixels.dtype), B, T, _ptr(ids), _ptr(labels), s), "tokenize")
-            for t in (pixels, ids, labels):
-                if t is not None:
-                    t.record_stream(self._run)
+            self._record(pixels, ids, labels)
 
     def encode_context(self, pixels, ids):
         B, T = pixels.shape[:2]
@@ -259,88 +288,38 @@ class Engine:
         with self.stream() as s:
             self.check(self.lib.ivg_kv_extend(self.h, _ptr(prompt), prompt.stride(0), B, int(keep_len), L0, _ptr(actions), act_T, int(ctx),
                                               _ptr(token_nll), s), "kv_extend")
-            for t in (prompt, actions, token_nll):
-                if t is not None:
-                    t.record_stream(self._run)
+            self._record(prompt, actions, token_nll)
         return self
 
-    def generate_fanout(self, prompt, group_size, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, force_sdf=False, frame_rewards=None,
-                        frame_hidden=None, token_scores=None):
-        """``ivg_generate_fanout``: ``generate_scored`` with ``group_size`` candidates per row of ``prompt`` (n_groups, L0) whose shared
-        prefix is the kept K / V cache (no prompt pass; the kept cache is left as it was).  Rows of everything else: group-major."""
-        n_groups, L0 = prompt.shape
-        act_T = actions.shape[1] if actions is not None else 0
+    def rollout(self, prompt, n_new, out, *, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,
+                fanout=False, reward=None, frame_rewards=None, frame_hidden=None, token_scores=None):
+        """One rollout from an id prompt through the entry ``rollout_entry`` names: ``prompt`` (B, L0) -> ``out`` (B, L0 + n_new).
+        ``group_size`` > 1 (ivg_generate_shared) and ``fanout`` (ivg_generate_fanout, the groups' prefix is the kept K / V cache):
+        ``prompt`` holds one row per group and everything else B = groups * group_size rows, row g * group_size + k = sample k of
+        prompt g.  ``reuse_kv``: ivg_generate_continue's kept cache.  ``force_sdf``: the forced-sdf schedule without actions.
+        Outputs beside the tokens: ``reward`` (B) float32 at the last forward pass; ``frame_rewards`` (B, n_new // 17) float32 and
+        ``frame_hidden`` (B, n_new // 17, hidden) in the llm dtype at the 16th token of every frame that was fed; ``token_scores``
+        (B, n_new, 3) float32, logprob, entropy and max_logprob of every decided new token (zeros on forced columns)."""
+        name = rollout_entry(fanout, token_scores is not None, frame_rewards is not None or frame_hidden is not None, group_size, reuse_kv,
+                             force_sdf, reward is not None, actions is not None)
+        rows, L0 = prompt.shape
+        act = (_ptr(actions), actions.shape[1] if actions is not None else 0, int(ctx))
+        sample = (_ptr(uniforms), int(top_k))
+        if name == "ivg_generate_fanout" or name == "ivg_generate_shared":
+            args = (rows, int(group_size), L0, int(n_new), *act, *sample, int(bool(force_sdf)), _ptr(out))
+            args += (_ptr(reward),) if name == "ivg_generate_shared" else (_ptr(frame_rewards), _ptr(frame_hidden), _ptr(token_scores))
+        elif name == "ivg_generate_scored" or name == "ivg_generate_frames":
+            args = (out.shape[0], L0, int(n_new), *act, *sample, int(group_size), int(bool(reuse_kv)), int(bool(force_sdf)), _ptr(out),
+                    _ptr(frame_rewards), _ptr(frame_hidden))
+            args += (_ptr(token_scores),) if name == "ivg_generate_scored" else ()
+        elif name == "ivg_generate_forced_sdf":
+            args = (rows, L0, int(n_new), int(ctx), *sample, _ptr(out))
+        else:   # ivg_generate, ivg_generate_continue
+            args = (rows, L0, int(n_new), *act, *sample, _ptr(out), _ptr(reward))
         with self.stream() as s:
-            self.check(self.lib.ivg_generate_fanout(self.h, _ptr(prompt), prompt.stride(0), n_groups, int(group_size), L0, int(n_new), _ptr(actions),
-                                                    act_T, int(ctx), _ptr(uniforms), int(top_k), int(bool(force_sdf)), _ptr(out), _ptr(frame_rewards),
-                                                    _ptr(frame_hidden), _ptr(token_scores), s), "generate_fanout")
-            for t in (prompt, out, actions, uniforms, frame_rewards, frame_hidden, token_scores):
-                if t is not None:
-                    t.record_stream(self._run)
-
-    def generate(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, reward=None, reuse_kv=False):
-        B, L0 = prompt.shape
-        act_T = actions.shape[1] if actions is not None else 0
-        fn = self.lib.ivg_generate_continue if reuse_kv else self.lib.ivg_generate
-        with self.stream() as s:
-            self.check(fn(self.h, _ptr(prompt), prompt.stride(0), B, L0, int(n_new), _ptr(actions), act_T, int(ctx),
-                                             _ptr(uniforms), int(top_k), _ptr(out), _ptr(reward), s), "generate")
-            for t in (prompt, out, actions, uniforms, reward):
-                if t is not None:
-                    t.record_stream(self._run)
-
-    def generate_shared(self, prompts, group_size, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, reward=None, force_sdf=False):
-        """ivg_generate_shared: ``prompts`` (n_groups, L0), one row per group of ``group_size`` consecutive trajectories; actions /
-        uniforms / out / reward have n_groups * group_size rows (row g * group_size + k = sample k of prompt g)."""
-        n_groups, L0 = prompts.shape
-        act_T = actions.shape[1] if actions is not None else 0
-        with self.stream() as s:
-            self.check(self.lib.ivg_generate_shared(self.h, _ptr(prompts), prompts.stride(0), n_groups, int(group_size), L0, int(n_new), _ptr(actions),
-                                                    act_T, int(ctx), _ptr(uniforms), int(top_k), int(bool(force_sdf)), _ptr(out), _ptr(reward), s),
-                       "generate_shared")
-            for t in (prompts, out, actions, uniforms, reward):
-                if t is not None:
-                    t.record_stream(self._run)
-
-    def generate_forced_sdf(self, prompt, n_new, out, ctx=1, uniforms=None, top_k=100):
-        B, L0 = prompt.shape
-        with self.stream() as s:
-            self.check(self.lib.ivg_generate_forced_sdf(self.h, _ptr(prompt), prompt.stride(0), B, L0, int(n_new), int(ctx), _ptr(uniforms),
-                                                        int(top_k), _ptr(out), s), "generate_forced_sdf")
-            for t in (prompt, out, uniforms):
-                if t is not None:
-                    t.record_stream(self._run)
-
-    def generate_frames(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,
-                        frame_rewards=None, frame_hidden=None):
-        """ivg_generate_frames: the rollout of ``generate`` (``group_size`` > 1: of ``generate_shared``, ``prompt`` one row per group;
-        ``reuse_kv``: of ``ivg_generate_continue``) that also leaves ``frame_rewards`` (B, n_new // 17) float32 and / or ``frame_hidden``
-        (B, n_new // 17, hidden) in the llm dtype: reward and post-norm hidden state at the 16th token of every frame that was fed."""
-        B = out.shape[0]
-        L0 = prompt.shape[1]
-        act_T = actions.shape[1] if actions is not None else 0
-        with self.stream() as s:
-            self.check(self.lib.ivg_generate_frames(self.h, _ptr(prompt), prompt.stride(0), B, L0, int(n_new), _ptr(actions), act_T, int(ctx),
-                                                    _ptr(uniforms), int(top_k), int(group_size), int(bool(reuse_kv)), int(bool(force_sdf)), _ptr(out),
-                                                    _ptr(frame_rewards), _ptr(frame_hidden), s), "generate_frames")
-            for t in (prompt, out, actions, uniforms, frame_rewards, frame_hidden):
-                if t is not None:
-                    t.record_stream(self._run)
-
-    def generate_scored(self, prompt, n_new, out, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,
-                        frame_rewards=None, frame_hidden=None, token_scores=None):
-        """ivg_generate_scored: ``generate_frames`` (without frame outputs also the action-free ``generate``) that also leaves
-        ``token_scores`` (B, n_new, 3) float32: logprob, entropy and max_logprob of every decided new token (zeros on forced columns)."""
-        B = out.shape[0]
-        L0 = prompt.shape[1]
-        act_T = actions.shape[1] if actions is not None else 0
-        with self.stream() as s:
-            self.check(self.lib.ivg_generate_scored(self.h, _ptr(prompt), prompt.stride(0), B, L0, int(n_new), _ptr(actions), act_T, int(ctx),
-                                                    _ptr(uniforms), int(top_k), int(group_size), int(bool(reuse_kv)), int(bool(force_sdf)), _ptr(out),
-                                                    _ptr(frame_rewards), _ptr(frame_hidden), _ptr(token_scores), s), "generate_scored")
-            for t in (prompt, out, actions, uniforms, frame_rewards, frame_hidden, token_scores):
-                if t is not None:
-                    t.record_stream(self._run)
+            self.check(getattr(self.lib, name)(self.h, _ptr(prompt), prompt.stride(0), *args, s),
+                       "generate" if name == "ivg_generate_continue" else name[4:])
+            self._record(prompt, out, actions, uniforms, reward, frame_rewards, frame_hidden, token_scores)
 
     def embed_tokens(self, ids, out):
         B, L = ids.shape
@@ -371,9 +350,7 @@ class Engine:
                 self.check(self.lib.ivg_generate_embeds_scored(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
                                                                _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), _ptr(token_scores), s),
                            "generate_embeds_scored")
-            for t in (embeds, out, hidden, uniforms, token_scores):
-                if t is not None:
-                    t.record_stream(self._run)
+            self._record(embeds, out, hidden, uniforms, token_scores)
         return bool(reused.value)
 
     def logits(self, ids, out, actions=None, ctx=1):
@@ -381,9 +358,7 @@ class Engine:
         act_T = actions.shape[1] if actions is not None else 0
         with self.stream() as s:
             self.check(self.lib.ivg_logits(self.h, _ptr(ids), B, L, _ptr(actions), act_T, int(ctx), _ptr(out), s), "logits")
-            for t in (ids, out, actions):
-                if t is not None:
-                    t.record_stream(self._run)
+            self._record(ids, out, actions)
 
     def eval_forward(self, ids, labels, token_nll, loss_rows, actions=None, ctx=1, hidden=None):
         B, L = ids.shape
@@ -391,17 +366,14 @@ class Engine:
         with self.stream() as s:
             self.check(self.lib.ivg_eval_forward(self.h, _ptr(ids), _ptr(labels), B, L, _ptr(actions), act_T, int(ctx), _ptr(token_nll),
                                                  _ptr(loss_rows), _ptr(hidden), s), "eval_forward")
-            for t in (ids, labels, token_nll, loss_rows, actions, hidden):
-                if t is not None:
-                    t.record_stream(self._run)
+            self._record(ids, labels, token_nll, loss_rows, actions, hidden)
 
     def action_recon_sqerr(self, hidden, actions, ctx, prelude, out):
         B, L = hidden.shape[:2]
         with self.stream() as s:
             self.check(self.lib.ivg_action_recon_sqerr(self.h, _ptr(hidden), _ptr(actions), B, L, actions.shape[1], int(ctx), int(prelude),
                                                        _ptr(out), s), "action_recon_sqerr")
-            for t in (hidden, actions, out):
-                t.record_stream(self._run)
+            self._record(hidden, actions, out)
 
     def profile_enable(self, kclass, on=True):
         self.check(self.lib.ivg_profile_enable(self.h, kclass, int(on)), "profile_enable")

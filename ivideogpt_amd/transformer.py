@@ -156,6 +156,17 @@ def _top_p_of(top_p, do_sample):
     return p
 
 
+def _check_temperature(temperature):
+    if not (isinstance(temperature, (int, float)) and temperature > 0):   # HF's TemperatureLogitsWarper raises the same way
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+
+
+def _result(*values):
+    """What a generate call returns: the values it was asked for (the others are None), a single one bare."""
+    res = tuple(v for v in values if v is not None)
+    return res if len(res) > 1 else res[0]
+
+
 KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
 
 
@@ -507,8 +518,7 @@ class LlamaForCausalLM:
         do_sample, temperature, top_k = gk.get("do_sample", True), gk.get("temperature", 1.0), gk.get("top_k", 100)
         n, rr, want_h, want_s = gk.get("max_new_tokens"), gk.get("return_reward", False), gk.get("output_frame_hidden_states", False), \
             gk.get("output_token_scores", False)
-        if not (isinstance(temperature, (int, float)) and temperature > 0):
-            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        _check_temperature(temperature)
         top_p = _top_p_of(gk.get("top_p"), do_sample)
         if not (isinstance(samples, int) and samples >= 1):
             raise ValueError(f"fan_out: samples must be a positive integer, not {samples!r}")
@@ -517,45 +527,21 @@ class LlamaForCausalLM:
         if rr == "frames" and not self._reward:
             raise ValueError("return_reward='frames' needs a model with reward_prediction=True")
         frames = rr == "frames" or want_h
-        F = _frames_of(n) if frames else 0
-        n_new = n + 1 if frames else n   # (as generate: one token more, the forced sdf that feeds the last frame's 16th token)
+        if frames:
+            _frames_of(n)
         eng = self._engine
-        B0, L0 = ids.shape
-        B = B0 * samples
+        B = ids.shape[0] * samples
         if eng is None:
             raise ValueError("fan_out: no kept cache (the model has not generated yet)")
         if B > eng.max_batch:
             raise ValueError(f"fan_out: {B} candidates exceed the batch the engine was built for ({eng.max_batch}); run the model once at that batch first")
-        u = gk.get("uniforms")
-        if u is None:
-            u = self._uniforms(B, n, do_sample, gk.get("generator"))
-        if u is not None:
-            u = u.to(device=self.device, dtype=torch.float32)
-            if u.shape[1] < n_new:
-                u = torch.cat([u, u.new_zeros(B, n_new - u.shape[1])], 1)
-            u = u[:, :n_new].contiguous()
-        if act is not None and frames:
-            need = (L0 - 257 * ctx) // 17 + n_new // 17 + ctx
-            if act.shape[1] < need:
-                act = torch.cat([act, act.new_zeros(B, need - act.shape[1], act.shape[2])], 1)
-        out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=self.device)
-        fr = torch.empty(B, F, dtype=torch.float32, device=self.device) if rr == "frames" else None
-        fh = torch.empty(B, F, self._cfg["hidden_size"], dtype=self.torch_dtype, device=self.device) if want_h else None
-        ts = _token_scores_buffer(B, n_new, self.device) if want_s else None
-        eng.set_temperature(temperature).set_top_p(top_p)
         try:
-            eng.generate_fanout(ids, samples, n_new, out, actions=act, ctx=ctx, uniforms=u, top_k=top_k or self._cfg["vocab_size"],
-                                force_sdf=act is None and (frames or force_sdf), frame_rewards=fr, frame_hidden=fh, token_scores=ts)
+            r = self._rollout(ids, n, (do_sample, temperature, top_k, top_p, gk.get("generator"), gk.get("uniforms")), act=act, ctx=ctx, fan=samples,
+                              force_sdf=act is None and (frames or force_sdf), sdf_tail=frames, frame_rewards=rr == "frames", frame_hidden=want_h,
+                              scores=want_s)
         except (AssertionError, _lib.IvgError) as err:
             raise ValueError(f"fan_out: {err}") from None
-        res = (out[:, :L0 + n].contiguous() if frames else out,)
-        if fr is not None:
-            res += (fr,)
-        if fh is not None:
-            res += (fh,)
-        if want_s:
-            res += (_token_scores_of(ts, n=n),)
-        return res if len(res) > 1 else res[0]
+        return r.result(r.tokens.contiguous(), r.frame_rewards, r.frame_hidden, r.token_scores)
 
     @torch.no_grad()
     def fan_out(self, input_ids, samples, **generate_kwargs):
@@ -573,6 +559,53 @@ class LlamaForCausalLM:
         if not do_sample:
             return None
         return torch.rand(B, n, device=self.device, dtype=torch.float32, generator=generator)
+
+    def _sampling_engine(self, B, frames, temperature, top_p, existing=False):
+        """The engine (``existing``: the live one, whose kept cache the call is about) with the call's temperature and top_p set."""
+        eng = self._engine if existing else self._ensure(B, frames)
+        return eng.set_temperature(temperature).set_top_p(top_p)
+
+    def _rollout(self, ids, n, sampling, act=None, ctx=1, groups=None, fan=0, reuse_kv=False, force_sdf=False, sdf_tail=False, reward=False,
+                 frame_rewards=False, frame_hidden=False, scores=False):
+        """One ``Engine.rollout`` of ``n`` new tokens after ``ids``, from the uniforms to the results, for every id-prompt entry of both
+        classes.  ``sampling``: (do_sample, temperature, top_k, top_p, generator, uniforms).  ``groups`` = (t, B0): ``ids`` is
+        ``prompts.repeat(t, 1)``, run as B0 groups of t -- inputs and results stay in the caller's row order, translated to and from
+        the engine's group-major one.  ``fan`` = samples > 0: ``ids`` holds one row per kept trajectory, everything else
+        ``rows * samples`` rows, group-major (the public order there); the live engine is used as it is.  ``sdf_tail``: the engine is
+        asked for one token more, the forced sdf that feeds the last frame's 16th token: the uniforms get a column (never read) and a
+        table that ends with the last frame's action a zero row (the token is dropped and never fed, the row reaches no output).
+        -> namespace(tokens (B, L0 + n), reward (B), frame_rewards (B, F), frame_hidden (B, F, hidden), token_scores: TokenScores of
+        (B, n)), None what was not asked for; ``.result(*values)``: the values that are not None, a single one bare."""
+        do_sample, temperature, top_k, top_p, generator, u = sampling
+        L0 = ids.shape[1]
+        B = ids.shape[0] * fan if fan else ids.shape[0]
+        t, B0 = groups or (1, B)
+        n_new = n + 1 if sdf_tail else n
+        if u is None:
+            u = self._uniforms(B, n, do_sample, generator)
+        if u is not None:
+            u = u.to(device=self.device, dtype=torch.float32)
+            if u.shape[1] < n_new:
+                u = torch.cat([u, u.new_zeros(B, n_new - u.shape[1])], 1)
+            u = u[:, :n_new].contiguous()
+        if act is not None and sdf_tail:
+            need = (L0 - 257 * ctx) // 17 + n_new // 17 + ctx
+            if act.shape[1] < need:
+                act = torch.cat([act, act.new_zeros(B, need - act.shape[1], act.shape[2])], 1)
+        dev, F = self.device, n_new // 17
+        out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=dev)
+        rw = torch.empty(B, dtype=torch.float32, device=dev) if reward else None
+        fr = torch.empty(B, F, dtype=torch.float32, device=dev) if frame_rewards else None
+        fh = torch.empty(B, F, self._cfg["hidden_size"], dtype=self.torch_dtype, device=dev) if frame_hidden else None
+        ts = _token_scores_buffer(B, n_new, dev) if scores else None
+        self._sampling_engine(B, act.shape[1] if act is not None else 32, temperature, top_p, existing=bool(fan)).rollout(
+            ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx, uniforms=_to_group_major(u, t, B0),
+            top_k=top_k or self._cfg["vocab_size"], group_size=fan or t, reuse_kv=reuse_kv, force_sdf=force_sdf, fanout=bool(fan), reward=rw,
+            frame_rewards=fr, frame_hidden=fh, token_scores=ts)
+        tokens = _from_group_major(out, t, B0)
+        return SimpleNamespace(tokens=tokens[:, :-1] if sdf_tail else tokens, reward=_from_group_major(rw, t, B0),
+                               frame_rewards=_from_group_major(fr, t, B0), frame_hidden=_from_group_major(fh, t, B0),
+                               token_scores=_token_scores_of(ts, t, B0, n) if scores else None, result=_result)
 
     def get_input_embeddings(self):
         return _Embedding(self)
@@ -597,8 +630,7 @@ class LlamaForCausalLM:
         ``hidden_states[-1][-1]`` = last layer (post final norm) of the LAST forward pass, (B, 1, hidden).
         When the engine's KV cache was built from exactly ``inputs_embeds[:, :-1]`` (the step-wise rollout: previous prompt +
         the embeddings of the tokens it generated), only the last row is fed -- verified on the device, never assumed."""
-        if not (isinstance(temperature, (int, float)) and temperature > 0):   # HF's TemperatureLogitsWarper raises the same way
-            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        _check_temperature(temperature)
         top_p = _top_p_of(top_p, do_sample)
         if inputs_embeds is not None:
             emb = inputs_embeds.to(device=self.device, dtype=self.torch_dtype).contiguous()
@@ -607,7 +639,7 @@ class LlamaForCausalLM:
             hidden = torch.empty(B, 1, emb.shape[-1], dtype=self.torch_dtype, device=self.device) if output_hidden_states else None
             u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
             ts = _token_scores_buffer(B, max_new_tokens, self.device) if output_token_scores else None
-            self.last_generate_reused_cache = self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_embeds(
+            self.last_generate_reused_cache = self._sampling_engine(B, 32, temperature, top_p).generate_embeds(
                 emb, max_new_tokens, out, hidden=hidden, uniforms=u, top_k=top_k or self._cfg["vocab_size"], allow_reuse=use_cache, token_scores=ts)
             scores = _token_scores_of(ts) if output_token_scores else None
             if not return_dict_in_generate:
@@ -618,23 +650,11 @@ class LlamaForCausalLM:
             return res
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
-        out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=self.device)
-        u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
         t, B0 = shared_prompt_groups(ids, shared_context) if shared_context else (1, B)
-        if output_token_scores:
-            if not (t > 1 and L0 >= 2):
-                t, B0 = 1, B
-            ts = _token_scores_buffer(B, max_new_tokens, self.device)
-            self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_scored(
-                ids[:B0].contiguous() if t > 1 else ids, max_new_tokens, out, uniforms=_to_group_major(u, t, B0), top_k=top_k or self._cfg["vocab_size"],
-                group_size=t, token_scores=ts)
-            return _from_group_major(out, t, B0), _token_scores_of(ts, t, B0)
-        if t > 1 and L0 >= 2:
-            self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_shared(
-                ids[:B0].contiguous(), t, max_new_tokens, out, uniforms=_to_group_major(u, t, B0), top_k=top_k or self._cfg["vocab_size"])
-            return _from_group_major(out, t, B0)
-        self._ensure(B).set_temperature(temperature).set_top_p(top_p).generate(ids, max_new_tokens, out, uniforms=u, top_k=top_k or self._cfg["vocab_size"])
-        return out
+        if not (t > 1 and L0 >= 2):   # (nothing to share)
+            t, B0 = 1, B
+        r = self._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), groups=(t, B0), scores=output_token_scores)
+        return r.result(r.tokens, r.token_scores)
 
     @torch.no_grad()
     def logits(self, input_ids):
@@ -679,32 +699,6 @@ def _frames_of(max_new_tokens):
     if not (isinstance(max_new_tokens, int) and max_new_tokens >= 16 and (max_new_tokens + 1) % 17 == 0):
         raise ValueError(f"per-frame outputs need max_new_tokens = 17 * frames - 1 (16 tokens per frame + the sdf between frames), not {max_new_tokens!r}")
     return (max_new_tokens + 1) // 17
-
-
-def _generate_frames(llm, eng, ids, max_new_tokens, act, ctx, u, top_k, t, B0, reuse_kv, force_sdf, want_rewards, want_hidden, want_scores=False):
-    """One ivg_generate_frames call of ``max_new_tokens + 1`` tokens -> (tokens (B, L0 + max_new_tokens), rewards (B, F) or None, hidden
-    (B, F, H) or None), rows in the caller's order (``t`` > 1: translated to and from the engine's group-major order).
-    ``want_scores``: ivg_generate_scored instead, and a fourth value, the TokenScores of the ``max_new_tokens`` columns."""
-    B, L0 = ids.shape
-    F, n_new = _frames_of(max_new_tokens), max_new_tokens + 1
-    if u is not None and u.shape[1] < n_new:   # (the extra token is the forced sdf: its column is never read)
-        u = torch.cat([u, u.new_zeros(B, n_new - u.shape[1])], 1)
-    if u is not None:
-        u = u[:, :n_new].contiguous()
-    out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=llm.device)
-    fr = torch.empty(B, F, dtype=torch.float32, device=llm.device) if want_rewards else None
-    fh = torch.empty(B, F, llm._cfg["hidden_size"], dtype=llm.torch_dtype, device=llm.device) if want_hidden else None
-    if want_scores:
-        ts = _token_scores_buffer(B, n_new, llm.device)
-        eng.generate_scored(ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx,
-                            uniforms=_to_group_major(u, t, B0), top_k=top_k, group_size=t, reuse_kv=reuse_kv, force_sdf=force_sdf,
-                            frame_rewards=fr, frame_hidden=fh, token_scores=ts)
-        return (_from_group_major(out, t, B0)[:, :-1], _from_group_major(fr, t, B0), _from_group_major(fh, t, B0),
-                _token_scores_of(ts, t, B0, max_new_tokens))
-    eng.generate_frames(ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx,
-                        uniforms=_to_group_major(u, t, B0), top_k=top_k, group_size=t, reuse_kv=reuse_kv, force_sdf=force_sdf,
-                        frame_rewards=fr, frame_hidden=fh)
-    return _from_group_major(out, t, B0)[:, :-1], _from_group_major(fr, t, B0), _from_group_major(fh, t, B0)
 
 
 class HeadModelWithAction:
@@ -862,8 +856,7 @@ class HeadModelWithAction:
         ``sdf`` columns 0 (include/ivg.h ivg_generate_scored); the other results are those of the call without it.  With
         ``return_reward=True`` the single reward is read off the per-frame rewards of the same call, which needs
         ``max_new_tokens`` a positive multiple of 17 (the step-wise callers' 17; ValueError otherwise)."""
-        if not (isinstance(temperature, (int, float)) and temperature > 0):
-            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        _check_temperature(temperature)
         top_p = _top_p_of(top_p, do_sample)
         per_frame = isinstance(return_reward, str)
         if per_frame and return_reward != "frames":
@@ -881,50 +874,16 @@ class HeadModelWithAction:
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
         act = action.to(device=llm.device, dtype=torch.float32).contiguous()
-        if per_frame or output_frame_hidden_states:
-            # the extra token, the forced sdf after the last frame, is decided with the action row after the last one: a table that
-            # ends with the last frame's action gets a zero row (the token is dropped and never fed, the row reaches no output)
-            need = (L0 - 257 * self.context) // 17 + (max_new_tokens + 1) // 17 + self.context
-            if act.shape[1] < need:
-                act = torch.cat([act, act.new_zeros(B, need - act.shape[1], act.shape[2])], 1)
-            t, B0 = shared_prompt_groups(ids, shared_context) if (shared_context and not reuse_cache) else (1, B)
-            if not (t > 1 and L0 == 257 * self.context):
-                t, B0 = 1, B
-            u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
-            out, fr, fh, *sc = _generate_frames(llm, llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens,
-                                                act, self.context, u, top_k or llm._cfg["vocab_size"], t, B0, reuse_cache, False, per_frame,
-                                                output_frame_hidden_states, output_token_scores)
-            res = (out,)
-            if per_frame:
-                res += (fr,)
-            if output_frame_hidden_states:
-                res += (fh,)
-            return res + (sc[0],) if output_token_scores else res
-        out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
-        u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
-        reward = torch.empty(B, dtype=torch.float32, device=llm.device) if return_reward else None
+        frames = per_frame or output_frame_hidden_states
+        single = bool(return_reward) and not frames   # one value (B); the scored entry has the per-frame rewards only: their last one
         t, B0 = shared_prompt_groups(ids, shared_context) if (shared_context and not reuse_cache) else (1, B)
-        if output_token_scores:
-            if not (t > 1 and L0 == 257 * self.context):
-                t, B0 = 1, B
-            ts = _token_scores_buffer(B, max_new_tokens, llm.device)
-            fr = torch.empty(B, max_new_tokens // 17, dtype=torch.float32, device=llm.device) if return_reward else None
-            llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate_scored(
-                ids[:B0].contiguous() if t > 1 else ids, max_new_tokens, out, actions=_to_group_major(act, t, B0), ctx=self.context,
-                uniforms=_to_group_major(u, t, B0), top_k=top_k or llm._cfg["vocab_size"], group_size=t, reuse_kv=reuse_cache, frame_rewards=fr,
-                token_scores=ts)
-            out, sc = _from_group_major(out, t, B0), _token_scores_of(ts, t, B0)
-            return (out, _from_group_major(fr, t, B0)[:, -1].contiguous(), sc) if return_reward else (out, sc)
-        if t > 1 and L0 == 257 * self.context:
-            llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate_shared(
-                ids[:B0].contiguous(), t, max_new_tokens, out, actions=_to_group_major(act, t, B0), ctx=self.context, uniforms=_to_group_major(u, t, B0),
-                top_k=top_k or llm._cfg["vocab_size"], reward=reward)
-            out, reward = _from_group_major(out, t, B0), _from_group_major(reward, t, B0)
-            return (out, reward) if return_reward else out
-        llm._ensure(B, act.shape[1]).set_temperature(temperature).set_top_p(top_p).generate(
-            ids, max_new_tokens, out, actions=act, ctx=self.context, uniforms=u, top_k=top_k or llm._cfg["vocab_size"], reward=reward,
-            reuse_kv=reuse_cache)
-        return (out, reward) if return_reward else out
+        if not (t > 1 and L0 == 257 * self.context):   # (a shared prefix ends before the first action slot)
+            t, B0 = 1, B
+        r = llm._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), act=act, ctx=self.context, groups=(t, B0),
+                         reuse_kv=reuse_cache, sdf_tail=frames, reward=single and not output_token_scores,
+                         frame_rewards=per_frame or (single and output_token_scores), frame_hidden=output_frame_hidden_states, scores=output_token_scores)
+        rewards = r.frame_rewards[:, -1].contiguous() if single and output_token_scores else r.frame_rewards
+        return r.result(r.tokens, r.reward, rewards, r.frame_hidden, r.token_scores)
 
     @torch.no_grad()
     def generate_without_action(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, generator=None,
@@ -936,29 +895,16 @@ class HeadModelWithAction:
         ``output_frame_hidden_states=True``: -> ``(tokens, hidden (B, F, hidden))``, the post-norm hidden state at every predicted
         frame's 16th token (as ``generate``); the tokens are those of the plain call.
         ``output_token_scores=True`` appends the ``TokenScores`` as the last element (as ``generate``)."""
-        if not (isinstance(temperature, (int, float)) and temperature > 0):
-            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        _check_temperature(temperature)
         top_p = _top_p_of(top_p, do_sample)
         if output_frame_hidden_states:
             _frames_of(max_new_tokens)   # (ValueError before any engine work)
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
-        B, L0 = ids.shape
         assert (max_new_tokens + 1) % (self.segment_length - self.context) == 0, "max_new_tokens must be (tokens_per_dyna + 1) * frames - 1"
-        out = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=llm.device)
-        u = uniforms if uniforms is not None else llm._uniforms(B, max_new_tokens, do_sample, generator)
-        if output_frame_hidden_states:
-            out, _, fh, *sc = _generate_frames(llm, llm._ensure(B).set_temperature(temperature).set_top_p(top_p), ids, max_new_tokens, None, self.context, u,
-                                               top_k or llm._cfg["vocab_size"], 1, B, False, True, False, True, output_token_scores)
-            return (out, fh, sc[0]) if output_token_scores else (out, fh)
-        if output_token_scores:
-            ts = _token_scores_buffer(B, max_new_tokens, llm.device)
-            llm._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_scored(ids, max_new_tokens, out, ctx=self.context, uniforms=u,
-                                                                                        top_k=top_k or llm._cfg["vocab_size"], force_sdf=True, token_scores=ts)
-            return out, _token_scores_of(ts)
-        llm._ensure(B).set_temperature(temperature).set_top_p(top_p).generate_forced_sdf(ids, max_new_tokens, out, ctx=self.context, uniforms=u,
-                                                                               top_k=top_k or llm._cfg["vocab_size"])
-        return out
+        r = llm._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), ctx=self.context, force_sdf=True,
+                         sdf_tail=output_frame_hidden_states, frame_hidden=output_frame_hidden_states, scores=output_token_scores)
+        return r.result(r.tokens, r.frame_hidden, r.token_scores)
 
     @torch.no_grad()
     def __call__(self, input_ids=None, attention_mask=None, labels=None, position_ids=None, action=None):

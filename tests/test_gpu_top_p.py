@@ -273,11 +273,11 @@ def test_lanes_do_not_share_top_p():
     # engine-level entry, below the Python cache): only its own state, still 1.0, may decide
     assert lib().ivg_set_top_p(a._engine.h, 0.3) == 0
     out_b = torch.empty(prompt.shape[0], prompt.shape[1] + 30, dtype=torch.int64, device=DEV)
-    b._engine.generate(prompt.contiguous(), 30, out_b, uniforms=u, top_k=100)
+    b._engine.rollout(prompt.contiguous(), 30, out_b, uniforms=u, top_k=100)
     assert torch.equal(out_b.cpu(), ref_b), "lane a's top_p reached lane b's engine"
     # and the other way round: b at 0.3 through the C ABI, a's engine (left at 0.3 by its own call) back to 1.0 by the C ABI
     assert lib().ivg_set_top_p(b._engine.h, 0.3) == 0 and lib().ivg_set_top_p(a._engine.h, 1.0) == 0
     out_a2 = torch.empty_like(out_b)
-    a._engine.generate(prompt.contiguous(), 30, out_a2, uniforms=u, top_k=100)
+    a._engine.rollout(prompt.contiguous(), 30, out_a2, uniforms=u, top_k=100)
     assert torch.equal(out_a2.cpu(), ref_b), "lane b's top_p reached lane a's engine"
     a._engine._top_p = 1.0

@@ -113,8 +113,8 @@ def test_header_bindings_and_engine_agree():
             assert len(args) == len(_lib.EXPORTS[base][1]) + extra and len(params) == len(_header_params(base)) + extra
             assert "token_scores_out" in params[-2]
     assert len(_lib.EXPORTS["ivg_generate_scored"][1]) == 19 and len(_lib.EXPORTS["ivg_op_token_scores"][1]) == 6
-    assert callable(Engine.generate_scored) and "token_scores" in Engine.generate_embeds.__code__.co_varnames
-    assert "token_scores" in Engine.generate_scored.__code__.co_varnames
+    assert callable(Engine.rollout) and "token_scores" in Engine.generate_embeds.__code__.co_varnames
+    assert "token_scores" in Engine.rollout.__code__.co_varnames
 
 
 def test_per_frame_sums_and_means_the_sampled_columns():
