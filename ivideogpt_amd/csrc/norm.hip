@@ -2,7 +2,7 @@
 //   gn_partial / gn_apply : GroupNorm(32 groups) [+ SiLU] [+ position embedding] on NHWC tensors
 //                           (SURVEY.md 2.4 K4, and the q/kv norms of K8).  Deterministic two-stage
 //                           statistics: per-chunk fp32 sums -> fp64 combine in fixed order.
-//   add_rmsnorm           : residual-stream update (sum of split-K partials) + Llama RMSNorm (K13).
+//   add_rmsnorm           : Llama RMSNorm of the residual stream, which it only reads (K13).
 //   softmax_rows          : row softmax of fp32 scores with optional causal mask (K7/K8/K16).
 #include "ops.h"
 
@@ -202,8 +202,8 @@ int launch_groupnorm_apply(const void* X, void* Y, const void* part, int nchunks
 
 // ------------------------------------------------------------------------------------------------ RMSNorm
 // One workgroup per row (H <= 2048), every thread owns up to 8 strided elements so all loads of a pass are
-// independent (the decode step is latency-bound: M = batch rows only).  x (T) is updated in place when split-K
-// partials are given (fixed order s = 0..S-1), out = rmsnorm(x) * w.
+// independent (the decode step is latency-bound: M = batch rows only).  x (T) is read only (the kernel takes no
+// split-K partials; M is unused), out = rmsnorm(x) * w with the normalised row rounded to T before the weight.
 template <typename T>
 __global__ __launch_bounds__(256) void add_rmsnorm_kernel(T* __restrict__ x, long xs, const float* __restrict__ w, T* __restrict__ out,
                                                           int M, int H, float eps) {
