@@ -196,6 +196,39 @@ int ivg_tokenize(ivg_engine* e, const void* pixels, int pixel_dtype, int B, int 
 int ivg_encode_context(ivg_engine* e, const void* pixels, int pixel_dtype, int B, int T, int64_t* ids_out, int64_t ids_stride,
                        ivg_stream stream);
 
+/* ---- The encoder's context cache: tokens of OBSERVED frames without encoding the context again.
+ * The reference's tokenize encodes every future frame on its own; a frame sees the context only through the cross-attention K / V of the
+ * conditional encoder (compressive_vq_model.py:174-196).  An ivg_enc_cache keeps those projections per trajectory -- for every
+ * cross-attention site the projected Kp [kv][C] and VpT [C][kv] (kv = ctx * side * side) in the encode dtype, the context length in
+ * force when it was filled, its row count and a filled flag; the engine owns the device memory.  Create / destroy: the refusals of
+ * ivg_cache_create (B against max_batch: IVG_ERR_CAPACITY). */
+typedef struct ivg_enc_cache ivg_enc_cache;
+int ivg_enc_cache_create(ivg_engine* e, int B, ivg_enc_cache** out);
+void ivg_enc_cache_destroy(ivg_engine* e, ivg_enc_cache* c);
+/* ivg_encode_context that also fills `cache` (created for the same B): the plain encoder runs over the context frames once, the
+ * features the conditional encoder reads are kept (as the full ivg_tokenize keeps them) and projected per site into the cache.  The
+ * ids are those of ivg_encode_context, bit for bit. */
+int ivg_encode_context_cached(ivg_engine* e, const void* pixels, int pixel_dtype, int B, int T, int64_t* ids_out, int64_t ids_stride,
+                              ivg_enc_cache* cache, ivg_stream stream);
+/* The tokens of n observed frames per trajectory against a filled cache.  frames (B, n, 3, H, W), planar, IVG_F32 or IVG_BF16;
+ * ids_out int64 (B, ids_stride >= 17 n): column 17 i + j, j < 16, is dyn token j of frame i (with the num_vq_embeddings offset),
+ * column 17 i + 16 is the sdf token, columns >= 17 n are not touched.  For the first n future frames of a clip that is
+ * ivg_tokenize(clip) columns [257*ctx, 257*ctx + 17 n - 1) followed by the sdf the next frame's slot needs: what a prompt ending in
+ * sdf is extended by (ivg_kv_extend).  The call runs the conditional encoder trunk over the B * n frames with the cached projections,
+ * quant_linear and the argmin against the dyn codebook -- no plain-encoder launch, no projection launch -- on `stream`, without
+ * synchronising the host, and never grows the workspace: n <= max_frames - ctx, else IVG_ERR_CAPACITY (as B above max_batch).
+ * IVG_ERR_INVALID, before anything is launched or written: an engine without a tokenizer, a null or unfilled cache, a cache of another
+ * engine or of another B, a cache filled under another context length than the one in force, n < 1, a pixel_dtype other than the two.
+ * Arithmetic: the ids are those of ivg_tokenize bit for bit on an fp32 encoder, whose kernels sum every output element in one K order
+ * whatever the number of images.  A bf16 encoder's ids are promised equal only where both calls dispatch the same kernels: its 1x1
+ * convolutions and dense GEMMs with an output width that is a multiple of 256 go to the 256 x 256-tile kernel from 4096 rows on (a
+ * multiple of 128: from 2^18 rows; gemm256.hip), and the row count is B * n * pixels here, B * (T - ctx) * pixels there. */
+int ivg_tokenize_frames(ivg_engine* e, const void* frames, int pixel_dtype, int B, int n, const ivg_enc_cache* cache, int64_t* ids_out,
+                        int64_t ids_stride, ivg_stream stream);
+/* ivg_cache_select for the encoder's cache: a NEW cache of n rows, row i gathered from row parents[i] of src (a HOST array; src is
+ * unchanged and stays the caller's), with the context length of src's fill.  Contract and refusals as there. */
+int ivg_enc_cache_select(ivg_engine* e, const ivg_enc_cache* src, const int32_t* parents, int n, ivg_enc_cache** out, ivg_stream stream);
+
 /* CompressiveVQModel.detokenize (compressive_vq_model.py:222-277).
  * ids int64 (B, 257*ctx - 1 + 17*F); pixels_out float32 (B, ctx + F, 3, H, W), unclamped.
  * cache: NULL, or a handle from ivg_cache_create.  cache_mode 1 = fill it (return_cache=True), 2 = reuse it
@@ -685,7 +718,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps; "enc_plain_images" / "enc_cond_images": images sent through the plain / the conditional encoder trunk; "enc_kv_projections": cross-attention K / V projections made for an encoder, one per site and call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

@@ -211,13 +211,15 @@ void Run::prof_cancel(DType dt, int base) {
 // Every entry point first walks its own allocation plan (host arithmetic only) and grows the arena if this call
 // needs more than any earlier one; then runs for real.  f(Run&) must be the same call in both passes.
 template <typename F>
-static int plan_then_run(ivg_engine* e, hipStream_t st, F&& f) {
+static int plan_then_run(ivg_engine* e, hipStream_t st, F&& f, bool may_grow = true) {
   e->ws.planning = true; e->ws.off = 0; e->ws.high = 0; e->ws.overflow = false;
   Run p{e, nullptr, true};
   int rc = f(p);
   const size_t need = e->ws.high + (1 << 20);
   e->ws.planning = false; e->ws.off = 0;
   if (rc) return rc;
+  // (an entry that promises not to synchronise the host stays inside what ivg_create planned, or says so)
+  if (need > e->ws.cap && !may_grow) return e->fail(IVG_ERR_CAPACITY, "internal: the call needs more workspace than the engine was created with");
   if (need > e->ws.cap) {
     API_CK(hipDeviceSynchronize());
     if (e->ws.base) API_CK(hipFree(e->ws.base));
@@ -417,6 +419,98 @@ int ivg_encode_context(ivg_engine* e, const void* pixels, int pixel_dtype, int B
   if (T < e->ctx || ids_stride < 257L * e->ctx) return e->fail(IVG_ERR_INVALID, "encode_context: T < context_length or ids_stride < 257*ctx");
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
     return r.tokenize(pixels, (DType)pixel_dtype, B, T, ids_out, ids_stride, nullptr, true); });
+}
+
+// ---- the encoder's context cache: the conditional encoder's cross-attention K / V projections of a context, kept per trajectory
+int ivg_enc_cache_create(ivg_engine* e, int B, ivg_enc_cache** out) {
+  if (!e || !out || e->cfg.n_levels <= 0) return IVG_ERR_INVALID;
+  const ivg_config& c = e->cfg;
+  if (B <= 0 || B > c.max_batch) return e->fail(IVG_ERR_CAPACITY, "enc_cache_create: batch " + std::to_string(B) + " exceeds the engine's max_batch");
+  ivg_enc_cache* k = new ivg_enc_cache();
+  k->owner = e; k->B = B;
+  bool ok = true;
+  for (const XAttW& x : e->cenc.xatt) {   // sized for the pretrained context length: any ivg_set_context_length fits
+    const size_t bytes = (size_t)B * x.kv_rows * x.C * dtype_size(e->enc_dt);
+    void* kp = nullptr; void* vp = nullptr;
+    if (ok && hipMalloc(&kp, bytes) == hipSuccess) k->Kp.push_back(kp); else ok = false;
+    if (ok && hipMalloc(&vp, bytes) == hipSuccess) k->VpT.push_back(vp); else ok = false;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    for (void* p : k->Kp) (void)hipFree(p);
+    for (void* p : k->VpT) (void)hipFree(p);
+    delete k;
+    return e->fail(IVG_ERR_HIP, "enc_cache_create: hipMalloc failed");
+  }
+  *out = k;
+  return IVG_OK;
+}
+
+void ivg_enc_cache_destroy(ivg_engine* e, ivg_enc_cache* c) {
+  if (!c) return;
+  if (e) (void)hipSetDevice(e->device);
+  (void)hipDeviceSynchronize();
+  for (void* p : c->Kp) (void)hipFree(p);
+  for (void* p : c->VpT) (void)hipFree(p);
+  delete c;
+}
+
+int ivg_encode_context_cached(ivg_engine* e, const void* pixels, int pixel_dtype, int B, int T, int64_t* ids_out, int64_t ids_stride,
+                              ivg_enc_cache* cache, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  IVG_TRY(check_tok(e, B, std::min(T, e->cfg.max_frames), "encode_context_cached"));
+  if (T < e->ctx || ids_stride < 257L * e->ctx) return e->fail(IVG_ERR_INVALID, "encode_context_cached: T < context_length or ids_stride < 257*ctx");
+  if (pixel_dtype != IVG_F32 && pixel_dtype != IVG_BF16) return e->fail(IVG_ERR_INVALID, "encode_context_cached: pixels are float32 or bfloat16");
+  if (!cache || cache->owner != e) return e->fail(IVG_ERR_INVALID, "encode_context_cached: null cache, or a cache of another engine");
+  if (cache->B != B)
+    return e->fail(IVG_ERR_INVALID, "encode_context_cached: cache was created for " + std::to_string(cache->B) + " trajectories, this call has " + std::to_string(B));
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
+    return r.tokenize(pixels, (DType)pixel_dtype, B, T, ids_out, ids_stride, nullptr, true, cache); });
+}
+
+int ivg_tokenize_frames(ivg_engine* e, const void* frames, int pixel_dtype, int B, int n, const ivg_enc_cache* cache, int64_t* ids_out,
+                        int64_t ids_stride, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  if (e->cfg.n_levels <= 0) return e->fail(IVG_ERR_INVALID, "tokenize_frames: engine was created without a tokenizer");
+  if (!cache || cache->owner != e) return e->fail(IVG_ERR_INVALID, "tokenize_frames: null cache, or a cache of another engine");
+  if (!cache->filled) return e->fail(IVG_ERR_INVALID, "tokenize_frames: the cache is empty (ivg_encode_context_cached fills it)");
+  if (B <= 0 || B > e->cfg.max_batch)
+    return e->fail(IVG_ERR_CAPACITY, "tokenize_frames: batch " + std::to_string(B) + " exceeds the engine's max_batch (" + std::to_string(e->cfg.max_batch) + ")");
+  if (cache->B != B)
+    return e->fail(IVG_ERR_INVALID, "tokenize_frames: cache holds " + std::to_string(cache->B) + " trajectories, this call has " + std::to_string(B));
+  if (cache->ctx != e->ctx)
+    return e->fail(IVG_ERR_INVALID, "tokenize_frames: cache was filled under context length " + std::to_string(cache->ctx) + ", " + std::to_string(e->ctx) +
+                                        " is in force (fill it again)");
+  if (n < 1) return e->fail(IVG_ERR_INVALID, "tokenize_frames: n must be at least 1");
+  if (pixel_dtype != IVG_F32 && pixel_dtype != IVG_BF16) return e->fail(IVG_ERR_INVALID, "tokenize_frames: frames are float32 or bfloat16");
+  if (!frames || !ids_out || ids_stride < 17L * n) return e->fail(IVG_ERR_INVALID, "tokenize_frames: null argument, or ids_stride < 17*n");
+  if (n > e->cfg.max_frames - e->ctx)
+    return e->fail(IVG_ERR_CAPACITY, "tokenize_frames: " + std::to_string(n) + " frames exceed max_frames - context_length (" +
+                                         std::to_string(e->cfg.max_frames - e->ctx) + "): the workspace is never grown by this call");
+  return plan_then_run(e, (hipStream_t)stream, [&](Run& r) {
+    return r.tokenize_frames(frames, (DType)pixel_dtype, B, n, cache, ids_out, ids_stride); }, false);
+}
+
+int ivg_enc_cache_select(ivg_engine* e, const ivg_enc_cache* src, const int32_t* parents, int n, ivg_enc_cache** out, ivg_stream stream) {
+  if (!e || !out || e->cfg.n_levels <= 0) return IVG_ERR_INVALID;
+  if (!src || src->owner != e || !src->filled || src->ctx <= 0) return e->fail(IVG_ERR_INVALID, "enc_cache_select: the source cache is empty (or of another engine)");
+  if (!parents) return e->fail(IVG_ERR_INVALID, "enc_cache_select: null argument");
+  for (int i = 0; i < n; ++i)
+    if (parents[i] < 0 || parents[i] >= src->B) return e->fail(IVG_ERR_INVALID, "enc_cache_select: every parent must be a row of the source cache, [0, " + std::to_string(src->B) + ")");
+  ivg_enc_cache* k = nullptr;
+  IVG_TRY(ivg_enc_cache_create(e, n, &k));
+  k->filled = true; k->ctx = src->ctx;
+  // rows are dense in the context length of the fill: ctx * side * side * C elements per trajectory, K and V^T alike
+  int rc = 0;
+  for (size_t s = 0; s < src->Kp.size() && rc == 0; ++s) {
+    const XAttW& x = e->cenc.xatt[s];
+    const long row = (long)src->ctx * x.side * x.side * x.C * (long)dtype_size(e->enc_dt);
+    rc = launch_gather_rows_by_parent(src->Kp[s], k->Kp[s], row, parents, n, (hipStream_t)stream);
+    if (rc == 0) rc = launch_gather_rows_by_parent(src->VpT[s], k->VpT[s], row, parents, n, (hipStream_t)stream);
+  }
+  if (rc) { ivg_enc_cache_destroy(e, k); return e->fail(IVG_ERR_HIP, "enc_cache_select: gather launch failed: hip error " + std::to_string(rc)); }
+  *out = k;
+  return IVG_OK;
 }
 
 void ivg_reload_switches(void) { reload_switches(); }
@@ -1285,6 +1379,9 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "kv_select_staged")) return kv_select_rows(1);
   if (name && !strcmp(name, "kv_extend_chunk_rows")) return kv_extend_rows(0);
   if (name && !strcmp(name, "kv_extend_step_rows")) return kv_extend_rows(1);
+  if (name && !strcmp(name, "enc_plain_images")) return enc_counter(0);
+  if (name && !strcmp(name, "enc_cond_images")) return enc_counter(1);
+  if (name && !strcmp(name, "enc_kv_projections")) return enc_counter(2);
   return -1;
 }
 

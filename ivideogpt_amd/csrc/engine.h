@@ -212,6 +212,17 @@ struct ivg_cache {
   int ctx = 0;                              // context length in force at fill time: rows of ctx_pixels / feat[] hold that many frames (ivg_cache_select)
 };
 
+// The conditional encoder's context, kept per trajectory: what Run::xatt_project_kv makes of the plain encoder's features at every
+// cross-attention site (order of TrunkW::xatt).  Buffers are sized for the pretrained context length; rows are dense in the context
+// length in force at fill time
+struct ivg_enc_cache {
+  const ivg_engine* owner = nullptr;
+  int B = 0;
+  std::vector<void*> Kp, VpT;               // per site: [B][kv][C] and [B][C][kv], kv = ctx * side * side, encode dtype
+  bool filled = false;
+  int ctx = 0;                              // context length in force at fill time
+};
+
 struct ivg_engine {
   ivg_config cfg;
   int device = 0;

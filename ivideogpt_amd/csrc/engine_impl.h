@@ -82,10 +82,13 @@ struct Run {
   int xatt_project_kv(DType dt, const void* feat, int B, const XAttW& x, void* Kp, void* VpT);
   int cross_attention(DType dt, const void* z, int B, int F, const XAttW& x, const void* Kp, const void* VpT, void* out);
   int encoder_trunk(const TrunkW& w, const void* pixels, DType pix_dt, int B, int per, int T_total, int t0,
-                    std::vector<Feature>* keep, const std::vector<Feature>* cond, void* latent);
+                    std::vector<Feature>* keep, const std::vector<Feature>* cond, void* latent,
+                    const ivg_enc_cache* kept = nullptr /* conditional encoder on kept K / V projections (cond is not read) */);
   int decoder_trunk(const TrunkW& w, const void* z, int B, int per, int T_total, int t0, std::vector<Feature>* keep,
                     const std::vector<Feature>* cond, void* out_pixels, DType out_dt);
-  int tokenize(const void* pixels, DType pix_dt, int B, int T, int64_t* ids, int64_t ids_stride, int64_t* labels, bool ctx_only);
+  int tokenize(const void* pixels, DType pix_dt, int B, int T, int64_t* ids, int64_t ids_stride, int64_t* labels, bool ctx_only,
+               ivg_enc_cache* fill = nullptr /* context-only call: also project the context features into this cache */);
+  int tokenize_frames(const void* frames, DType pix_dt, int B, int n, const ivg_enc_cache* cache, int64_t* ids, int64_t ids_stride);
   int detokenize(const int64_t* ids, int B, int F, void* out_pixels, DType out_dt, ivg_cache* cache, int cache_mode,
                  int group = 1 /* > 1: consecutive rows share their context (decoded / projected once per group) */);
 
@@ -101,6 +104,7 @@ struct Run {
 };
 
 size_t dtype_size(DType d);
+long long enc_counter(int which);   // 0: images through the plain encoder trunk, 1: through the conditional one, 2: xatt_project_kv calls for an encoder
 int build_tokenizer(ivg_engine* e);
 int build_transformer(ivg_engine* e);
 size_t gen_buffer_bytes(const ivg_engine* e);

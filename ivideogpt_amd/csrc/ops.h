@@ -48,6 +48,8 @@ int launch_gather_rows(const int64_t* ids, const TokMap& map, const float* E, vo
 int launch_unpatchify(const void* q, void* out, DType dt, int M, int np, int C, int p, hipStream_t st);
 // special tokens (scf / sdf slots) and labels (-100 over the context part)                    (compressive_vq_model.py:205-218)
 int launch_finish_tokens(int64_t* ids, long stride, int64_t* labels, int B, int L, int ctx, int64_t scf, int64_t sdf, hipStream_t st);
+// ids[b][17 i + 16] = sdf for i < n, rows `stride` apart: the separators of n frame slots (ivg_tokenize_frames)
+int launch_sdf_columns(int64_t* ids, long stride, int B, int n, int64_t sdf, hipStream_t st);
 
 // ---- llama_ops.hip
 struct StepState {  // device-resident per-generate state (so one captured step graph can be replayed)

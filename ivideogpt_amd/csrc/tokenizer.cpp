@@ -14,6 +14,8 @@
 //     through batch strides of 0;
 //   * nearest-x2 upsampling, the stride-2 right/bottom zero pad and 4x4 patchify are index arithmetic
 //     inside the implicit-GEMM gather, never materialised.
+#include <atomic>
+
 #include "engine_impl.h"
 #include "switches.h"
 
@@ -310,9 +312,14 @@ int Run::cross_attention(DType dt, const void* z, int B, int F, const XAttW& x, 
 // cond != null: conditional encoder, cross-attending to cond features (index = level + 1).
 // keep != null: plain encoder; keep[i] (i = feature index) receives persistent copies of the features that
 // a conditional pass will need.  latent: [N,16,16,latent] in dt.
+static std::atomic<long long> g_enc_counter[3] = {{0}, {0}, {0}};
+long long enc_counter(int which) { return g_enc_counter[which].load(std::memory_order_relaxed); }
+
 int Run::encoder_trunk(const TrunkW& w, const void* pixels, DType pix_dt, int B, int per, int T_total, int t0,
-                       std::vector<Feature>* keep, const std::vector<Feature>* cond, void* latent) {
+                       std::vector<Feature>* keep, const std::vector<Feature>* cond, void* latent, const ivg_enc_cache* kept) {
   Run& R = *this;
+  const bool xatt = cond || kept;
+  if (!planning) g_enc_counter[xatt ? 1 : 0].fetch_add((long long)B * per, std::memory_order_relaxed);
   const DType dt = e->enc_dt;
   const ivg_config& c = e->cfg;
   const int N = B * per, nl = c.n_levels;
@@ -329,7 +336,10 @@ int Run::encoder_trunk(const TrunkW& w, const void* pixels, DType pix_dt, int B,
   const size_t m = e->ws.mark();
   // cross-attention K/V of every site first (persist for the whole trunk)
   std::vector<void*> Kp, Vp;
-  if (cond) {
+  if (kept) {   // ... or those an earlier call kept (ivg_encode_context_cached): nothing is projected
+    Kp = kept->Kp; Vp = kept->VpT;
+    if (Kp.size() != w.xatt.size()) return e->fail(IVG_ERR_INVALID, "encoder cache layout mismatch");
+  } else if (cond) {
     int s = side, k = 0;
     for (int i = 0; i < nl; ++i) {
       if (i != nl - 1) s /= 2;
@@ -339,6 +349,7 @@ int Run::encoder_trunk(const TrunkW& w, const void* pixels, DType pix_dt, int B,
         void* kp = e->ws.alloc((size_t)B * kv * x.C * esz(dt));
         void* vp = e->ws.alloc((size_t)B * kv * x.C * esz(dt));
         IVG_TRY(xatt_project_kv(dt, (*cond)[i + 1].p, B, x, kp, vp));
+        if (!planning) g_enc_counter[2].fetch_add(1, std::memory_order_relaxed);
         Kp.push_back(kp); Vp.push_back(vp);
       }
     }
@@ -368,7 +379,7 @@ int Run::encoder_trunk(const TrunkW& w, const void* pixels, DType pix_dt, int B,
       side /= 2;
     }
     const int C = c.block_out_channels[i];
-    if (cond && side <= c.max_att_resolution) {
+    if (xatt && side <= c.max_att_resolution) {
       IVG_TRY(cross_attention(dt, a, B, per, w.xatt[k], Kp[k], Vp[k], b));
       std::swap(a, b); std::swap(sa, sb); sa.chunks = 0;
       ++k;
@@ -396,7 +407,8 @@ static void encoder_feature_plan(const ivg_config& c, std::vector<Feature>& f) {
   }
 }
 
-int Run::tokenize(const void* pixels, DType pix_dt, int B, int T, int64_t* ids, int64_t ids_stride, int64_t* labels, bool ctx_only) {
+int Run::tokenize(const void* pixels, DType pix_dt, int B, int T, int64_t* ids, int64_t ids_stride, int64_t* labels, bool ctx_only,
+                  ivg_enc_cache* fill) {
   Run& R = *this;
   x3 = false;   // bit-exact ids: the exact fp32 chain, always
   const ivg_config& c = e->cfg;
@@ -406,12 +418,24 @@ int Run::tokenize(const void* pixels, DType pix_dt, int B, int T, int64_t* ids, 
   const size_t m = e->ws.mark();
   std::vector<Feature> feats;
   encoder_feature_plan(c, feats);
-  if (!ctx_only)
+  const bool keep_feats = !ctx_only || fill;
+  if (keep_feats)
     for (auto& f : feats)
       if (f.side) f.p = e->ws.alloc((size_t)B * ctx * f.side * f.side * f.C * esz(dt));
   const int N = B * ctx;
   void* h = e->ws.alloc((size_t)N * 256 * lat * esz(dt));
-  IVG_TRY(encoder_trunk(e->enc, pixels, pix_dt, B, ctx, T, 0, ctx_only ? nullptr : &feats, nullptr, h));
+  IVG_TRY(encoder_trunk(e->enc, pixels, pix_dt, B, ctx, T, 0, keep_feats ? &feats : nullptr, nullptr, h));
+  if (fill) {   // the conditional encoder's K / V projections of this context, per site (the order encoder_trunk projects them in)
+    size_t k = 0;
+    for (int i = 0; i < c.n_levels; ++i) {
+      if (!feats[i + 1].side) continue;
+      if (k >= e->cenc.xatt.size() || (!planning && k >= fill->Kp.size())) return e->fail(IVG_ERR_INVALID, "encode_context_cached: cache layout mismatch");
+      IVG_TRY(xatt_project_kv(dt, feats[i + 1].p, B, e->cenc.xatt[k], planning ? nullptr : fill->Kp[k], planning ? nullptr : fill->VpT[k]));
+      if (!planning) g_enc_counter[2].fetch_add(1, std::memory_order_relaxed);
+      ++k;
+    }
+    if (!planning) { fill->filled = true; fill->ctx = ctx; }
+  }
   float* hq = (float*)e->ws.alloc((size_t)N * 256 * dim * sizeof(float));
   IVG_TRY(conv(dt, h, N, 16, 16, e->quant_conv, hq, 1, 0, nullptr, 0, 1));
   if (!planning) {
@@ -434,6 +458,30 @@ int Run::tokenize(const void* pixels, DType pix_dt, int B, int T, int64_t* ids, 
   if (!planning) {
     if (ids_stride != L && labels) return e->fail(IVG_ERR_INVALID, "labels need a dense token matrix");
     CK(launch_finish_tokens(ids, ids_stride, labels, B, L, ctx, nvq + ndyn, nvq + ndyn + 1, st));
+  }
+  e->ws.reset(m);
+  return 0;
+}
+
+// The dyn tokens of n observed frames per trajectory against a kept encoder context (ivg_tokenize_frames): the conditional trunk of
+// tokenize over B * n frames with the cache's K / V projections -- no plain encoder, no projection.  frames (B, n, 3, H, W);
+// ids columns 17 i + j (j < 16): dyn token j of frame i, column 17 i + 16: sdf.
+int Run::tokenize_frames(const void* frames, DType pix_dt, int B, int n, const ivg_enc_cache* cache, int64_t* ids, int64_t ids_stride) {
+  Run& R = *this;
+  x3 = false;
+  const ivg_config& c = e->cfg;
+  const DType dt = e->enc_dt;
+  const int lat = c.latent_channels, dim = c.vq_embed_dim, M = B * n;
+  const int64_t nvq = c.num_vq_embeddings, ndyn = c.num_dyn_embeddings;
+  const size_t m = e->ws.mark();
+  void* d = e->ws.alloc((size_t)M * 256 * lat * esz(dt));
+  IVG_TRY(encoder_trunk(e->cenc, frames, pix_dt, B, n, n, 0, nullptr, nullptr, d, cache));
+  float* dq = (float*)e->ws.alloc((size_t)M * 16 * dim * sizeof(float));
+  IVG_TRY(conv(dt, d, M, 16, 16, e->quant_linear, dq, c.patch_size, 0, nullptr, 0, 1));
+  if (!planning) {
+    TokMap mp{16, n, ids_stride, 0, 17};
+    CK(launch_vq_argmin(dq, e->cb_d, e->ee_d, ids, mp, nvq, M * 16, (int)ndyn, st));
+    CK(launch_sdf_columns(ids, ids_stride, B, n, nvq + ndyn + 1, st));
   }
   e->ws.reset(m);
   return 0;

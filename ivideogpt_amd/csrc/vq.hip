@@ -207,4 +207,17 @@ int launch_finish_tokens(int64_t* ids, long stride, int64_t* labels, int B, int 
   return (int)hipGetLastError();
 }
 
+// the sdf that closes each of n frame slots of 17 tokens on a strided row (ivg_tokenize_frames): ids[b][17 i + 16] = sdf
+__global__ __launch_bounds__(256) void sdf_columns_kernel(int64_t* __restrict__ ids, long stride, int B, int n, int64_t sdf) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * n) return;
+  ids[(i / n) * stride + (i % n) * 17 + 16] = sdf;
+}
+
+int launch_sdf_columns(int64_t* ids, long stride, int B, int n, int64_t sdf, hipStream_t st) {
+  if (B <= 0 || n <= 0) return 0;
+  hipLaunchKernelGGL(sdf_columns_kernel, dim3(cdiv((long)B * n, 256)), dim3(256), 0, st, ids, stride, B, n, sdf);
+  return (int)hipGetLastError();
+}
+
 }  // namespace ivg

@@ -94,6 +94,7 @@ class Engine:
         # streams land on the SAME hardware queue do not overlap at all (bench.py --lanes: 4,230 instead of 5,050 frames/s)
         self._stream = None
         self._caches = set()   # live detokenize caches (device memory owned here: released with the engine)
+        self._enc_caches = set()   # live encoder context caches, likewise
         self._clamp_out = False
         self._temperature = 1.0
         self._top_p = 1.0
@@ -104,6 +105,9 @@ class Engine:
             for c in list(getattr(self, "_caches", ())):
                 self.lib.ivg_cache_destroy(self.h, C.c_void_p(c))
             self._caches = set()
+            for c in list(getattr(self, "_enc_caches", ())):
+                self.lib.ivg_enc_cache_destroy(self.h, C.c_void_p(c))
+            self._enc_caches = set()
             self.lib.ivg_destroy(self.h)
             self.h = None
 
@@ -233,6 +237,42 @@ class Engine:
             self.check(self.lib.ivg_encode_context(self.h, _ptr(pixels), dtype_code(pixels.dtype), B, T, _ptr(ids), ids.stride(0), s),
                        "encode_context")
             pixels.record_stream(self._run); ids.record_stream(self._run)
+
+    def enc_cache_create(self, B):
+        h = C.c_void_p()
+        self.check(self.lib.ivg_enc_cache_create(self.h, int(B), C.byref(h)), "enc_cache_create")
+        self._enc_caches.add(h.value)
+        return h
+
+    def enc_cache_destroy(self, h):
+        if self.h is not None and h.value in self._enc_caches:   # (already released when the engine was closed first)
+            self._enc_caches.discard(h.value)
+            self.lib.ivg_enc_cache_destroy(self.h, h)
+
+    def enc_cache_select(self, h, parents):
+        """``ivg_enc_cache_select``: a new encoder cache whose row i is row ``parents[i]`` (host integers) of cache ``h``; ``h`` is unchanged."""
+        p = np.ascontiguousarray(parents, dtype=np.int32)
+        out = C.c_void_p()
+        with self.stream() as s:
+            self.check(self.lib.ivg_enc_cache_select(self.h, h, p.ctypes.data_as(C.c_void_p), int(p.size), C.byref(out), s), "enc_cache_select")
+        self._enc_caches.add(out.value)
+        return out
+
+    def encode_context_cached(self, pixels, ids, cache):
+        """``ivg_encode_context_cached``: ``encode_context`` that also fills the encoder cache ``cache`` (a handle of ``enc_cache_create``)."""
+        B, T = pixels.shape[:2]
+        with self.stream() as s:
+            self.check(self.lib.ivg_encode_context_cached(self.h, _ptr(pixels), dtype_code(pixels.dtype), B, T, _ptr(ids), ids.stride(0), cache, s),
+                       "encode_context_cached")
+            self._record(pixels, ids)
+
+    def tokenize_frames(self, frames, cache, ids):
+        """``ivg_tokenize_frames``: ``frames`` (B, n, 3, H, W) against the filled encoder cache -> columns [0, 17 n) of ``ids`` (B, >= 17 n)."""
+        B, n = frames.shape[:2]
+        with self.stream() as s:
+            self.check(self.lib.ivg_tokenize_frames(self.h, _ptr(frames), dtype_code(frames.dtype), B, n, cache, _ptr(ids), ids.stride(0), s),
+                       "tokenize_frames")
+            self._record(frames, ids)
 
     def detokenize(self, ids, F, out, cache=None, cache_mode=0, clamp=False):
         if clamp != self._clamp_out:   # clamp(0, 1) in the epilogue of the decoders' last convolution (engine state, rarely toggled)

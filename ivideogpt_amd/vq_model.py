@@ -6,8 +6,9 @@ Same names, argument meaning and error behaviour as the reference class:
 ``.context_length``, ``.num_vq_embeddings``, ``.num_dyn_embeddings``, ``set_context_length``,
 ``tokenize(pixel_values, context_length) -> (indices, labels)``,
 ``detokenize(indices, context_length, cache=None, return_cache=False)``.
-``encode_context`` is the one addition: the context-only path every prediction caller wants
-(predict.py:53-54 tokenizes the whole clip and then drops all future-frame tokens).
+``encode_context`` is an addition: the context-only path every prediction caller wants
+(predict.py:53-54 tokenizes the whole clip and then drops all future-frame tokens).  So are ``encode_context(...,
+return_cache=True)`` / ``tokenize_frames`` / ``EncodeCache``: the tokens of frames observed later, against a context encoded once.
 
 Only tensor plumbing and checkpoint I/O happen here; every FLOP is in libivg (HIP).
 """
@@ -46,6 +47,47 @@ class DetokenizeCache:
     def __del__(self):
         try:
             self.engine.cache_destroy(self.handle)
+        except Exception:
+            pass
+
+
+def frame_token_columns(context_length, i):
+    """Columns ``(first, stop)`` of a ``tokenize`` row that hold the 16 dyn tokens of future frame ``i`` (compressive_vq_model.py:205-215:
+    ``ctx`` blocks of 256 context tokens + scf, the last scf slot holding the first sdf; then per future frame 16 dyn tokens + sdf, the
+    very last sdf cut off).  Column ``first - 1`` is the sdf in front of the frame; column ``stop`` the one behind it, which exists in
+    the row when another future frame follows."""
+    first = CTX_TOKENS * context_length + DYN_TOKENS * i
+    return first, first + DYN_TOKENS - 1
+
+
+class EncodeCache:
+    """The encoder's context cache of ``encode_context(..., return_cache=True)`` (include/ivg.h ivg_enc_cache): the conditional encoder's
+    cross-attention K / V projections of B contexts, which ``tokenize_frames`` tokenizes observed frames against.  It keeps a reference
+    to the context pixels it was filled from: when the tokenizer's engine is rebuilt (the batch or clip length grew) it is filled again
+    from them on its next use instead of failing in the middle of an episode."""
+
+    def __init__(self, engine, B, context_length, pixels, handle):
+        # handle: of engine.enc_cache_create (the engine owns the device memory), or None: to be filled from `pixels` on first use
+        self.engine, self.B, self.context_length, self.pixels, self.handle = engine, B, context_length, pixels, handle
+
+    def select(self, parents):
+        """A NEW cache whose row i is row ``parents[i]`` of this one (ivg_enc_cache_select; this cache is unchanged), as
+        ``DetokenizeCache.select``.  ValueError for an index outside this cache's rows or more rows than the engine's batch."""
+        from .transformer import normalize_parents
+        from ._lib import IvgError
+        p = normalize_parents(parents, self.B)
+        px = self.pixels[torch.from_numpy(p).long().to(self.pixels.device)]
+        if self.handle is None or self.engine.h is None:   # the engine is gone: the new cache is filled from its pixels on first use, like this one
+            return EncodeCache(self.engine, int(p.size), self.context_length, px, None)
+        try:
+            return EncodeCache(self.engine, int(p.size), self.context_length, px, self.engine.enc_cache_select(self.handle, p))
+        except (AssertionError, IvgError) as err:
+            raise ValueError(f"EncodeCache.select: {err}") from None
+
+    def __del__(self):
+        try:
+            if self.handle is not None:
+                self.engine.enc_cache_destroy(self.handle)
         except Exception:
             pass
 
@@ -214,15 +256,50 @@ class CompressiveVQModel:
         return ids, labels
 
     @torch.no_grad()
-    def encode_context(self, pixel_values, context_length=0):
+    def encode_context(self, pixel_values, context_length=0, return_cache=False):
         """(B, >=ctx, 3, H, W) -> int64 (B, 257*ctx): context tokens, scf separators and the trailing sdf --
-        exactly ``tokenize(...)[0][:, :257*ctx]`` without encoding any future frame."""
+        exactly ``tokenize(...)[0][:, :257*ctx]`` without encoding any future frame.
+        ``return_cache=True``: -> (ids, EncodeCache), the same ids and the encoder's context cache ``tokenize_frames`` works on."""
         assert context_length == self.context_length
         px = self._pixels(pixel_values)
         B, T = px.shape[:2]
         assert T >= context_length
         ids = torch.empty(B, CTX_TOKENS * context_length, dtype=torch.int64, device=self.device)
-        self._ensure(B, max(T, context_length + 1)).encode_context(px, ids)
+        eng = self._ensure(B, max(T, context_length + 1))
+        if not return_cache:
+            eng.encode_context(px, ids)
+            return ids
+        cache = EncodeCache(eng, B, context_length, px[:, :context_length], eng.enc_cache_create(B))
+        eng.encode_context_cached(px, ids, cache.handle)
+        return ids, cache
+
+    @torch.no_grad()
+    def tokenize_frames(self, frames, cache):
+        """The tokens of observed frames against a kept context: ``frames`` (B, n, 3, H, W), ``cache`` an ``EncodeCache`` of the same B
+        -> int64 (B, 17 n); columns ``17 i .. 17 i + 15`` are the dyn tokens of frame i, column ``17 i + 16`` is sdf.  For the first n
+        future frames of a clip that is ``tokenize(clip)[0][:, 257*ctx : 257*ctx + 17 n - 1]`` plus the sdf the next frame's slot
+        needs -- what a prompt ending in sdf is extended by.  Every frame is encoded on its own against the cached cross-attention
+        K / V (libivg ``ivg_tokenize_frames``): no context frame is encoded again."""
+        if not isinstance(cache, EncodeCache):
+            raise AssertionError("tokenize_frames: cache must be the EncodeCache of encode_context(..., return_cache=True)")
+        px = self._pixels(frames)
+        B, n = px.shape[:2]
+        if cache.B != B:
+            raise AssertionError("tokenize_frames: cache was filled for another batch size")
+        if cache.context_length != self.context_length:
+            raise AssertionError("tokenize_frames: cache was filled under another context length (encode the context again)")
+        assert n >= 1
+        eng = self._ensure(B, self.context_length + n)
+        if cache.handle is None or cache.engine is not eng or cache.engine.h is None:
+            # the engine was rebuilt since the cache was filled (batch or clip length grew): the projections are gone with it -- fill a
+            # cache of the new engine from the kept context pixels instead of failing mid-episode
+            if cache.handle is not None:
+                cache.engine.enc_cache_destroy(cache.handle)   # (nothing left to release when that engine was closed)
+            cache.engine, cache.handle = eng, eng.enc_cache_create(B)
+            eng.encode_context_cached(cache.pixels.contiguous(), torch.empty(B, CTX_TOKENS * self.context_length, dtype=torch.int64, device=self.device),
+                                      cache.handle)
+        ids = torch.empty(B, DYN_TOKENS * n, dtype=torch.int64, device=self.device)
+        eng.tokenize_frames(px, cache.handle, ids)
         return ids
 
     @torch.no_grad()

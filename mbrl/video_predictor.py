@@ -10,7 +10,10 @@ output_hidden_states=True)``, reward = ``reward_linear(hidden_states[-1][-1])``,
 embedded and appended, the new frame decoded with the detokenizer cache and pushed onto the 3-frame stack.  What differs from
 the reference is inside the engine: from the second step on ``generate`` recognises (device-side comparison with the inputs it
 kept) that the KV cache already holds everything but the last embedding and feeds only that row -- 17 cached decode steps per
-environment step instead of a prefill of the grown prompt."""
+environment step instead of a prefill of the grown prompt.
+
+Not in the reference: ``rollout_actions`` (open-loop plans in three calls) and ``track`` -> ``TrackedEpisode``, the closed loop of a
+caller that acts, observes and re-plans, on the encoder's context cache and the transformer's kept cache."""
 import os
 import sys
 
@@ -80,6 +83,127 @@ def load_models(args):
         else:
             model.load_state_dict(state_dict, strict=True)
     return model, tokenizer
+
+
+class TrackedEpisode:
+    """The closed loop of ``VideoPredictor.track``: the model follows an episode as it is OBSERVED.  Both contexts are kept on the
+    device -- the encoder's (``EncodeCache``: no context frame is encoded again) and the transformer's (the kept K / V cache: no
+    prompt pass) -- so a control step costs one conditional-encoder pass over the new frame plus 17 teacher-forced positions, and a
+    ``plan`` fans candidates out of the very cache ``observe`` extends.  Existing primitives only; no arithmetic of its own.
+
+    ``tokens`` (B, 257*ctx + 17*steps): the context tokens and the tokens of the ``steps`` frames observed since, ending in the sdf
+    of the next frame's slot.  ``table`` (B, ctx - 1 + max_steps, A): the actions taken, row ``i + ctx - 1`` on the i-th sdf slot
+    (rows not yet taken are zero).  ``reanchors``: how often the positions were used up and the episode was anchored again."""
+
+    def __init__(self, predictor, obs, max_steps=None, on_full="reanchor"):
+        if on_full not in ("reanchor", "raise"):
+            raise ValueError(f"track: on_full must be 'reanchor' or 'raise', not {on_full!r}")
+        self.p, self.on_full = predictor, on_full
+        ctx, llm = predictor.context_length, predictor.model.llm
+        room = ((llm._max_seq or llm._cfg["max_position_embeddings"]) + 1 - 257 * ctx) // 17   # observe needs 257*ctx + 17*steps - 1 kept positions
+        if room < 1:
+            raise ValueError("track: max_position_embeddings leaves no room for a frame after the context")
+        self.max_steps = room if max_steps is None else min(int(max_steps), room)
+        if self.max_steps < 1:
+            raise ValueError("track: max_steps must be at least 1")
+        obs = obs.to(predictor.device).float() / 255.
+        self.stack = list(torch.chunk(obs, 3, dim=1))                          # frame_stack = 3
+        self.reanchors = 0
+        self._anchor()
+
+    def _anchor(self):
+        """The last ``ctx`` frames of the stack become the context: a fresh encoder cache, fresh tokens and table, a fresh kept cache."""
+        p, ctx = self.p, self.p.context_length
+        self.tokens, self.enc_cache = p.tokenizer.encode_context(torch.stack(self.stack[-ctx:], dim=1), ctx, return_cache=True)
+        B = self.tokens.shape[0]
+        self.table = torch.zeros(B, ctx - 1 + self.max_steps, p.model.action_dim, dtype=torch.float32, device=p.device)
+        self.steps = 0
+        self._establish()
+
+    def _establish(self, rows=None):
+        """The transformer's kept cache at ``tokens[:, :-1]``: a one-token ``generate`` (the prompt pass), then a pure rewind in front
+        of the last sdf slot, whose action is not known yet.  ``rows``: the batch the engine must hold (``plan``'s candidates), with one
+        action row more than the table has for the forced sdf behind a plan's last frame."""
+        model, L0 = self.p.model, self.tokens.shape[1]
+        model.llm._ensure(max(rows or 0, self.tokens.shape[0]), self.table.shape[1] + 1)
+        model.generate(self.tokens, do_sample=False, max_new_tokens=1, action=self.table)
+        model.extend_kept_cache(self.tokens, action=self.table, keep=L0 - 1)
+
+    @property
+    def batch(self):
+        return self.tokens.shape[0]
+
+    @torch.no_grad()
+    def observe(self, frame, action):
+        """The environment's answer to ``action``: ``frame`` [B, 3, H, W] in 0..255, ``action`` [B, A].  The frame is tokenized against
+        the encoder cache and teacher-forced onto the kept cache (``extend_kept_cache`` with the action on its sdf slot).
+        -> float32 (B,): the model's surprise at that frame, the sum of its 16 token NLLs (nats).  ``tokens`` and ``steps`` advance.
+        When the positions are used up, the last ``ctx`` frames observed SO FAR become the new context first (real frames: the model's
+        own episode start; ``reanchors`` counts it) and this frame is its first step -- or, with ``on_full="raise"``, RuntimeError
+        with the session as it was."""
+        p, ctx = self.p, self.p.context_length
+        if self.steps >= self.max_steps:
+            if self.on_full == "raise":
+                raise RuntimeError(f"track: the {self.max_steps} steps the positions allow are used up (on_full='raise')")
+            self._anchor()
+            self.reanchors += 1
+        frame = frame.to(p.device).float() / 255.
+        dyn = p.tokenizer.tokenize_frames(frame[:, None], self.enc_cache)      # (B, 17): 16 dyn tokens + the next slot's sdf
+        table = self.table.clone()
+        table[:, self.steps + ctx - 1] = action.to(p.device).float()
+        tokens = torch.cat([self.tokens, dyn], 1)
+        nll = p.model.extend_kept_cache(tokens, action=table, keep=self.tokens.shape[1] - 1, return_nll=True)   # (B, 17); column 16: the forced sdf
+        self.tokens, self.table, self.steps = tokens, table, self.steps + 1
+        self.stack = self.stack[1:] + [frame]
+        return nll[:, :TOKENS_PER_DYN].sum(1)
+
+    @torch.no_grad()
+    def plan(self, plans, samples=1, return_uncertainty=False, uniforms=None, generator=None):
+        """Imagines ``samples`` action plans per tracked history: ``plans`` [B * samples, horizon, A], rows ``b * samples + k`` the
+        candidates of history b (``rollout_actions``' order, also of ``uniforms`` [B * samples, 17 * horizon - 1] and every result).
+        One ``fan_out`` of the kept cache and one ``detokenize`` of the imagined frames; the kept cache is afterwards what it was.
+        -> (obss [B * samples, horizon + 1, 9, H, W], actions [B * samples, horizon + 1, A], rewards [B * samples, horizon + 1, 1])
+        and, with ``return_uncertainty``, uncertainty [B * samples, horizon + 1, 1]: ``rollout_actions``' results, step 0 being the
+        observed stack."""
+        p, ctx, model, k = self.p, self.p.context_length, self.p.model, int(samples)
+        B, horizon = self.batch, plans.shape[1]
+        assert k >= 1 and plans.shape[0] == B * k, "plans must hold `samples` consecutive rows per tracked history"
+        if self.steps + horizon > self.max_steps:
+            raise ValueError(f"plan: {self.steps} observed + {horizon} imagined frames exceed the {self.max_steps} the positions allow")
+        if B * k > model.llm._engine.max_batch:   # the engine is rebuilt for the candidates: one prompt pass brings the kept cache back
+            self._establish(rows=B * k)
+        act = plans.to(p.device).float()
+        table = self.table.repeat_interleave(k, 0)
+        table[:, self.steps + ctx - 1:self.steps + ctx - 1 + horizon] = act
+        L0 = self.tokens.shape[1]
+        tokens, hidden, *scores = model.fan_out(self.tokens, k, action=table, do_sample=True, temperature=1.0, top_k=100,
+                                                max_new_tokens=17 * horizon - 1, uniforms=uniforms, generator=generator,
+                                                output_frame_hidden_states=True, output_token_scores=return_uncertainty)
+        rewards = model.reward_linear(hidden).squeeze(-1)                      # (B * samples, horizon)
+        # every frame is decoded against the context alone: the imagined frames directly behind the context tokens
+        clip = p.tokenizer.detokenize(torch.cat([tokens[:, :257 * ctx], tokens[:, L0:]], 1), ctx)
+        frames = [f.repeat_interleave(k, 0) if k > 1 else f for f in self.stack] + list(clip[:, ctx:].clamp(0.0, 1.0).unbind(1))
+        obss = torch.stack([torch.cat(frames[s:s + 3], dim=1) for s in range(horizon + 1)], 1).float()
+        actions = torch.cat([torch.zeros_like(act[:, :1]), act], 1).float()
+        rewards = torch.cat([torch.zeros_like(rewards[:, :1]), rewards], 1).unsqueeze(-1)
+        if p.symlog:
+            rewards = symexp(rewards)
+        if return_uncertainty:
+            unc = scores[0].per_frame()[1]                                     # (B * samples, horizon)
+            return obss, actions, rewards.float(), torch.cat([torch.zeros_like(unc[:, :1]), unc], 1).unsqueeze(-1).float()
+        return obss, actions, rewards.float()
+
+    def select(self, parents):
+        """Row i of the session becomes what row ``parents[i]`` was (particle resampling, dropping finished environments): the kept
+        cache (``select_kept_cache``), the encoder cache (``EncodeCache.select``), the tokens, the action table and the frame stack."""
+        from ivideogpt_amd.transformer import normalize_parents
+        q = normalize_parents(parents, self.batch)
+        self.p.model.select_kept_cache(q)
+        self.enc_cache = self.enc_cache.select(q)
+        idx = torch.from_numpy(q).to(self.p.device, torch.int64)
+        self.tokens, self.table = self.tokens[idx].contiguous(), self.table[idx].contiguous()
+        self.stack = [f[idx] for f in self.stack]
+        return self
 
 
 class VideoPredictor:
@@ -169,6 +293,17 @@ class VideoPredictor:
             uncertainty = torch.stack([torch.zeros_like(trace["unc"][0])] + trace["unc"], 1).float()
             return obss, actions, torch.stack(rewards, 1).float(), uncertainty
         return obss, actions, torch.stack(rewards, 1).float()
+
+    @torch.no_grad()
+    def track(self, obs, max_steps=None, on_full="reanchor"):
+        """Starts a closed-loop session (act, observe, re-plan: MPC, MBRL on real transitions, monitoring the model's surprise) at
+        ``obs`` [B, 9, H, W] in 0..255, as for ``rollout``: its last ``ctx`` frames are encoded once, with the encoder's context cache
+        kept, and the transformer's kept cache is established at the context.  -> ``TrackedEpisode``: ``plan`` imagines candidate action
+        sequences from where the episode stands, ``observe`` moves it on by the frame that was really seen and returns the model's
+        surprise, ``select`` resamples its rows.  ``max_steps``: frames to observe before the session anchors itself again at the
+        last ``ctx`` observed frames (default and upper bound: what ``max_position_embeddings`` allows); ``on_full="raise"``:
+        RuntimeError instead.  The model and tokenizer objects serve one session at a time."""
+        return TrackedEpisode(self, obs, max_steps=max_steps, on_full=on_full)
 
     @torch.no_grad()
     def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None, return_uncertainty=False):
