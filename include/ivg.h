@@ -327,6 +327,49 @@ int ivg_generate_continue(ivg_engine* e, const int64_t* prompt, int64_t prompt_s
  * a row is). */
 int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream stream);
 
+/* Set the kept cache aside and bring it back (HF: copy.deepcopy(past_key_values)): a snapshot is a caller-held copy of everything
+ * ivg_kv_select gathers, in device memory of its own.  For callers whose engine must do something else between two steps of a
+ * step-wise rollout -- imagine a batch beside a tracked session, serve several sessions, grow its batch -- and then go on with
+ * ivg_generate_continue / ivg_kv_extend / ivg_generate_fanout instead of a prompt pass over the whole prefix; and for checkpointing a
+ * node of a search that is left along another path than a rewind walks back.
+ *
+ * ivg_kv_snapshot_create.  Precondition: that of ivg_kv_select (the engine holds a kept cache).  Allocates exactly the kept state's
+ * size -- [layers * 2][B][heads]{len * row_bytes_a | len * row_bytes_b} of the K / V slabs in the cache's own format (native bf16 /
+ * fp32, both planes of the 24-bit format, FP8 bytes), then rows [0, len) of the embeddings snapshot of an embeds call, columns [0, len]
+ * of the id rows and the rows of the kept action table, each dense: the layout depends neither on the engine's cache chunk nor on its
+ * cache length -- and enqueues the copies on `stream`.  Recorded on the host: the kept state (len, B, built from ids or embeds, act_T,
+ * ctx); layers, heads, head_dim, hidden size, action_dim, llm dtype and K / V format; the FP8 scales in force, by value (the two scalars
+ * or the whole table); the device; and a weights tag, the device addresses of the packed embed_tokens and lm_head tensors the engine
+ * was created with.  No host synchronisation beyond what hipMalloc implies; the live kept cache is unchanged.
+ *   IVG_ERR_INVALID   no kept cache (as ivg_kv_select); an engine without a transformer; out == NULL
+ *   IVG_ERR_HIP       the allocation failed: nothing is leaked, *out is not written
+ * The snapshot belongs to the caller and outlives the engine: ivg_kv_snapshot_destroy takes no engine (its hipFree waits for the device).
+ *
+ * ivg_kv_snapshot_restore.  Afterwards the engine's kept cache holds n trajectories at the snapshot's length, row i = snapshot row
+ * parents[i] (HOST array; NULL: the identity over the snapshot's rows, n is ignored) -- duplicates, drops, any order, more rows than
+ * the snapshot has, up to the cache chunk -- and the kept host state is the snapshot's with B = n.  The kept-cache entries then accept
+ * a prompt / actions / embeds gathered by the same parents exactly as after ivg_kv_select, and refuse anything else: the on-device
+ * verification stays the guard.  Cache rows >= n, positions >= len and id columns beyond len are neither read nor written; no captured
+ * step graph is invalidated.  The snapshot is const: it is restored any number of times, into the engine that made it or into another
+ * engine over the SAME weights (the engine a model rebuilds for a larger batch, a second lane).  Enqueued on `stream`, which must be
+ * ordered after the create's; no host synchronisation (the first restore of an embeds snapshot into an engine that never ran an embeds
+ * call allocates that engine's embeddings snapshot).
+ * Refusals, each before anything is launched or written -- the engine's kept cache stays usable exactly as it was:
+ *   IVG_ERR_INVALID   a null snapshot; n <= 0 with parents != NULL; a parent outside the snapshot's rows; another device; any recorded
+ *                     geometry, dtype or format that differs from the engine's; FP8 scales in force that differ from the recorded ones in
+ *                     any bit; another weights tag; an engine without a transformer
+ *   IVG_ERR_CAPACITY  n above the cache chunk; the snapshot's length beyond this engine's cache and id rows; its action table longer
+ *                     than max_frames
+ * ivg_kv_snapshot_info: out[IVG_KV_SNAPSHOT_INFO_INTS] = rows, length, device bytes, built from embeds (0 / 1), act_T, ctx, K / V format
+ * (enum ivg_kv_format; 2: the 24-bit planes), device.  ivg_debug_counter("kv_snapshot_rows_saved" / "kv_snapshot_rows_restored") count
+ * trajectory rows. */
+typedef struct ivg_kv_snapshot ivg_kv_snapshot;
+int ivg_kv_snapshot_create(ivg_engine* e, ivg_kv_snapshot** out, ivg_stream stream);
+int ivg_kv_snapshot_restore(ivg_engine* e, const ivg_kv_snapshot* s, const int32_t* parents, int n, ivg_stream stream);
+void ivg_kv_snapshot_destroy(ivg_kv_snapshot* s);
+#define IVG_KV_SNAPSHOT_INFO_INTS 8
+int ivg_kv_snapshot_info(const ivg_kv_snapshot* s, int64_t* out);
+
 /* Extend the kept cache with GIVEN tokens (teacher forcing), or rewind it: afterwards it holds positions [0, L0 - 1) of prompt, of which
  * [0, keep_len) are the kept rows as they were and [keep_len, L0 - 1) are appended by this call.  T = L0 - 1 - keep_len.  For callers
  * that replace an imagined frame by the one they then observed, teacher-force ground-truth frames after the context, or rewind a few
@@ -696,6 +739,12 @@ int ivg_op_kv_absmax(const void* k16, const void* v16, int B, int heads, int L, 
  * allows; IVG_ERR_CAPACITY, with nothing launched, when it does not hold one slab's staged rows or n > chunk.  Enqueued on `stream`. */
 int ivg_op_kv_select(void* base, int layers, int chunk, int heads, int Lmax, int row_bytes_a, int row_bytes_b /* second plane, 0 if none */,
                      int len, int B_old, const int32_t* parents, int n, void* scratch, size_t scratch_bytes, ivg_stream stream);
+/* ivg_kv_snapshot_create / _restore's copy on a caller-owned buffer laid out as for ivg_op_kv_select, against dense (device, 16-byte
+ * aligned) = [layers * 2][B][heads]{len * row_bytes_a | len * row_bytes_b}.  direction 0: dense := the compact image of rows [0, B)
+ * (parents, n ignored); 1: rows [0, n) := dense rows parents[i] (host array, [0, B)).  Every other byte of either side stays.
+ * IVG_ERR_CAPACITY, with nothing launched, when dense_bytes is smaller than the image or n > chunk.  Enqueued on `stream`. */
+int ivg_op_kv_snapshot(void* base, int layers, int chunk, int heads, int Lmax, int row_bytes_a, int row_bytes_b /* second plane, 0 if none */,
+                       int len, int B, void* dense, size_t dense_bytes, const int32_t* parents, int n, int direction, ivg_stream stream);
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream);
 /* ivg_op_sample followed by the nucleus filter of ivg_set_top_p (steps 1-4 there); top_p outside [0, 1] or NaN: IVG_ERR_INVALID */
 int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temperature, float top_p, const float* uniforms, int64_t* out,
@@ -718,7 +767,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps; "enc_plain_images" / "enc_cond_images": images sent through the plain / the conditional encoder trunk; "enc_kv_projections": cross-attention K / V projections made for an encoder, one per site and call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_snapshot_rows_saved" / "kv_snapshot_rows_restored": trajectory rows ivg_kv_snapshot_create / _restore (and ivg_op_kv_snapshot) copied out / in; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps; "enc_plain_images" / "enc_cond_images": images sent through the plain / the conditional encoder trunk; "enc_kv_projections": cross-attention K / V projections made for an encoder, one per site and call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

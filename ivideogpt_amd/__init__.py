@@ -5,7 +5,8 @@ There is no CPU / eager-PyTorch compute path: using a model without the built li
 non-GPU device, raises.
 """
 from .vq_model import CompressiveVQModel, DetokenizeCache  # noqa: F401
+from .engine import KeptCache  # noqa: F401
 from .transformer import HeadModelWithAction, LlamaForCausalLM, TokenScores  # noqa: F401
 from . import switches, weights  # noqa: F401
 
-__all__ = ["CompressiveVQModel", "DetokenizeCache", "HeadModelWithAction", "LlamaForCausalLM", "TokenScores", "switches", "weights"]
+__all__ = ["CompressiveVQModel", "DetokenizeCache", "HeadModelWithAction", "KeptCache", "LlamaForCausalLM", "TokenScores", "switches", "weights"]

@@ -12,6 +12,7 @@ IVG_K_IGEMM_BF16, IVG_K_IGEMM_F32, IVG_K_CONV3X3_BF16, IVG_K_CONV3X3_F32, IVG_K_
 IG_BIAS_N, IG_BIAS_M, IG_RESIDUAL, IG_SILU, IG_GLU, IG_OUT_F32 = 1, 2, 4, 8, 16, 32
 IG_RELU = 256
 IVG_KV_NATIVE, IVG_KV_FP8_E4M3 = 0, 1   # ivg_set_kv_format
+IVG_KV_SNAPSHOT_INFO_INTS = 8           # ivg_kv_snapshot_info
 
 
 class IvgTensor(C.Structure):
@@ -85,6 +86,10 @@ EXPORTS = {
     "ivg_cache_destroy": (None, [C.c_void_p, C.c_void_p]),
     "ivg_cache_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "ivg_kv_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ivg_kv_snapshot_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "ivg_kv_snapshot_restore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ivg_kv_snapshot_destroy": (None, [C.c_void_p]),
+    "ivg_kv_snapshot_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ivg_kv_extend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ivg_generate_fanout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -158,6 +163,7 @@ EXPORTS = {
     "ivg_op_add_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "ivg_op_conv_in": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
     "ivg_op_kv_select": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_op_kv_snapshot": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ivg_op_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_op_sample_top_p": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ivg_op_token_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -843,6 +843,34 @@ int ivg_kv_select(ivg_engine* e, const int32_t* parents, int n, ivg_stream strea
   return kv_select(e, parents, n, (hipStream_t)stream);
 }
 
+int ivg_kv_snapshot_create(ivg_engine* e, ivg_kv_snapshot** out, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!out) return e->fail(IVG_ERR_INVALID, "kv_snapshot_create: null argument");
+  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "kv_snapshot_create: engine was created without a transformer");
+  return kv_snapshot_create(e, out, (hipStream_t)stream);
+}
+
+int ivg_kv_snapshot_restore(ivg_engine* e, const ivg_kv_snapshot* s, const int32_t* parents, int n, ivg_stream stream) {
+  if (!e) return IVG_ERR_INVALID;
+  if (!s) return e->fail(IVG_ERR_INVALID, "kv_snapshot_restore: null snapshot");
+  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "kv_snapshot_restore: engine was created without a transformer");
+  return kv_snapshot_restore(e, s, parents, n, (hipStream_t)stream);
+}
+
+void ivg_kv_snapshot_destroy(ivg_kv_snapshot* s) {
+  if (!s) return;
+  (void)hipFree(s->mem);   // (waits for the device: copies of a create or restore still queued have finished)
+  delete s;
+}
+
+int ivg_kv_snapshot_info(const ivg_kv_snapshot* s, int64_t* out) {
+  if (!s || !out) return IVG_ERR_INVALID;
+  const int64_t v[IVG_KV_SNAPSHOT_INFO_INTS] = {s->B, s->len, (int64_t)s->bytes, s->snap_valid ? 1 : 0, s->act_T, s->ctx,
+                                                s->format == KvFormat::Fp8 ? IVG_KV_FP8_E4M3 : s->format == KvFormat::Planes24 ? 2 : IVG_KV_NATIVE, s->device};
+  for (int i = 0; i < IVG_KV_SNAPSHOT_INFO_INTS; ++i) out[i] = v[i];
+  return IVG_OK;
+}
+
 int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0, const float* actions, int act_T, int ctx,
                   float* token_nll_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
@@ -1377,6 +1405,8 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "token_scores")) return token_scores_launches();
   if (name && !strcmp(name, "kv_select_direct")) return kv_select_rows(0);
   if (name && !strcmp(name, "kv_select_staged")) return kv_select_rows(1);
+  if (name && !strcmp(name, "kv_snapshot_rows_saved")) return kv_snapshot_rows(0);
+  if (name && !strcmp(name, "kv_snapshot_rows_restored")) return kv_snapshot_rows(1);
   if (name && !strcmp(name, "kv_extend_chunk_rows")) return kv_extend_rows(0);
   if (name && !strcmp(name, "kv_extend_step_rows")) return kv_extend_rows(1);
   if (name && !strcmp(name, "enc_plain_images")) return enc_counter(0);
@@ -1551,6 +1581,27 @@ int ivg_op_kv_select(void* base, int layers, int chunk, int heads, int Lmax, int
   const int rc = launch_kv_select(b, plan, scratch, scratch_bytes, (hipStream_t)stream);
   if (rc == 0) kv_select_note(plan.n_direct, plan.n_staged);
   return rc == 0 ? IVG_OK : (rc == -4 ? IVG_ERR_CAPACITY : IVG_ERR_HIP);
+}
+
+int ivg_op_kv_snapshot(void* base, int layers, int chunk, int heads, int Lmax, int row_bytes_a, int row_bytes_b, int len, int B, void* dense,
+                       size_t dense_bytes, const int32_t* parents, int n, int direction, ivg_stream stream) {
+  if (!base || !dense || layers <= 0 || heads <= 0 || Lmax <= 0 || row_bytes_a <= 0 || row_bytes_b < 0 || row_bytes_a % 16 || row_bytes_b % 16 || len < 1 ||
+      len > Lmax || chunk <= 0 || chunk > KV_SELECT_MAX_ROWS || B <= 0 || B > chunk || (direction != 0 && direction != 1))
+    return IVG_ERR_INVALID;
+  if (direction == 1) {
+    if (!parents || n <= 0) return IVG_ERR_INVALID;
+    if (n > chunk) return IVG_ERR_CAPACITY;
+    for (int i = 0; i < n; ++i)
+      if (parents[i] < 0 || parents[i] >= B) return IVG_ERR_INVALID;
+  }
+  KvSelectBuf b;   // [layers][2][chunk][heads]{[Lmax] rows of row_bytes_a | [Lmax] rows of row_bytes_b}
+  b.base = (char*)base; b.slabs = layers * 2; b.heads = heads;
+  b.head_stride = (long)Lmax * (row_bytes_a + row_bytes_b); b.row_stride = heads * b.head_stride; b.slab_stride = chunk * b.row_stride;
+  b.bytes_a = (long)len * row_bytes_a; b.bytes_b = (long)len * row_bytes_b; b.plane_b = (long)Lmax * row_bytes_a;
+  if ((size_t)b.slabs * B * heads * (size_t)(b.bytes_a + b.bytes_b) > dense_bytes) return IVG_ERR_CAPACITY;
+  const int rc = launch_kv_snapshot(b, dense, B, parents, direction ? n : B, direction == 1, (hipStream_t)stream);
+  if (rc == 0) kv_snapshot_note(direction ? 0 : B, direction ? n : 0);
+  return rc == 0 ? IVG_OK : IVG_ERR_HIP;
 }
 
 int ivg_op_sample(const float* logits, int B, int V, int top_k, float temperature, const float* uniforms, int64_t* out, ivg_stream stream) {

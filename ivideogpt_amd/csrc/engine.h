@@ -223,6 +223,30 @@ struct ivg_enc_cache {
   int ctx = 0;                              // context length in force at fill time
 };
 
+// A copy of the transformer's kept cache (ivg_kv_snapshot_create), owned by the caller: one device allocation holding the compact image
+// of every buffer ivg_kv_select gathers, the kept host state, and what makes the bytes meaningful to an engine that restores them
+struct ivg_kv_snapshot {
+  struct Part { size_t off = 0; int slabs = 1, heads = 1; long bytes_a = 0, bytes_b = 0; int vec = 16; };   // [slabs][B][heads]{bytes_a | bytes_b} at off
+  char* mem = nullptr;
+  size_t bytes = 0;
+  int device = 0;
+  // the kept state (KvCache::keep's arguments)
+  int len = 0, B = 0;
+  bool ids_valid = false, snap_valid = false;
+  int act_T = 0, ctx = 0;
+  int id_cols = 0;                          // columns [0, id_cols) of the id rows: len + 1 where the rows are that long
+  Part kv, ids, act, emb;                   // (act / emb: bytes_a == 0 when the kept cache has none)
+  // what the bytes mean
+  int layers = 0, heads = 0, hd = 0, hidden = 0, action_dim = 0;
+  ivg::DType dt = ivg::F32;
+  bool x3 = false;
+  ivg::KvFormat format = ivg::KvFormat::Native;
+  bool table = false;
+  float k_scale = 1.0f, v_scale = 1.0f;
+  std::vector<float> scales;
+  const void* embed = nullptr; const void* lm_head = nullptr;   // the weights tag
+};
+
 struct ivg_engine {
   ivg_config cfg;
   int device = 0;

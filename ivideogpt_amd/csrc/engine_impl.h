@@ -117,6 +117,10 @@ int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, h
 int need_kept_cache(ivg_engine* e, const char* entry);   // 0, or the refusal of an entry that works on a kept cache where the engine holds none
 // ivg_kv_select: the kept cache's rows, and everything the verification above compares them with, gathered by `parents`
 int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st);
+// ivg_kv_snapshot_create / _restore: everything kv_select gathers, copied out into a device allocation of the caller's and back in
+// (arguments other than the engine and the snapshot pointers are checked here)
+int kv_snapshot_create(ivg_engine* e, ivg_kv_snapshot** out, hipStream_t st);
+int kv_snapshot_restore(ivg_engine* e, const ivg_kv_snapshot* s, const int32_t* parents, int n, hipStream_t st);
 size_t kv_select_scratch_bytes(const ivg_engine* e);   // workspace that stages one slab of any buffer ivg_kv_select gathers, all rows staged
 
 }  // namespace ivg

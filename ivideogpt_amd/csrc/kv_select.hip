@@ -94,6 +94,38 @@ int launch_gather_rows_by_parent(const void* src, void* dst, long row_bytes, con
   return 0;
 }
 
+// ivg_kv_snapshot_create / _restore: the rows of b against their compact image dense = [slabs][dense_rows][heads]{bytes_a | bytes_b}.
+// The image is the dense side of the gather kernel; for a restore it is a table side too, indexed by parents through the move list
+int launch_kv_snapshot(const KvSelectBuf& b, void* dense, int dense_rows, const int32_t* parents, int n, bool restore, hipStream_t st) {
+  if (n <= 0 || b.slabs <= 0 || b.bytes_a + b.bytes_b <= 0) return 0;
+  if (!b.base || !dense || (b.vec != 16 && b.vec != 4) || b.heads <= 0 || b.slabs > 65535 || (long)KV_SELECT_MAX_ROWS * b.heads > 65535 ||
+      dense_rows <= 0 || dense_rows > 256 || n > 256 || (!restore && n != dense_rows) || (restore && !parents))
+    return (int)hipErrorInvalidValue;
+  const long al = b.vec - 1;
+  if ((((uintptr_t)b.base | (uintptr_t)dense) & al) || ((b.slab_stride | b.row_stride | b.head_stride | b.bytes_a | b.bytes_b | b.plane_b) & al) ||
+      (b.bytes_a + b.bytes_b) / b.vec > (long)INT32_MAX / 2)
+    return (int)hipErrorInvalidValue;
+  if (restore)
+    for (int i = 0; i < n; ++i)
+      if (parents[i] < 0 || parents[i] >= dense_rows) return (int)hipErrorInvalidValue;
+  const long seg = b.bytes_a + b.bytes_b, drow = (long)b.heads * seg;
+  const KvSide rows{b.base, b.slab_stride, b.row_stride, b.head_stride, b.plane_b, 1};
+  for (int i0 = 0; i0 < n; i0 += KV_SELECT_MAX_ROWS) {   // cache rows [i0, i0 + k)
+    const int k = std::min(KV_SELECT_MAX_ROWS, n - i0);
+    KvMoves mv{};
+    for (int m = 0; m < k; ++m) { mv.src[m] = (uint8_t)(restore ? parents[i0 + m] : i0 + m); mv.dst[m] = (uint8_t)(i0 + m); }
+    const KvSide image{(char*)dense + (restore ? 0 : (size_t)i0 * drow), (long)dense_rows * drow, drow, seg, b.bytes_a, restore ? 1 : 0};
+    if (int rc = restore ? launch_gather(image, rows, mv, k, b.slabs, b.heads, b.bytes_a, b.bytes_b, b.vec, st)
+                         : launch_gather(rows, image, mv, k, b.slabs, b.heads, b.bytes_a, b.bytes_b, b.vec, st))
+      return rc;
+  }
+  return 0;
+}
+
+static std::atomic<long long> g_kv_snapshot_rows[2] = {{0}, {0}};
+void kv_snapshot_note(int saved, int restored) { g_kv_snapshot_rows[0] += saved; g_kv_snapshot_rows[1] += restored; }
+long long kv_snapshot_rows(int restored) { return g_kv_snapshot_rows[restored ? 1 : 0].load(); }
+
 static std::atomic<long long> g_kv_select_rows[2] = {{0}, {0}};
 void kv_select_note(int direct, int staged) { g_kv_select_rows[0] += direct; g_kv_select_rows[1] += staged; }
 long long kv_select_rows(int staged) { return g_kv_select_rows[staged ? 1 : 0].load(); }

@@ -184,6 +184,12 @@ int launch_kv_select(const KvSelectBuf& b, const KvSelectPlan& plan, void* scrat
 // dst row i := src row parents[i], 0 <= i < n, rows of row_bytes (a multiple of 16) bytes, contiguous, in two buffers that do not
 // overlap; any n and any parents[i] >= 0 (the rows go in launches of at most 128 moves within windows of 256 rows)
 int launch_gather_rows_by_parent(const void* src, void* dst, long row_bytes, const int32_t* parents, int n, hipStream_t st);
+// ivg_kv_snapshot_create / _restore: b's rows against their compact image dense = [slabs][dense_rows][heads]{bytes_a |
+// bytes_b} (aligned to b.vec).  restore false: image row i := row i, i < n == dense_rows; true: row i := image row parents[i], i < n
+// (host array, [0, dense_rows); the caller keeps n within the rows b has room for).  At most 256 rows either way.  0 or a hipError_t
+int launch_kv_snapshot(const KvSelectBuf& b, void* dense, int dense_rows, const int32_t* parents, int n, bool restore, hipStream_t st);
+void kv_snapshot_note(int saved, int restored);   // trajectory rows saved / restored (test hook, ivg_debug_counter("kv_snapshot_rows_saved" / "_restored"))
+long long kv_snapshot_rows(int restored);
 void kv_select_note(int direct, int staged);   // trajectory rows a select moved (test hook, ivg_debug_counter("kv_select_direct" / "_staged"))
 long long kv_select_rows(int staged);
 

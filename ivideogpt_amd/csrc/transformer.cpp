@@ -689,29 +689,40 @@ int Run::extend(const ExtendReq& q) {
 // ---------------------------------------------------------------------------------------- kept-cache row selection (ivg_kv_select)
 // the buffers whose rows belong to the kept trajectories: the K / V slabs in the cache's own format, and what the verification above
 // compares a caller's "same prefix" claim with -- the id rows, the action table, the embeddings snapshot
-static void kv_select_bufs(const ivg_engine* e, const GenBuf& g, std::vector<KvSelectBuf>& out) {
+struct KeptBufs { KvSelectBuf kv, ids, act, emb; };   // act / emb: bytes_a == 0 where the kept state has no action table / no embeddings snapshot
+
+// ... of a kept state given by value: `len` positions, an action table of act_T rows, with or without the embeddings snapshot
+// (ivg_kv_snapshot_restore describes the state it is about to install; everyone else the one the engine holds)
+static KeptBufs kept_bufs(const ivg_engine* e, const GenBuf& g, int len, int act_T, bool snap) {
   const KvCache& k = e->kvc;
   const long eb = (long)k.elem_bytes(), blk = (long)k.Lmax * k.hd * eb;
-  KvSelectBuf c;
+  KeptBufs r;
+  KvSelectBuf& c = r.kv;
   c.base = k.base; c.slabs = k.layers * 2; c.row_stride = (long)k.heads * blk; c.slab_stride = (long)k.chunk * c.row_stride;
   c.heads = k.heads; c.head_stride = blk;
-  if (k.format == KvFormat::Planes24) { c.bytes_a = (long)k.len * k.hd * 2; c.bytes_b = (long)k.len * k.hd; c.plane_b = (long)k.Lmax * k.hd * 2; }
-  else c.bytes_a = (long)k.len * k.hd * eb;
-  out.push_back(c);
-  KvSelectBuf ids;
-  ids.base = (char*)g.ids; ids.row_stride = (long)g.ids_ld * 8; ids.bytes_a = (long)std::min(k.len + 1, g.ids_ld) * 8; ids.vec = 4;   // (column len: decided, not yet fed)
-  out.push_back(ids);
-  if (k.last_act_T > 0) {
-    KvSelectBuf a;
-    a.base = (char*)g.last_act; a.row_stride = (long)k.last_act_T * e->cfg.action_dim * 4; a.bytes_a = a.row_stride; a.vec = 4;
-    out.push_back(a);
+  if (k.format == KvFormat::Planes24) { c.bytes_a = (long)len * k.hd * 2; c.bytes_b = (long)len * k.hd; c.plane_b = (long)k.Lmax * k.hd * 2; }
+  else c.bytes_a = (long)len * k.hd * eb;
+  KvSelectBuf& ids = r.ids;
+  ids.base = (char*)g.ids; ids.row_stride = (long)g.ids_ld * 8; ids.bytes_a = (long)std::min(len + 1, g.ids_ld) * 8; ids.vec = 4;   // (column len: decided, not yet fed)
+  if (act_T > 0) {
+    KvSelectBuf& a = r.act;
+    a.base = (char*)g.last_act; a.row_stride = (long)act_T * e->cfg.action_dim * 4; a.bytes_a = a.row_stride; a.vec = 4;
   }
-  if (k.snap_valid && e->emb_snap) {
+  if (snap) {
     const long rowb = (long)e->cfg.hidden_size * (long)esz(e->llm_dt);
-    KvSelectBuf s;
-    s.base = e->emb_snap; s.row_stride = (long)e->Lmax * rowb; s.bytes_a = (long)k.len * rowb;
-    out.push_back(s);
+    KvSelectBuf& s = r.emb;
+    s.base = e->emb_snap; s.row_stride = (long)e->Lmax * rowb; s.bytes_a = (long)len * rowb;
   }
+  return r;
+}
+
+static void kv_select_bufs(const ivg_engine* e, const GenBuf& g, std::vector<KvSelectBuf>& out) {
+  const KvCache& k = e->kvc;
+  const KeptBufs r = kept_bufs(e, g, k.len, k.last_act_T, k.snap_valid && e->emb_snap);
+  out.push_back(r.kv);
+  out.push_back(r.ids);
+  if (r.act.bytes_a > 0) out.push_back(r.act);
+  if (r.emb.bytes_a > 0) out.push_back(r.emb);
 }
 
 size_t kv_select_scratch_bytes(const ivg_engine* e) {   // (a native K / V slab and the embeddings snapshot are the same size; the id rows the rest)
@@ -742,6 +753,93 @@ int kv_select(ivg_engine* e, const int32_t* parents, int n, hipStream_t st) {
     kv_select_note(plan.n_direct, plan.n_staged);
   }
   k.B = n;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------- kept-cache snapshots (ivg_kv_snapshot_*)
+static size_t part_bytes(const ivg_kv_snapshot::Part& p, int rows) { return (size_t)p.slabs * rows * p.heads * (size_t)(p.bytes_a + p.bytes_b); }
+
+int kv_snapshot_create(ivg_engine* e, ivg_kv_snapshot** out, hipStream_t st) {
+  IVG_TRY(need_kept_cache(e, "kv_snapshot_create"));
+  const KvCache& k = e->kvc;
+  const GenBuf g = gen_buf(e);
+  const KeptBufs kb = kept_bufs(e, g, k.len, k.last_act_T, k.snap_valid && e->emb_snap);
+  ivg_kv_snapshot s;
+  s.device = e->device;
+  s.len = k.len; s.B = k.B; s.ids_valid = k.ids_valid; s.snap_valid = k.snap_valid; s.act_T = k.last_act_T; s.ctx = k.last_ctx;
+  s.id_cols = (int)(kb.ids.bytes_a / 8);
+  s.layers = k.layers; s.heads = k.heads; s.hd = k.hd; s.hidden = e->cfg.hidden_size; s.action_dim = e->cfg.action_dim;
+  s.dt = e->llm_dt; s.x3 = e->llm_x3; s.format = k.format;
+  s.table = k.table; s.k_scale = k.k_scale; s.v_scale = k.v_scale; s.scales = k.scales;
+  s.embed = e->embed; s.lm_head = e->lm_head;
+  // the 16-byte parts first: every part then starts at a multiple of its own vector with no padding in between
+  const KvSelectBuf* bufs[4] = {&kb.kv, &kb.emb, &kb.ids, &kb.act};
+  ivg_kv_snapshot::Part* parts[4] = {&s.kv, &s.emb, &s.ids, &s.act};
+  for (int i = 0; i < 4; ++i) {
+    ivg_kv_snapshot::Part& p = *parts[i];
+    p.off = s.bytes; p.slabs = bufs[i]->slabs; p.heads = bufs[i]->heads; p.bytes_a = bufs[i]->bytes_a; p.bytes_b = bufs[i]->bytes_b; p.vec = bufs[i]->vec;
+    s.bytes += part_bytes(p, s.B);
+  }
+  if (hipMalloc((void**)&s.mem, s.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return e->fail(IVG_ERR_HIP, "kv_snapshot_create: hipMalloc of " + std::to_string(s.bytes) + " bytes failed");
+  }
+  for (int i = 0; i < 4; ++i)
+    if (const int rc = launch_kv_snapshot(*bufs[i], s.mem + parts[i]->off, s.B, nullptr, s.B, false, st)) {
+      (void)hipDeviceSynchronize();   // (launches already queued write the allocation)
+      (void)hipFree(s.mem);
+      return e->fail(IVG_ERR_HIP, "kv_snapshot_create: launch failed: hip error " + std::to_string(rc));
+    }
+  kv_snapshot_note(s.B, 0);
+  *out = new ivg_kv_snapshot(std::move(s));
+  return 0;
+}
+
+int kv_snapshot_restore(ivg_engine* e, const ivg_kv_snapshot* s, const int32_t* parents, int n, hipStream_t st) {
+  KvCache& k = e->kvc;
+  auto no = [&](const std::string& what) { return e->fail(IVG_ERR_INVALID, "kv_snapshot_restore: " + what); };
+  if (parents && n <= 0) return no("parents must hold at least one row");
+  if (!parents) n = s->B;
+  if (s->device != e->device) return no("the snapshot lives on device " + std::to_string(s->device) + ", the engine on " + std::to_string(e->device));
+  if (s->layers != k.layers || s->heads != k.heads || s->hd != k.hd || s->hidden != e->cfg.hidden_size || s->action_dim != e->cfg.action_dim)
+    return no("the snapshot was taken from a transformer of another geometry (layers, heads, head_dim, hidden size or action_dim differ)");
+  if (s->dt != e->llm_dt || s->x3 != e->llm_x3 || s->format != k.format)
+    return no("the snapshot's element type or K/V format is not this engine's");
+  if (k.format == KvFormat::Fp8) {
+    const bool same = s->table == k.table &&
+                      (k.table ? s->scales.size() == k.scales.size() && !memcmp(s->scales.data(), k.scales.data(), k.scales.size() * 4)
+                               : !memcmp(&s->k_scale, &k.k_scale, 4) && !memcmp(&s->v_scale, &k.v_scale, 4));
+    if (!same) return no("the FP8 scales in force differ from the ones the snapshot's bytes were written with");
+  }
+  if (s->embed != e->embed || s->lm_head != e->lm_head) return no("the snapshot was taken over other weights");
+  if (parents)
+    for (int i = 0; i < n; ++i)
+      if (parents[i] < 0 || parents[i] >= s->B) return no("every parent must be a row of the snapshot, [0, " + std::to_string(s->B) + ")");
+  const GenBuf g = gen_buf(e);
+  if (n > k.chunk) return e->fail(IVG_ERR_CAPACITY, "kv_snapshot_restore: " + std::to_string(n) + " rows exceed the KV-cache chunk (" + std::to_string(k.chunk) + ")");
+  if (s->len > k.Lmax || s->id_cols > g.ids_ld)
+    return e->fail(IVG_ERR_CAPACITY, "kv_snapshot_restore: " + std::to_string(s->len) + " kept positions exceed the KV cache (" + std::to_string(k.Lmax) + ")");
+  if (s->act_T > e->cfg.max_frames)
+    return e->fail(IVG_ERR_CAPACITY, "kv_snapshot_restore: an action table of " + std::to_string(s->act_T) + " rows exceeds max_frames (" + std::to_string(e->cfg.max_frames) + ")");
+  const bool emb = s->emb.bytes_a > 0;
+  if (emb && !e->emb_snap && hipMalloc((void**)&e->emb_snap, (size_t)g.Bc * e->Lmax * e->cfg.hidden_size * esz(e->llm_dt)) != hipSuccess) {
+    (void)hipGetLastError(); e->emb_snap = nullptr;
+    return e->fail(IVG_ERR_HIP, "hipMalloc of the embeddings snapshot failed");
+  }
+  KeptBufs kb = kept_bufs(e, g, s->len, s->act_T, emb);
+  kb.ids.bytes_a = (long)s->id_cols * 8;   // (a snapshot of a full cache has no column len; it fits, checked above)
+  const KvSelectBuf* bufs[4] = {&kb.kv, &kb.emb, &kb.ids, &kb.act};
+  const ivg_kv_snapshot::Part* parts[4] = {&s->kv, &s->emb, &s->ids, &s->act};
+  for (int i = 0; i < 4; ++i)   // the engine's description of the state must be the snapshot's, byte count for byte count
+    if (bufs[i]->slabs != parts[i]->slabs || bufs[i]->heads != parts[i]->heads || bufs[i]->bytes_a != parts[i]->bytes_a ||
+        bufs[i]->bytes_b != parts[i]->bytes_b || bufs[i]->vec != parts[i]->vec)
+      return no("internal: the engine lays the kept state out differently from the snapshot");
+  std::vector<int32_t> ident;
+  if (!parents) { ident.resize(n); for (int i = 0; i < n; ++i) ident[i] = i; parents = ident.data(); }
+  k.forget_kept();   // kept again once every launch is queued
+  for (int i = 0; i < 4; ++i) CK(launch_kv_snapshot(*bufs[i], s->mem + parts[i]->off, s->B, parents, n, true, st));
+  k.len = s->len; k.B = n; k.ids_valid = s->ids_valid; k.snap_valid = s->snap_valid; k.last_act_T = s->act_T; k.last_ctx = s->ctx;
+  kv_snapshot_note(0, n);
   return 0;
 }
 

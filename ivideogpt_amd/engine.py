@@ -40,6 +40,45 @@ def rollout_entry(fanout=False, token_scores=False, frame_outputs=False, group_s
             return name
 
 
+class KeptCache:
+    """A transformer's kept K / V cache set aside (include/ivg.h ivg_kv_snapshot): device memory of its own, independent of the engine
+    that made it -- it outlives that engine and is restored, any number of times, into it or into any engine over the same weights.
+    ``rows``, ``length`` (kept positions), ``nbytes`` (device memory); ``from_embeds``, ``act_T``, ``ctx``, ``kv_format``, ``device_index``:
+    how the cache was built.  ``close()`` releases the memory (idempotent; also on garbage collection); a context manager."""
+
+    _FIELDS = ("rows", "length", "nbytes", "from_embeds", "act_T", "ctx", "kv_format", "device_index")
+
+    def __init__(self, lib, h, weights_version=None):
+        self.lib, self.h = lib, h
+        self.weights_version = weights_version   # set by the model that saved it (LlamaForCausalLM.save_kept_cache)
+        info = (C.c_int64 * _lib.IVG_KV_SNAPSHOT_INFO_INTS)()
+        _lib.check(lib.ivg_kv_snapshot_info(h, info), None, "kv_snapshot_info")
+        for k, v in zip(self._FIELDS, info):
+            setattr(self, k, int(v))
+        self.from_embeds = bool(self.from_embeds)
+
+    @property
+    def closed(self):
+        return self.h is None
+
+    def close(self):
+        h, self.h = getattr(self, "h", None), None
+        if h is not None:
+            self.lib.ivg_kv_snapshot_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, device, tensors, tok_cfg=None, llm_cfg=None, action_dim=0, reward_head=False,
                  encode_dtype="fp32", decode_dtype="bf16", llm_dtype="bf16", max_batch=1, max_frames=16, max_seq=0,
@@ -318,6 +357,23 @@ class Engine:
         p = np.ascontiguousarray(parents, dtype=np.int32)
         with self.stream() as s:
             self.check(self.lib.ivg_kv_select(self.h, p.ctypes.data_as(C.c_void_p), int(p.size), s), "kv_select")
+        return self
+
+    def kv_snapshot(self):
+        """``ivg_kv_snapshot_create``: -> ``KeptCache``, a copy of the kept K / V cache in device memory of its own.  Enqueued."""
+        h = C.c_void_p()
+        with self.stream() as s:
+            self.check(self.lib.ivg_kv_snapshot_create(self.h, C.byref(h), s), "kv_snapshot_create")
+        return KeptCache(self.lib, h)
+
+    def kv_restore(self, kept, parents=None):
+        """``ivg_kv_snapshot_restore``: row i of the kept K / V cache := row ``parents[i]`` (host integers; None: every row) of ``kept``."""
+        if kept.h is None:
+            raise ValueError("kv_restore: the KeptCache is closed")
+        p = np.ascontiguousarray(parents, dtype=np.int32) if parents is not None else None
+        with self.stream() as s:
+            self.check(self.lib.ivg_kv_snapshot_restore(self.h, kept.h, p.ctypes.data_as(C.c_void_p) if p is not None else None,
+                                                        int(p.size) if p is not None else 0, s), "kv_snapshot_restore")
         return self
 
     def kv_extend(self, prompt, keep_len, actions=None, ctx=1, token_nll=None):

@@ -486,6 +486,44 @@ class LlamaForCausalLM:
             raise ValueError(f"select_kept_cache: {err}") from None
         return self
 
+    def save_kept_cache(self):
+        """Sets the KV cache the last ``generate`` call kept aside (include/ivg.h ivg_kv_snapshot_create; HF:
+        ``copy.deepcopy(past_key_values)``) -> ``KeptCache``: a copy in device memory of its own -- ``.rows``, ``.length``, ``.nbytes``,
+        ``.close()`` -- that survives whatever this model does next, its engine being rebuilt included.  The live kept cache is
+        unchanged; the copy is enqueued.  ValueError when there is no kept cache (``select_kept_cache`` has the cases)."""
+        if self._engine is None:
+            raise ValueError("save_kept_cache: no kept cache (the model has not generated yet)")
+        try:
+            kept = self._engine.kv_snapshot()
+        except (AssertionError, _lib.IvgError) as err:
+            raise ValueError(f"save_kept_cache: {err}") from None
+        kept.weights_version = self._pack_key()
+        return kept
+
+    def restore_kept_cache(self, kept, parents=None):
+        """Brings a ``KeptCache`` back (ivg_kv_snapshot_restore): row i of this model's kept cache becomes row ``parents[i]`` of ``kept``
+        (``select_kept_cache``'s ``parents``; None: every row), at the saved length -- continue with ``reuse_cache=True`` /
+        ``use_cache=True`` on the prompt, actions or embeddings gathered by the same ``parents``, ``extend_kept_cache``, ``fan_out``,
+        ``select_kept_cache``.  ``kept`` is unchanged and may be restored again, into this model, into the larger engine it builds when
+        the restored rows need one (the only case in which this call builds an engine), or into a ``replica()``.  ValueError, with this
+        model's kept cache as it was, where the engine refuses: a model with other weights or another config, a K / V format or FP8
+        scale other than the saved one, a parent outside ``kept.rows``, more rows than the cache chunk (128) or more positions than
+        ``max_seq`` holds."""
+        if kept.closed:
+            raise ValueError("restore_kept_cache: the KeptCache is closed")
+        p = normalize_parents(parents, kept.rows) if parents is not None else None
+        if kept.weights_version is not None and kept.weights_version != self._pack_key():
+            raise ValueError("restore_kept_cache: the KeptCache was saved by a model with other weights (or on another device, or in another dtype)")
+        n, frames = int(p.size) if p is not None else kept.rows, kept.act_T if kept.act_T > 0 else 32
+        try:
+            eng = self._engine
+            if eng is None or (n <= 128 and (n > eng.max_batch or frames > eng.max_frames)):   # (more than the chunk: the engine refuses, nothing is rebuilt)
+                eng = self._ensure(min(n, 128), frames)
+            eng.kv_restore(kept, p)
+        except (AssertionError, _lib.IvgError) as err:
+            raise ValueError(f"restore_kept_cache: {err}") from None
+        return self
+
     def extend_kept_cache(self, input_ids, keep, return_nll=False, _actions=None, _ctx=1):
         """Appends GIVEN tokens to the KV cache the last ``generate`` call kept (include/ivg.h ivg_kv_extend): afterwards it holds
         ``input_ids[:, :-1]``, of which positions [0, keep) are the kept rows as they were (verified on the device) and [keep, L0 - 1)
@@ -777,6 +815,15 @@ class HeadModelWithAction:
         """``LlamaForCausalLM.select_kept_cache``: the kept cache of the last ``generate`` call (its action table included) gathered by
         ``parents``; continue with ``reuse_cache=True`` on ``inputs_token[parents]`` and ``action[parents]``."""
         self.llm.select_kept_cache(parents)
+        return self
+
+    def save_kept_cache(self):
+        """``LlamaForCausalLM.save_kept_cache``: -> ``KeptCache``, the kept cache of the last call (its action table included) set aside."""
+        return self.llm.save_kept_cache()
+
+    def restore_kept_cache(self, kept, parents=None):
+        """``LlamaForCausalLM.restore_kept_cache``; continue with ``reuse_cache=True`` on ``inputs_token[parents]`` and ``action[parents]``."""
+        self.llm.restore_kept_cache(kept, parents)
         return self
 
     def extend_kept_cache(self, inputs_token, action=None, keep=None, return_nll=False):

@@ -93,12 +93,22 @@ class TrackedEpisode:
 
     ``tokens`` (B, 257*ctx + 17*steps): the context tokens and the tokens of the ``steps`` frames observed since, ending in the sdf
     of the next frame's slot.  ``table`` (B, ctx - 1 + max_steps, A): the actions taken, row ``i + ctx - 1`` on the i-th sdf slot
-    (rows not yet taken are zero).  ``reanchors``: how often the positions were used up and the episode was anchored again."""
+    (rows not yet taken are zero).  ``reanchors``: how often the positions were used up and the episode was anchored again.
 
-    def __init__(self, predictor, obs, max_steps=None, on_full="reanchor"):
+    The transformer has ONE kept cache, so one session of a predictor is the active one; the others, and the active one while the
+    predictor rolls out, are suspended: ``suspend`` sets the kept cache aside in a ``KeptCache`` (``save_kept_cache``), ``resume`` brings
+    it back (``restore_kept_cache``: a copy, no prompt pass).  ``observe``, ``plan`` and ``select`` make their session the active one
+    first, so sessions and rollouts of one predictor interleave freely.  ``restore_fallbacks``: how often a resume found its snapshot
+    unusable (the model was given new weights) and paid the prompt pass of a fresh kept cache instead."""
+
+    def __init__(self, predictor, obs, max_steps=None, on_full="reanchor", grow="prefill"):
         if on_full not in ("reanchor", "raise"):
             raise ValueError(f"track: on_full must be 'reanchor' or 'raise', not {on_full!r}")
-        self.p, self.on_full = predictor, on_full
+        if grow not in ("prefill", "restore"):
+            raise ValueError(f"track: grow must be 'prefill' or 'restore', not {grow!r}")
+        predictor._suspend_active()   # the session about to be anchored takes the model's kept cache
+        self.p, self.on_full, self.grow = predictor, on_full, grow
+        self.suspended, self._kept, self.restore_fallbacks = False, None, 0
         ctx, llm = predictor.context_length, predictor.model.llm
         room = ((llm._max_seq or llm._cfg["max_position_embeddings"]) + 1 - 257 * ctx) // 17   # observe needs 257*ctx + 17*steps - 1 kept positions
         if room < 1:
@@ -110,6 +120,40 @@ class TrackedEpisode:
         self.stack = list(torch.chunk(obs, 3, dim=1))                          # frame_stack = 3
         self.reanchors = 0
         self._anchor()
+        predictor._active = self
+
+    def suspend(self):
+        """Sets this session's kept cache aside (``save_kept_cache``); the model is then free for anything else.  The session keeps the
+        snapshot beside its tokens, table, frame stack and encoder cache.  No effect on a suspended session."""
+        if not self.suspended:
+            try:
+                self._kept = self.p.model.save_kept_cache()
+            except ValueError:   # the model holds no kept cache any more (new weights, a call made past the predictor): resume starts afresh
+                self._kept = None
+            self.suspended = True
+        if self.p._active is self:
+            self.p._active = None
+        return self
+
+    def resume(self):
+        """Makes the model's kept cache this session's again: the snapshot is restored, or, where the model refuses it (it was given
+        new weights since) or nothing could be saved, a fresh kept cache is established with a prompt pass over ``tokens`` and ``restore_fallbacks`` counts it.
+        The caller sees to it that no other session is active (``VideoPredictor`` does).  No effect on a session that is not suspended."""
+        if self.suspended:
+            kept, self._kept = self._kept, None
+            try:
+                if kept is None:
+                    raise ValueError("nothing was saved")
+                self.p.model.restore_kept_cache(kept)
+            except ValueError:
+                self._establish()
+                self.restore_fallbacks += 1
+            finally:
+                if kept is not None:
+                    kept.close()
+            self.suspended = False
+        self.p._active = self
+        return self
 
     def _anchor(self):
         """The last ``ctx`` frames of the stack become the context: a fresh encoder cache, fresh tokens and table, a fresh kept cache."""
@@ -142,6 +186,7 @@ class TrackedEpisode:
         own episode start; ``reanchors`` counts it) and this frame is its first step -- or, with ``on_full="raise"``, RuntimeError
         with the session as it was."""
         p, ctx = self.p, self.p.context_length
+        p._activate(self)
         if self.steps >= self.max_steps:
             if self.on_full == "raise":
                 raise RuntimeError(f"track: the {self.max_steps} steps the positions allow are used up (on_full='raise')")
@@ -166,12 +211,13 @@ class TrackedEpisode:
         and, with ``return_uncertainty``, uncertainty [B * samples, horizon + 1, 1]: ``rollout_actions``' results, step 0 being the
         observed stack."""
         p, ctx, model, k = self.p, self.p.context_length, self.p.model, int(samples)
+        p._activate(self)
         B, horizon = self.batch, plans.shape[1]
         assert k >= 1 and plans.shape[0] == B * k, "plans must hold `samples` consecutive rows per tracked history"
         if self.steps + horizon > self.max_steps:
             raise ValueError(f"plan: {self.steps} observed + {horizon} imagined frames exceed the {self.max_steps} the positions allow")
-        if B * k > model.llm._engine.max_batch:   # the engine is rebuilt for the candidates: one prompt pass brings the kept cache back
-            self._establish(rows=B * k)
+        if B * k > model.llm._engine.max_batch:   # the engine is rebuilt for the candidates
+            self._grow(B * k)
         act = plans.to(p.device).float()
         table = self.table.repeat_interleave(k, 0)
         table[:, self.steps + ctx - 1:self.steps + ctx - 1 + horizon] = act
@@ -193,11 +239,22 @@ class TrackedEpisode:
             return obss, actions, rewards.float(), torch.cat([torch.zeros_like(unc[:, :1]), unc], 1).unsqueeze(-1).float()
         return obss, actions, rewards.float()
 
+    def _grow(self, rows):
+        """The kept cache in an engine that holds ``rows`` trajectories.  ``grow="prefill"``: one prompt pass over ``tokens`` brings it
+        back; ``"restore"``: the rows ``observe`` built are saved, the model rebuilds its engine, and they are restored into it."""
+        model = self.p.model
+        if self.grow != "restore":
+            return self._establish(rows=rows)
+        with model.save_kept_cache() as kept:
+            model.llm._ensure(rows, self.table.shape[1] + 1)   # (one action row more: the forced sdf behind a plan's last frame)
+            model.restore_kept_cache(kept)
+
     def select(self, parents):
         """Row i of the session becomes what row ``parents[i]`` was (particle resampling, dropping finished environments): the kept
         cache (``select_kept_cache``), the encoder cache (``EncodeCache.select``), the tokens, the action table and the frame stack."""
         from ivideogpt_amd.transformer import normalize_parents
         q = normalize_parents(parents, self.batch)
+        self.p._activate(self)
         self.p.model.select_kept_cache(q)
         self.enc_cache = self.enc_cache.select(q)
         idx = torch.from_numpy(q).to(self.p.device, torch.int64)
@@ -207,6 +264,8 @@ class TrackedEpisode:
 
 
 class VideoPredictor:
+    _active = None   # the TrackedEpisode whose kept cache the model holds (None: nobody's, or a rollout's)
+
     def __init__(self, device, args=None, reuse_cache=True):
         """``VideoPredictor('cuda', cfg.world_model)`` -- the reference's constructor (:100-110): models built by ``load_models(args)``
         and moved to ``device``.  ``reuse_cache=False`` forces a prefill of the whole prompt at every step (the reference's behaviour;
@@ -228,6 +287,22 @@ class VideoPredictor:
         self.steps_with_kept_cache = 0
         return self
 
+    # ---- one model, one kept cache: which session it belongs to.  Sessions of THIS predictor and its rollouts arbitrate here; a call that
+    # goes to the model directly, past the predictor, overwrites the kept cache unseen, and the active session's next call is refused by
+    # the engine's on-device verification, as it always was
+    def _suspend_active(self):
+        """The active session, if any, sets its kept cache aside: called before anything else touches the model."""
+        if self._active is not None:
+            self._active.suspend()
+        self._active = None
+
+    def _activate(self, session):
+        """``session`` becomes the active one: the previous one is suspended first, then ``session`` resumes."""
+        if self._active is not session:
+            self._suspend_active()
+            session.resume()
+            self._active = session
+
     @torch.no_grad()
     def rollout(self, obs, policy, horizon, return_uncertainty=False, select=None):
         """obs [B, 9, H, W] in 0..255 (3 stacked RGB frames); policy(obs, t) -> [B, A].
@@ -245,6 +320,7 @@ class VideoPredictor:
         n may exceed B up to the batch the models' engines were built for.  ``ivideogpt_amd.transformer.stable_parents`` keeps
         survivors in their rows, the cheapest resampling.  ``select=None``: exactly the rollout without it."""
         from ivideogpt_amd.transformer import normalize_parents
+        self._suspend_active()
         ctx, model, llm = self.context_length, self.model, self.model.llm
         B = obs.shape[0]
         obs = obs.to(self.device).float() / 255.
@@ -295,15 +371,20 @@ class VideoPredictor:
         return obss, actions, torch.stack(rewards, 1).float()
 
     @torch.no_grad()
-    def track(self, obs, max_steps=None, on_full="reanchor"):
+    def track(self, obs, max_steps=None, on_full="reanchor", grow="prefill"):
         """Starts a closed-loop session (act, observe, re-plan: MPC, MBRL on real transitions, monitoring the model's surprise) at
         ``obs`` [B, 9, H, W] in 0..255, as for ``rollout``: its last ``ctx`` frames are encoded once, with the encoder's context cache
         kept, and the transformer's kept cache is established at the context.  -> ``TrackedEpisode``: ``plan`` imagines candidate action
         sequences from where the episode stands, ``observe`` moves it on by the frame that was really seen and returns the model's
         surprise, ``select`` resamples its rows.  ``max_steps``: frames to observe before the session anchors itself again at the
         last ``ctx`` observed frames (default and upper bound: what ``max_position_embeddings`` allows); ``on_full="raise"``:
-        RuntimeError instead.  The model and tokenizer objects serve one session at a time."""
-        return TrackedEpisode(self, obs, max_steps=max_steps, on_full=on_full)
+        RuntimeError instead.  ``grow``: how a ``plan`` whose candidates need a larger engine than the model has built brings the kept
+        cache into the new one -- ``"prefill"``, a prompt pass over the tracked tokens, or ``"restore"``, a copy of the very rows
+        ``observe`` built (``save_kept_cache`` / ``restore_kept_cache``; bit-different from a prompt pass over the same tokens, hence opt-in).
+        A predictor serves any number of sessions, and ``rollout`` / ``rollout_actions`` beside them: whoever touches the model first
+        suspends the session whose kept cache it holds, and a session resumes by a copy when it is used next (``TrackedEpisode``).
+        Only calls made on the model or tokenizer objects directly, past the predictor, still end a session."""
+        return TrackedEpisode(self, obs, max_steps=max_steps, on_full=on_full, grow=grow)
 
     @torch.no_grad()
     def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None, return_uncertainty=False):
@@ -320,6 +401,7 @@ class VideoPredictor:
         [B * samples, horizon + 1, 1]`` as ``rollout`` does: the per-frame mean predictive entropy from the same ``generate`` call
         (``output_token_scores``), equal to ``rollout``'s bit for bit on the same actions and uniforms."""
         from ivideogpt_amd.transformer import _from_group_major, _to_group_major
+        self._suspend_active()
         ctx, model = self.context_length, self.model
         B, t = obs.shape[0], int(samples)
         N, horizon = actions.shape[0], actions.shape[1]
