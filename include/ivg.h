@@ -401,6 +401,40 @@ int ivg_kv_snapshot_info(const ivg_kv_snapshot* s, int64_t* out);
 int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0,
                   const float* actions, int act_T, int ctx, float* token_nll_out /* (B, L0 - 1 - keep_len) or NULL */, ivg_stream stream);
 
+/* ivg_kv_extend that also returns what the model thinks of the OBSERVED tokens it is given: token scores, and the reward and hidden
+ * state of every frame whose 16th token this call feeds -- the values ivg_generate_scored returns for imagined frames, without a
+ * prompt pass over the whole row (ivg_eval_forward + ivg_logits).  Preconditions, verification, effect on the kept cache, the two routes
+ * and every refusal are ivg_kv_extend's, in its order and with its statuses (messages begin "kv_extend_scored: ").
+ * With T = L0 - 1 - keep_len and p = keep_len + c:
+ * Frames.  Predicted frame i >= 0 has its 16th token at position q_i = 257*ctx + 17 i + 15.  The call has outputs for exactly the frames
+ *   with keep_len <= q_i <= L0 - 2, i.e. those whose 16th token this call feeds, written in increasing i from column 0; F_out is their
+ *   number and i_first the first one.
+ *   frame_hidden[b][k][:]  the final RMSNorm of the residual stream left by the pass that fed position q_{i_first + k}, with
+ *                          final_hidden_kernel's rounding
+ *   frame_rewards[b][k]    reward_linear on that row, in rowdot_kernel's arithmetic -- both as ivg_generate_frames defines them
+ * Scores.  token_scores[b][c] = { z_p[g] - lse(z_p), H(softmax z_p), max z_p - lse(z_p) } with g = prompt[b][p + 1], in
+ *   token_scores_kernel's arithmetic (ivg_generate_scored): NaN in all three for a maximum that is not finite, a NaN logprob for an id
+ *   outside [0, V).  With actions != NULL (the forced schedule) a column whose TARGET position p + 1 is an sdf slot -- p + 1 >= 257*ctx - 1
+ *   and (p + 1 - (257*ctx - 1)) % 17 == 0 -- is exactly 0, 0, 0, as ivg_generate_scored's forced columns; without actions every column
+ *   is scored.  token_nll_out keeps ce_row_nll's arithmetic: -logprob and nll are the same quantity in two summation orders and are
+ *   not promised bit-equal.
+ * On the decode-step route the frame outputs and the score columns are bit for bit what ivg_generate_scored's own steps produce for a
+ * rollout that had sampled these tokens; on the chunk pass the frame rows are bit for bit launch_rowdot / launch_final_hidden of the
+ * pass's residual rows (frame_rows_heads_kernel: only the F_out rows per trajectory are normed) and lm_head runs only when
+ * token_nll_out or token_scores_out is given.
+ * Extra refusals, after ivg_kv_extend's argument checks and before the on-device comparison, outputs and kept cache untouched:
+ *   IVG_ERR_MISSING   frame_rewards_out without a reward head; frame_hidden_out without 'llm.norm'
+ * A rewind (T == 0) launches nothing after the verification and writes nothing; with F_out == 0 no frame kernel is launched and the
+ * frame outputs are not written.  With all three new outputs NULL the entry launches exactly what ivg_kv_extend launches.
+ * ivg_debug_counter("kv_extend_frame_rows") counts B * F_out per call, ("kv_extend_scored_rows") B * T per call that asked for scores. */
+int ivg_kv_extend_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0,
+                         const float* actions, int act_T, int ctx,
+                         float* token_nll_out      /* (B, T) or NULL: exactly ivg_kv_extend's */,
+                         float* token_scores_out   /* (B, T, 3) or NULL */,
+                         float* frame_rewards_out  /* (B, F_out) or NULL */,
+                         void*  frame_hidden_out   /* (B, F_out, hidden), llm dtype, or NULL */,
+                         ivg_stream stream);
+
 /* Per-frame rewards and hidden states of one rollout call (the reference's generate is declared to return `reward (B, segment -
  * context)` and leaves it a TODO, action_model.py:83-99,118-120; its forward reads reward_linear at the hidden state of every frame's
  * 16th token, :198-204).
@@ -753,6 +787,11 @@ int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temp
  * chosen token of each row (not forced, j >= 1), out (B, 3) = logprob, entropy, max_logprob; V <= 256 * 72; an id outside [0, V) gives
  * a NaN logprob without a read */
 int ivg_op_token_scores(const float* logits, const int64_t* ids, int B, int V, float* out, ivg_stream stream);
+/* token_scores_rows_kernel (ivg_kv_extend_scored): the same arithmetic per row of a chunk of `rows` logits rows (rows, V); chunk row i is
+ * row r = row0 + i of (B, Tc) rows, (b, c) = (r / Tc, r % Tc), its target id ids[b * ids_stride + c], its scores out[(b * out_ld + c) * 3 ..];
+ * column c is three zeros when period > 0, c >= first_forced and (c - first_forced) % period == 0.  Nothing else is written. */
+int ivg_op_token_scores_rows(const float* logits, const int64_t* ids, int64_t ids_stride, int64_t row0, int rows, int Tc, int V,
+                             int first_forced, int period, float* out, int64_t out_ld, ivg_stream stream);
 /* LPIPS pieces (csrc/lpips.hip).  ivg_op_lpips_features: n images (n, 3, H, W) in [0, 1] (IVG_F32 / IVG_BF16) through the VGG-16 trunk,
  * taps_out[k] (n, H >> k, W >> k, 64 / 128 / 256 / 512 / 512) NHWC float32 (NULL entries are skipped); ws as ivg_lpips_rows (one image
  * at least).  ivg_op_lpips_head: out[i] = mean over the P pixels of sum_c lin[c] (f0n - f1n)^2 with f normalised per pixel by
@@ -767,7 +806,7 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
- * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_snapshot_rows_saved" / "kv_snapshot_rows_restored": trajectory rows ivg_kv_snapshot_create / _restore (and ivg_op_kv_snapshot) copied out / in; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps; "enc_plain_images" / "enc_cond_images": images sent through the plain / the conditional encoder trunk; "enc_kv_projections": cross-attention K / V projections made for an encoder, one per site and call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
+ * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_snapshot_rows_saved" / "kv_snapshot_rows_restored": trajectory rows ivg_kv_snapshot_create / _restore (and ivg_op_kv_snapshot) copied out / in; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps; "kv_extend_frame_rows" / "kv_extend_scored_rows": B * F_out of the ivg_kv_extend_scored calls / B * T of those that asked for scores; "enc_plain_images" / "enc_cond_images": images sent through the plain / the conditional encoder trunk; "enc_kv_projections": cross-attention K / V projections made for an encoder, one per site and call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */
 int64_t ivg_debug_counter(const char* name);
 
 #ifdef __cplusplus

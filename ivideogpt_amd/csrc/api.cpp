@@ -871,34 +871,50 @@ int ivg_kv_snapshot_info(const ivg_kv_snapshot* s, int64_t* out) {
   return IVG_OK;
 }
 
-int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0, const float* actions, int act_T, int ctx,
-                  float* token_nll_out, ivg_stream stream) {
+// ivg_kv_extend and ivg_kv_extend_scored: one body, `who` the entry's name in its messages; the three outputs of the latter are null for the former
+static int kv_extend_checked(ivg_engine* e, const std::string& who, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0,
+                             const float* actions, int act_T, int ctx, float* token_nll_out, float* token_scores_out, float* frame_rewards_out,
+                             void* frame_hidden_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
-  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, "kv_extend: engine was created without a transformer");
+  if (e->cfg.num_layers <= 0) return e->fail(IVG_ERR_INVALID, who + ": engine was created without a transformer");
   const KvCache& k = e->kvc;
-  if (!prompt) return e->fail(IVG_ERR_INVALID, "kv_extend: null prompt");
-  IVG_TRY(need_kept_cache(e, "kv_extend"));
-  if (!k.ids_valid) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache was built from input embeddings (only caches built from ids are extended)");
-  if (L0 - 1 > e->Lmax) return e->fail(IVG_ERR_CAPACITY, "kv_extend: " + std::to_string(L0 - 1) + " positions exceed the KV cache (" + std::to_string(e->Lmax) + ")");
-  if (B != k.B) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache holds " + std::to_string(k.B) + " trajectories, the call presents " + std::to_string(B));
+  if (!prompt) return e->fail(IVG_ERR_INVALID, who + ": null prompt");
+  IVG_TRY(need_kept_cache(e, who.c_str()));
+  if (!k.ids_valid) return e->fail(IVG_ERR_INVALID, who + ": the kept cache was built from input embeddings (only caches built from ids are extended)");
+  if (L0 - 1 > e->Lmax) return e->fail(IVG_ERR_CAPACITY, who + ": " + std::to_string(L0 - 1) + " positions exceed the KV cache (" + std::to_string(e->Lmax) + ")");
+  if (B != k.B) return e->fail(IVG_ERR_INVALID, who + ": the kept cache holds " + std::to_string(k.B) + " trajectories, the call presents " + std::to_string(B));
   if (keep_len < 1 || keep_len > k.len || keep_len > L0 - 1)
-    return e->fail(IVG_ERR_INVALID, "kv_extend: keep_len must lie in [1, min(" + std::to_string(k.len) + " kept positions, L0 - 1)]");
+    return e->fail(IVG_ERR_INVALID, who + ": keep_len must lie in [1, min(" + std::to_string(k.len) + " kept positions, L0 - 1)]");
   if (actions) {
-    if (e->cfg.action_dim <= 0 || !e->act_w) return e->fail(IVG_ERR_INVALID, "kv_extend: actions given but the model is action-free");
+    if (e->cfg.action_dim <= 0 || !e->act_w) return e->fail(IVG_ERR_INVALID, who + ": actions given but the model is action-free");
     const int slots = std::max(0, (L0 - 1 - (257 * ctx - 1) + 16) / 17);   // sdf slots among positions [0, L0 - 1)
     if (ctx < 1 || act_T < 1 || act_T > e->cfg.max_frames || (slots > 0 && ctx - 1 + slots > act_T))
-      return e->fail(IVG_ERR_INVALID, "kv_extend: action tensor too short for the sdf slots of the prompt (or longer than max_frames)");
+      return e->fail(IVG_ERR_INVALID, who + ": action tensor too short for the sdf slots of the prompt (or longer than max_frames)");
   }
+  if (frame_rewards_out && !e->rew_w) return e->fail(IVG_ERR_MISSING, who + ": rewards requested but reward_linear is not loaded");
+  if (frame_hidden_out && !e->final_norm) return e->fail(IVG_ERR_MISSING, who + ": hidden states requested but 'llm.norm' is not in the weight table");
   bool same = false;
   IVG_TRY(kv_prefix_matches_ids(e, prompt, prompt_stride, B, keep_len, actions, act_T, ctx, (hipStream_t)stream, &same));
-  if (!same) return e->fail(IVG_ERR_INVALID, "kv_extend: the kept cache was built from a different prefix (tokens, actions or context length differ)");
+  if (!same) return e->fail(IVG_ERR_INVALID, who + ": the kept cache was built from a different prefix (tokens, actions or context length differ)");
   if (keep_len == L0 - 1) {   // a pure rewind: the kept rows [0, keep_len) are what they were, nothing is launched
     e->kvc.len = keep_len;
     return IVG_OK;
   }
   ExtendReq q; q.prompt = prompt; q.prompt_stride = prompt_stride; q.B = B; q.keep_len = keep_len; q.L0 = L0; q.actions = actions; q.act_T = act_T; q.ctx = ctx;
   q.token_nll = token_nll_out; q.chunk = kv_extend_chunk_covers(e);
+  q.token_scores = token_scores_out; q.frame_rewards = frame_rewards_out; q.frame_hidden = frame_hidden_out;
   return plan_then_run(e, (hipStream_t)stream, [&](Run& r) { return r.extend(q); });
+}
+
+int ivg_kv_extend(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0, const float* actions, int act_T, int ctx,
+                  float* token_nll_out, ivg_stream stream) {
+  return kv_extend_checked(e, "kv_extend", prompt, prompt_stride, B, keep_len, L0, actions, act_T, ctx, token_nll_out, nullptr, nullptr, nullptr, stream);
+}
+
+int ivg_kv_extend_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int keep_len, int L0, const float* actions, int act_T,
+                         int ctx, float* token_nll_out, float* token_scores_out, float* frame_rewards_out, void* frame_hidden_out, ivg_stream stream) {
+  return kv_extend_checked(e, "kv_extend_scored", prompt, prompt_stride, B, keep_len, L0, actions, act_T, ctx, token_nll_out, token_scores_out,
+                           frame_rewards_out, frame_hidden_out, stream);
 }
 
 // ivg_generate_frames, ivg_generate_scored and ivg_generate_fanout each stand for several rollouts: which one, from group_size / kept_cache /
@@ -1409,6 +1425,8 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "kv_snapshot_rows_restored")) return kv_snapshot_rows(1);
   if (name && !strcmp(name, "kv_extend_chunk_rows")) return kv_extend_rows(0);
   if (name && !strcmp(name, "kv_extend_step_rows")) return kv_extend_rows(1);
+  if (name && !strcmp(name, "kv_extend_frame_rows")) return kv_extend_heads_rows(0);
+  if (name && !strcmp(name, "kv_extend_scored_rows")) return kv_extend_heads_rows(1);
   if (name && !strcmp(name, "enc_plain_images")) return enc_counter(0);
   if (name && !strcmp(name, "enc_cond_images")) return enc_counter(1);
   if (name && !strcmp(name, "enc_kv_projections")) return enc_counter(2);
@@ -1628,6 +1646,13 @@ int ivg_op_token_scores(const float* logits, const int64_t* ids, int B, int V, f
   if (!logits || !ids || !out || B <= 0 || V < 1 || V > 256 * 72) return IVG_ERR_INVALID;
   // the rollout's score kernel on given rows and ids: new token j = 1 of a prompt of length 0, no forced schedule, one column
   return one_step(0, stream, [&](StepState* state, hipStream_t st) { return launch_token_scores(logits, V, state, ids, 1, 0, 0, out, 1, B, st); });
+}
+
+int ivg_op_token_scores_rows(const float* logits, const int64_t* ids, int64_t ids_stride, int64_t row0, int rows, int Tc, int V, int first_forced,
+                             int period, float* out, int64_t out_ld, ivg_stream stream) {
+  if (!logits || !ids || !out || rows <= 0 || Tc < 1 || row0 < 0 || V < 1 || V > 256 * 72 || first_forced < 0 || period < 0) return IVG_ERR_INVALID;
+  return launch_token_scores_rows(logits, ids, (long)ids_stride, (long)row0, rows, Tc, V, first_forced, period, out, (long)out_ld, (hipStream_t)stream) == 0
+             ? IVG_OK : IVG_ERR_HIP;
 }
 
 }  // extern "C"

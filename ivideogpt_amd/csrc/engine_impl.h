@@ -26,6 +26,10 @@ struct PrefillReq {
   // ivg_kv_extend's chunk pass: the L rows are positions [pos0, pos0 + L) appended to the kept cache (`ids` points at column pos0);
   // next_ids (stride ids_stride, pointing at column pos0 + 1): the given next tokens token_nll [B][L] is taken against, instead of labels
   bool append = false; int pos0 = 0; const int64_t* next_ids = nullptr;
+  // ivg_kv_extend_scored's chunk pass: token_scores [B][L][3] against next_ids, columns c >= ts_first_forced with (c - ts_first_forced) %
+  // ts_period == 0 forced (three zeros); frame_rew [B][fr_F] / frame_hid [B][fr_F][H] from residual rows b * L + fr_row0 + 17 k
+  float* token_scores = nullptr; int ts_first_forced = 0, ts_period = 0;
+  float* frame_rew = nullptr; void* frame_hid = nullptr; int fr_row0 = 0, fr_F = 0;
 };
 
 // ivg_kv_extend: positions [keep_len, L0 - 1) of `prompt` teacher-forced onto the kept cache (arguments already checked and verified)
@@ -33,6 +37,8 @@ struct ExtendReq {
   const int64_t* prompt = nullptr; int64_t prompt_stride = 0; int B = 0, keep_len = 0, L0 = 0;
   const float* actions = nullptr; int act_T = 0, ctx = 1;
   float* token_nll = nullptr;       // [B][L0 - 1 - keep_len] or null
+  // ivg_kv_extend_scored: [B][T][3], [B][F_out], [B][F_out][H] or null; the frames are i_first .. i_first + F_out - 1 (kv_extend_frames)
+  float* token_scores = nullptr; float* frame_rewards = nullptr; void* frame_hidden = nullptr;
   bool chunk = false;               // route: one chunk pass (native bf16 cache, head_dim 64) or decode steps with given inputs
 };
 
@@ -112,6 +118,8 @@ size_t gen_buffer_bytes(const ivg_engine* e);
 // (positions [0, len) of B kept trajectories, 1 <= len <= the kept length; ids_only: the action rows of the cached slots are not compared)
 int kv_prefix_matches_ids(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int len, const float* actions, int act_T,
                           int ctx, hipStream_t st, bool* ok, bool ids_only = false);
+// frames whose 16th token, position q_i = 257 ctx + 17 i + 15, lies in [keep_len, L0 - 2]: *i_first the first one; -> their number
+int kv_extend_frames(int keep_len, int L0, int ctx, int* i_first);
 bool kv_extend_chunk_covers(const ivg_engine* e);   // ivg_kv_extend takes the chunk pass on this engine (format, element type, head dim, switch)
 int kv_prefix_matches_embeds(ivg_engine* e, const void* embeds, int B, int L0, hipStream_t st, bool* ok);
 int need_kept_cache(ivg_engine* e, const char* entry);   // 0, or the refusal of an entry that works on a kept cache where the engine holds none

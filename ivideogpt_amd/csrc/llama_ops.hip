@@ -561,6 +561,9 @@ int launch_chunk_attn(const void* qkv, const void* kc, const void* vc, void* out
 static std::atomic<long long> g_kv_extend_rows[2] = {{0}, {0}};
 void kv_extend_note(int chunk_rows, int step_rows) { g_kv_extend_rows[0] += chunk_rows; g_kv_extend_rows[1] += step_rows; }
 long long kv_extend_rows(int stepwise) { return g_kv_extend_rows[stepwise ? 1 : 0].load(); }
+static std::atomic<long long> g_kv_extend_heads[2] = {{0}, {0}};
+void kv_extend_heads_note(int frame_rows, int scored_rows) { g_kv_extend_heads[0] += frame_rows; g_kv_extend_heads[1] += scored_rows; }
+long long kv_extend_heads_rows(int scored) { return g_kv_extend_heads[scored ? 1 : 0].load(); }
 
 // ------------------------------------------------------------------------------------------------ tokenizer cross-attention
 // CrossAttentionBlock's multi-head attention (ivideogpt/vq_model/conditional_vae.py:38-55) in one pass, bf16:
@@ -2067,6 +2070,39 @@ int launch_final_hidden(const void* x, const float* w, void* out, int B, int H, 
 // is a frame's 16th, j = 17 i + 16; then workgroup b leaves frame i of trajectory b: hid[b][i][:] with final_hidden_kernel's
 // arithmetic (all four waves) and rew[b][i] with rowdot_kernel's (wave 0 alone, its own stride-64 sums), so that either equals what
 // those kernels give on the same row bit for bit.  F: frames a row of rew / hid holds; a frame beyond it is never written.
+// One residual row through both heads, by a workgroup of 256 threads (red: 4 floats of LDS): hid_out[:] with final_hidden_kernel's
+// arithmetic (all four waves), *rew_out with rowdot_kernel's (wave 0 alone, its own stride-64 sums); either may be null
+template <typename T>
+__device__ __forceinline__ void frame_heads_row(const T* __restrict__ row, const float* __restrict__ rew_w, const float* __restrict__ rew_b,
+                                                const float* __restrict__ norm_w, float* __restrict__ rew_out, T* __restrict__ hid_out, int H,
+                                                float eps, float* red) {
+  const int tid = threadIdx.x;
+  if (hid_out) {
+    float ss = 0.f;
+    for (int c = tid; c < H; c += 256) { const float v = to_f32(row[c]); ss = fmaf(v, v, ss); }
+    ss = wave_sum(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    const float rs = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + eps);
+    for (int c = tid; c < H; c += 256) {
+      const T n = from_f32<T>(to_f32(row[c]) * rs);
+      hid_out[c] = from_f32<T>(to_f32(from_f32<T>(norm_w[c])) * to_f32(n));
+    }
+  }
+  if (rew_out && tid < 64) {
+    float s = 0.f, ss = 0.f;
+    for (int c = tid; c < H; c += 64) { const float v = to_f32(row[c]); s = fmaf(v, rew_w[c], s); ss = fmaf(v, v, ss); }
+    s = wave_sum(s);
+    ss = wave_sum(ss);
+    if (tid == 0) {
+      // rowdot_kernel rounds the product before it adds the bias (its select keeps the two apart): no contraction into an fma here
+#pragma clang fp contract(off)
+      const float r = s * rsqrtf(ss / (float)H + eps);
+      *rew_out = r + rew_b[0];
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void frame_heads_kernel(const T* __restrict__ x, const StepState* __restrict__ state, const float* __restrict__ rew_w,
                                                           const float* __restrict__ rew_b, const float* __restrict__ norm_w,
@@ -2076,33 +2112,8 @@ __global__ __launch_bounds__(256) void frame_heads_kernel(const T* __restrict__ 
   const int i = j / 17;
   if (i >= F) return;
   __shared__ float red[4];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const T* row = x + (long)b * H;
-  if (hid) {
-    float ss = 0.f;
-    for (int c = tid; c < H; c += 256) { const float v = to_f32(row[c]); ss = fmaf(v, v, ss); }
-    ss = wave_sum(ss);
-    if ((tid & 63) == 0) red[tid >> 6] = ss;
-    __syncthreads();
-    const float rs = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + eps);
-    T* out = hid + ((long)b * F + i) * H;
-    for (int c = tid; c < H; c += 256) {
-      const T n = from_f32<T>(to_f32(row[c]) * rs);
-      out[c] = from_f32<T>(to_f32(from_f32<T>(norm_w[c])) * to_f32(n));
-    }
-  }
-  if (rew && tid < 64) {
-    float s = 0.f, ss = 0.f;
-    for (int c = tid; c < H; c += 64) { const float v = to_f32(row[c]); s = fmaf(v, rew_w[c], s); ss = fmaf(v, v, ss); }
-    s = wave_sum(s);
-    ss = wave_sum(ss);
-    if (tid == 0) {
-      // rowdot_kernel rounds the product before it adds the bias (its select keeps the two apart): no contraction into an fma here
-#pragma clang fp contract(off)
-      const float r = s * rsqrtf(ss / (float)H + eps);
-      rew[(long)b * F + i] = r + rew_b[0];
-    }
-  }
+  const int b = blockIdx.x;
+  frame_heads_row<T>(x + (long)b * H, rew_w, rew_b, norm_w, rew ? rew + (long)b * F + i : nullptr, hid ? hid + ((long)b * F + i) * H : nullptr, H, eps, red);
 }
 
 int launch_frame_heads(const void* x, const StepState* state, const float* rew_w, const float* rew_b, const float* norm_w, float* rew, void* hid,
@@ -2111,6 +2122,36 @@ int launch_frame_heads(const void* x, const StepState* state, const float* rew_w
   if ((rew && !(rew_w && rew_b)) || (hid && !norm_w)) return (int)hipErrorInvalidValue;
   if (dt == BF16) hipLaunchKernelGGL(frame_heads_kernel<bf16_t>, dim3(B), dim3(256), 0, st, (const bf16_t*)x, state, rew_w, rew_b, norm_w, rew, (bf16_t*)hid, H, F, eps);
   else hipLaunchKernelGGL(frame_heads_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)x, state, rew_w, rew_b, norm_w, rew, (float*)hid, H, F, eps);
+  return (int)hipGetLastError();
+}
+
+// The same heads on residual rows picked out of a matrix of rows (ivg_kv_extend_scored): workgroup (b, k) = (blockIdx.x / F, blockIdx.x % F)
+// reads row row0 + b * row_stride + k * frame_stride of x and writes rew[b * out_F + out_k0 + k] and hid[b * out_F + out_k0 + k][:] -- the
+// caller's own buffers.  The chunk pass: rows b * T + (q_i - keep_len) of its residual stream, all frames in one launch (frame_stride 17);
+// a decode step that fed a frame's 16th token: the B rows of the step buffer, F = 1, out_k0 the frame's column.
+template <typename T>
+__global__ __launch_bounds__(256) void frame_rows_heads_kernel(const T* __restrict__ x, long row0, long row_stride, long frame_stride,
+                                                               const float* __restrict__ rew_w, const float* __restrict__ rew_b,
+                                                               const float* __restrict__ norm_w, float* __restrict__ rew, T* __restrict__ hid,
+                                                               int H, int F, int out_k0, int out_F, float eps) {
+  __shared__ float red[4];
+  const long b = blockIdx.x / F, k = blockIdx.x - b * F;
+  const long o = b * out_F + out_k0 + k;
+  frame_heads_row<T>(x + (row0 + b * row_stride + k * frame_stride) * H, rew_w, rew_b, norm_w, rew ? rew + o : nullptr, hid ? hid + o * H : nullptr, H,
+                     eps, red);
+}
+
+int launch_frame_rows_heads(const void* x, long row0, long row_stride, long frame_stride, const float* rew_w, const float* rew_b, const float* norm_w,
+                            float* rew, void* hid, int B, int H, int F, int out_k0, int out_F, float eps, DType dt, hipStream_t st) {
+  if (B <= 0 || F <= 0 || (!rew && !hid)) return 0;
+  if ((rew && !(rew_w && rew_b)) || (hid && !norm_w) || out_k0 < 0 || out_k0 + F > out_F) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)B * (unsigned)F);
+  if (dt == BF16)
+    hipLaunchKernelGGL(frame_rows_heads_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, row0, row_stride, frame_stride, rew_w, rew_b, norm_w, rew,
+                       (bf16_t*)hid, H, F, out_k0, out_F, eps);
+  else
+    hipLaunchKernelGGL(frame_rows_heads_kernel<float>, grid, dim3(256), 0, st, (const float*)x, row0, row_stride, frame_stride, rew_w, rew_b, norm_w, rew,
+                       (float*)hid, H, F, out_k0, out_F, eps);
   return (int)hipGetLastError();
 }
 
@@ -2128,19 +2169,9 @@ long long frame_heads_hits() { return g_frame_heads_hits.load(); }
 // alignment (16-, 8- or 4-byte loads), and the sums run in one fixed order (thread, wave butterfly, waves 0..3): no atomics, the same
 // bits on every run, in a replayed graph and for a row at any place in the batch.  The sampler's own instances are untouched.
 constexpr int SCORE_GROUPS = 18;   // 4 logits each: vocab <= 256 * 72, the sampler's own limit
-__global__ __launch_bounds__(256) void token_scores_kernel(const float* __restrict__ logits, int V, const StepState* __restrict__ state,
-                                                           const int64_t* __restrict__ ids, long ids_stride, int L0, int forced_period,
-                                                           float* __restrict__ out, int cols) {
-  const int j = state->j;
-  if (j < 1 || j > cols) return;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float* o = out + ((long)b * cols + (j - 1)) * 3;
-  if (forced_period > 0 && j % forced_period == 0) {
-    if (tid < 3) o[tid] = 0.f;
-    return;
-  }
-  __shared__ float red[12];
-  const float* row = logits + (long)b * V;
+// The three scores of one logits row against the id `tok`, by a workgroup of 256 threads (red: 12 floats of LDS); thread 0 writes o[0..2]
+__device__ __forceinline__ void token_scores_row(const float* __restrict__ row, int V, long tok, float* __restrict__ o, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int al = (int)(((uintptr_t)row) & 15);
   float v[4 * SCORE_GROUPS];
 #pragma unroll
@@ -2179,7 +2210,6 @@ __global__ __launch_bounds__(256) void token_scores_kernel(const float* __restri
   if (tid == 0) {
     s = (red[4] + red[5]) + (red[6] + red[7]);
     t = (red[8] + red[9]) + (red[10] + red[11]);
-    const long tok = ids[(long)b * ids_stride + L0 + (j - 1)];
     const float ls = logf(s), nan = __int_as_float(0x7fc00000);
     const bool ok = mx > -INFINITY && mx < INFINITY;   // (a NaN among finite entries reaches s and t by itself)
     o[0] = ok && tok >= 0 && tok < V ? (row[tok] - mx) - ls : nan;
@@ -2188,11 +2218,53 @@ __global__ __launch_bounds__(256) void token_scores_kernel(const float* __restri
   }
 }
 
+__global__ __launch_bounds__(256) void token_scores_kernel(const float* __restrict__ logits, int V, const StepState* __restrict__ state,
+                                                           const int64_t* __restrict__ ids, long ids_stride, int L0, int forced_period,
+                                                           float* __restrict__ out, int cols) {
+  const int j = state->j;
+  if (j < 1 || j > cols) return;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  float* o = out + ((long)b * cols + (j - 1)) * 3;
+  if (forced_period > 0 && j % forced_period == 0) {
+    if (tid < 3) o[tid] = 0.f;
+    return;
+  }
+  __shared__ float red[12];
+  token_scores_row(logits + (long)b * V, V, ids[(long)b * ids_stride + L0 + (j - 1)], o, red);
+}
+
 int launch_token_scores(const float* logits, int V, const StepState* state, const int64_t* ids, long ids_stride, int L0, int forced_period,
                         float* out, int cols, int B, hipStream_t st) {
   if (B <= 0 || cols <= 0) return 0;
   if (!logits || !ids || !out || V < 1 || V > 256 * 4 * SCORE_GROUPS) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(token_scores_kernel, dim3(B), dim3(256), 0, st, logits, V, state, ids, ids_stride, L0, forced_period, out, cols);
+  return (int)hipGetLastError();
+}
+
+// The same scores per row of a chunk of teacher-forced logits rows whose targets are given ids (ivg_kv_extend_scored): chunk row i is row
+// r = row0 + i of [B][Tc] rows, (b, c) = (r / Tc, r % Tc), as token_nll_kernel; its target is ids[b][c] and its scores go to
+// out[(b * out_ld + c) * 3 ..].  Column c is forced (three zeros, the row is not read) when period > 0, c >= first_forced and
+// (c - first_forced) % period == 0.
+__global__ __launch_bounds__(256) void token_scores_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ ids, long ids_stride,
+                                                                long row0, int Tc, int V, int first_forced, int period,
+                                                                float* __restrict__ out, long out_ld) {
+  const long r = row0 + blockIdx.x;
+  const long b = r / Tc, c = r - b * Tc;
+  float* o = out + (b * out_ld + c) * 3;
+  if (period > 0 && c >= first_forced && (c - first_forced) % period == 0) {
+    if (threadIdx.x < 3) o[threadIdx.x] = 0.f;
+    return;
+  }
+  __shared__ float red[12];
+  token_scores_row(logits + (long)blockIdx.x * V, V, ids[b * ids_stride + c], o, red);
+}
+
+int launch_token_scores_rows(const float* logits, const int64_t* ids, long ids_stride, long row0, int rows, int Tc, int V, int first_forced, int period,
+                             float* out, long out_ld, hipStream_t st) {
+  if (rows <= 0) return 0;
+  if (!logits || !ids || !out || Tc < 1 || row0 < 0 || V < 1 || V > 256 * 4 * SCORE_GROUPS || first_forced < 0 || period < 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(token_scores_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, ids, ids_stride, row0, Tc, V, first_forced, period, out,
+                     out_ld);
   return (int)hipGetLastError();
 }
 

@@ -77,6 +77,8 @@ int launch_chunk_attn(const void* qkv, const void* kc, const void* vc, void* out
                       DType dt, hipStream_t st);
 void kv_extend_note(int chunk_rows, int step_rows);   // B * T of an ivg_kv_extend by route (test hook, ivg_debug_counter("kv_extend_chunk_rows" / "_step_rows"))
 long long kv_extend_rows(int stepwise);
+void kv_extend_heads_note(int frame_rows, int scored_rows);   // B * F_out / B * T of an ivg_kv_extend_scored (test hook, "kv_extend_frame_rows" / "_scored_rows")
+long long kv_extend_heads_rows(int scored);
 // tokenizer attention in one pass (bf16): cross-attention, 4 heads of 32 / 64 / 128 / 192 channels, and the single-head
 // self-attention of the conditional mid blocks (512 / 768 channels; M frames attending to themselves: F = 1, B = M); -1 = not covered
 int launch_xattn(const void* q, const void* Kp, const void* VpT, void* out, int M, int F, int P, int kv, int C, int nh, DType dt, hipStream_t st);
@@ -144,6 +146,11 @@ int launch_final_hidden(const void* x, const float* w, void* out, int B, int H, 
 // floats / [B][F][H] T, either may be null
 int launch_frame_heads(const void* x, const StepState* state, const float* rew_w, const float* rew_b, const float* norm_w, float* rew, void* hid,
                        int B, int H, int F, float eps, DType dt, hipStream_t st);
+// the same heads on residual rows picked out of a matrix (ivg_kv_extend_scored): workgroup (b, k), b < B, k < F, reads row
+// row0 + b * row_stride + k * frame_stride of x and writes rew[b * out_F + out_k0 + k], hid[b * out_F + out_k0 + k][:] -- on a given row
+// the bits of launch_rowdot / launch_final_hidden
+int launch_frame_rows_heads(const void* x, long row0, long row_stride, long frame_stride, const float* rew_w, const float* rew_b, const float* norm_w,
+                            float* rew, void* hid, int B, int H, int F, int out_k0, int out_F, float eps, DType dt, hipStream_t st);
 void frame_heads_note(int hits);   // the host's count of the launches above that hit a frame (test hook, ivg_debug_counter("frame_heads"))
 long long frame_heads_hits();
 // token scores of a rollout (ivg_generate_scored), launched directly after launch_sample_embed: out[b][j - 1][0..2] = { logprob of the
@@ -151,6 +158,11 @@ long long frame_heads_hits();
 // column (j % forced_period == 0), nothing for j = 0 or j > cols.  out: [B][cols][3] floats
 int launch_token_scores(const float* logits, int V, const StepState* state, const int64_t* ids, long ids_stride, int L0, int forced_period,
                         float* out, int cols, int B, hipStream_t st);
+// launch_token_scores' row arithmetic per row of a chunk of logits rows whose targets are given ids, addressed as launch_token_nll's rows:
+// scores of chunk row i = row r = row0 + i to out[((r / Tc) * out_ld + r % Tc) * 3 ..]; column c = r % Tc is three zeros when
+// period > 0, c >= first_forced and (c - first_forced) % period == 0
+int launch_token_scores_rows(const float* logits, const int64_t* ids, long ids_stride, long row0, int rows, int Tc, int V, int first_forced, int period,
+                             float* out, long out_ld, hipStream_t st);
 void token_scores_note(int launches);   // the host's count of the launches above (test hook, ivg_debug_counter("token_scores"))
 long long token_scores_launches();
 // eval heads: shifted cross-entropy per row of a logits chunk, per-trajectory (sum, count), action reconstruction squared error

@@ -190,12 +190,16 @@ int Run::prefill(const PrefillReq& q) {
     if (!e->final_norm) return e->fail(IVG_ERR_MISSING, "hidden states requested but 'llm.norm' is not in the weight table");
     CK(launch_final_hidden(x, e->final_norm, q.hidden_all, (int)M, H, c.rms_norm_eps, dt, st));
   }
+  // frame heads of an append pass: only the fr_F residual rows per trajectory that fed a frame's 16th token (not a norm over all M rows)
+  if ((q.frame_rew || q.frame_hid) && q.fr_F > 0 && !planning)
+    CK(launch_frame_rows_heads(x, q.fr_row0, L, 17, e->rew_w, e->rew_b, e->final_norm, q.frame_rew, q.frame_hid, B, H, q.fr_F, 0, q.fr_F,
+                               c.rms_norm_eps, dt, st));
   if (q.logits_all) {
     if (!planning) CK(launch_add_rmsnorm(x, H, e->ones, xn, (int)M, H, c.rms_norm_eps, dt, st));
     ConvW wl; wl.w = e->lm_head; wl.cin = H; wl.cout = V;
     IVG_TRY(linear(dt, xn, M, wl, q.logits_all, nullptr, 0, 1));
   }
-  if (q.token_nll) {
+  if (q.token_nll || q.token_scores) {
     // loss without the [B][L][V] fp32 logits tensor (3.1 GB at B = 64, L = 751): lm_head over chunks of rows, each chunk reduced
     // to its per-position cross-entropy before the next one overwrites it
     const long Rc = std::min<long>(M, 4096);
@@ -206,8 +210,12 @@ int Run::prefill(const PrefillReq& q) {
       const long rows = std::min(Rc, M - r0);
       IVG_TRY(linear(dt, xn + (size_t)r0 * H * esz(dt), rows, wl, chunk, nullptr, 0, 1));
       if (planning) continue;
-      if (q.next_ids) CK(launch_token_nll(chunk, q.next_ids, q.ids_stride, r0, (int)rows, L, V, q.token_nll, L, st));
-      else CK(launch_ce_rows(chunk, q.labels, r0, (int)rows, L, V, q.token_nll, st));
+      if (q.token_nll) {
+        if (q.next_ids) CK(launch_token_nll(chunk, q.next_ids, q.ids_stride, r0, (int)rows, L, V, q.token_nll, L, st));
+        else CK(launch_ce_rows(chunk, q.labels, r0, (int)rows, L, V, q.token_nll, st));
+      }
+      if (q.token_scores)
+        CK(launch_token_scores_rows(chunk, q.next_ids, q.ids_stride, r0, (int)rows, L, V, q.ts_first_forced, q.ts_period, q.token_scores, L, st));
     }
   }
   if (q.logits_last && !planning) {
@@ -643,6 +651,14 @@ bool kv_extend_chunk_covers(const ivg_engine* e) {
   return sw().kv_extend_chunk && e->kvc.format == KvFormat::Native && e->llm_dt == BF16 && e->hd == 64;   // IVG_KV_EXTEND_CHUNK=0: decode steps (A/B tests)
 }
 
+int kv_extend_frames(int keep_len, int L0, int ctx, int* i_first) {
+  const int q0 = 257 * ctx + 15;
+  const int first = keep_len <= q0 ? 0 : (keep_len - q0 + 16) / 17;
+  if (i_first) *i_first = first;
+  if (L0 - 2 < q0) return 0;
+  return std::max(0, (L0 - 2 - q0) / 17 - first + 1);
+}
+
 // Teacher-forces positions [keep_len, L0 - 1) onto the kept cache.  chunk: one pass over the B * T rows through Run::prefill's layers
 // (append mode: RoPE at keep_len, chunk_attn_kernel).  Otherwise T eager decode steps whose input rows are given instead of sampled --
 // exactly the launches generate's own steps make after the sampler, so the appended rows are bit for bit what a rollout that had
@@ -653,13 +669,24 @@ int Run::extend(const ExtendReq& q) {
   const int H = c.hidden_size, V = c.vocab_size, B = q.B, T = q.L0 - 1 - q.keep_len, A = c.action_dim;
   const size_t es = esz(dt);
   const GenBuf g = gen_buf(e);
+  // ivg_kv_extend_scored: frames i_first .. i_first + F_out - 1 have their 16th token among the fed positions; score column c has its
+  // target at position keep_len + c + 1, forced (under the forced schedule: actions given) when that is an sdf slot
+  int i_first = 0;
+  const bool want_frames = q.frame_rewards || q.frame_hidden;
+  const int F_out = want_frames ? kv_extend_frames(q.keep_len, q.L0, q.ctx, &i_first) : 0;
+  const int q_first = 257 * q.ctx + 17 * i_first + 15;
+  const int slot_d = q.keep_len + 1 - (257 * q.ctx - 1);   // (target of column 0) - (first sdf slot)
+  const int first_forced = slot_d <= 0 ? -slot_d : (17 - slot_d % 17) % 17, period = q.actions ? 17 : 0;
   if (!planning) e->kvc.forget_kept();   // rows from keep_len on are about to be overwritten; kept again once every launch is queued
   if (!planning && q.actions) CK(launch_action_embed(q.actions, e->act_w, e->act_b, g.act_emb, dt, B * q.act_T, A, H, st));
   if (q.chunk) {
     PrefillReq p; p.ids = q.prompt + q.keep_len; p.ids_stride = q.prompt_stride; p.B = B; p.L = T; p.ctx = q.ctx;
     p.act_emb = q.actions ? g.act_emb : nullptr; p.act_T = q.act_T; p.all_slots = true;
     p.append = true; p.pos0 = q.keep_len;
-    if (q.token_nll) { p.token_nll = q.token_nll; p.next_ids = q.prompt + q.keep_len + 1; }
+    if (q.token_nll || q.token_scores) p.next_ids = q.prompt + q.keep_len + 1;
+    p.token_nll = q.token_nll;
+    p.token_scores = q.token_scores; p.ts_first_forced = first_forced; p.ts_period = period;
+    if (F_out > 0) { p.frame_rew = q.frame_rewards; p.frame_hid = q.frame_hidden; p.fr_row0 = q_first - q.keep_len; p.fr_F = F_out; }
     IVG_TRY(prefill(p));
   } else if (!planning) {
     CK(launch_state_set(g.state, q.keep_len, 0, st));   // (every step's lm_head advances the position)
@@ -673,6 +700,16 @@ int Run::extend(const ExtendReq& q) {
         CK(launch_add_rows(g.x, H, g.act_emb + (size_t)(slot / 17 + q.ctx - 1) * H * es, (long)q.act_T * H, B, H, dt, st));
       IVG_TRY(step_body(e, st, g, plain, B, none, true, true));
       if (q.token_nll) CK(launch_token_nll(g.logits, q.prompt + pos + 1, q.prompt_stride, 0, B, 1, V, q.token_nll + t, T, st));
+      // the heads of ivg_kv_extend_scored, launched by the host (these steps are eager): g.x is the residual row this step left (lm_head
+      // only reads it), g.logits the row the next decision would read -- what the rollout's own steps hand frame_heads_kernel and
+      // token_scores_kernel
+      if (F_out > 0 && pos >= q_first && (pos - q_first) % 17 == 0 && (pos - q_first) / 17 < F_out)
+        CK(launch_frame_rows_heads(g.x, 0, 1, 0, e->rew_w, e->rew_b, e->final_norm, q.frame_rewards, q.frame_hidden, B, H, 1, (pos - q_first) / 17, F_out,
+                                   c.rms_norm_eps, dt, st));
+      if (q.token_scores) {
+        const bool forced = period > 0 && t >= first_forced && (t - first_forced) % period == 0;
+        CK(launch_token_scores_rows(g.logits, q.prompt + pos + 1, q.prompt_stride, 0, B, 1, V, 0, forced ? 1 : 0, q.token_scores + (size_t)t * 3, T, st));
+      }
     }
   }
   if (planning) return 0;
@@ -683,6 +720,7 @@ int Run::extend(const ExtendReq& q) {
   if (q.actions) CK((int)hipMemcpyAsync(g.last_act, q.actions, (size_t)B * q.act_T * A * 4, hipMemcpyDeviceToDevice, st));
   e->kvc.keep(q.L0 - 1, B, false, q.actions ? q.act_T : 0, q.ctx);
   kv_extend_note(q.chunk ? B * T : 0, q.chunk ? 0 : B * T);
+  kv_extend_heads_note(B * F_out, q.token_scores ? B * T : 0);
   return 0;
 }
 

@@ -376,15 +376,22 @@ class Engine:
                                                         int(p.size) if p is not None else 0, s), "kv_snapshot_restore")
         return self
 
-    def kv_extend(self, prompt, keep_len, actions=None, ctx=1, token_nll=None):
+    def kv_extend(self, prompt, keep_len, actions=None, ctx=1, token_nll=None, token_scores=None, frame_rewards=None, frame_hidden=None):
         """``ivg_kv_extend``: positions [keep_len, L0 - 1) of ``prompt`` (B, L0) teacher-forced onto the kept K / V cache (``keep_len`` ==
-        L0 - 1: a rewind); ``token_nll`` (B, L0 - 1 - keep_len) float32 receives the model's surprise at each given token."""
+        L0 - 1: a rewind); ``token_nll`` (B, L0 - 1 - keep_len) float32 receives the model's surprise at each given token.  With
+        ``token_scores`` (B, T, 3) float32, ``frame_rewards`` (B, F_out) float32 or ``frame_hidden`` (B, F_out, hidden) in the llm dtype
+        the call is ``ivg_kv_extend_scored``'s (``transformer.extend_frames`` gives F_out)."""
         B, L0 = prompt.shape
         act_T = actions.shape[1] if actions is not None else 0
         with self.stream() as s:
-            self.check(self.lib.ivg_kv_extend(self.h, _ptr(prompt), prompt.stride(0), B, int(keep_len), L0, _ptr(actions), act_T, int(ctx),
-                                              _ptr(token_nll), s), "kv_extend")
-            self._record(prompt, actions, token_nll)
+            if token_scores is None and frame_rewards is None and frame_hidden is None:
+                self.check(self.lib.ivg_kv_extend(self.h, _ptr(prompt), prompt.stride(0), B, int(keep_len), L0, _ptr(actions), act_T, int(ctx),
+                                                  _ptr(token_nll), s), "kv_extend")
+            else:
+                self.check(self.lib.ivg_kv_extend_scored(self.h, _ptr(prompt), prompt.stride(0), B, int(keep_len), L0, _ptr(actions), act_T, int(ctx),
+                                                         _ptr(token_nll), _ptr(token_scores), _ptr(frame_rewards), _ptr(frame_hidden), s),
+                           "kv_extend_scored")
+            self._record(prompt, actions, token_nll, token_scores, frame_rewards, frame_hidden)
         return self
 
     def rollout(self, prompt, n_new, out, *, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,

@@ -14,7 +14,7 @@ All compute is in libivg (HIP); this file is tensor plumbing and checkpoint I/O.
 """
 import math
 from types import SimpleNamespace
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -141,6 +141,28 @@ def _token_scores_of(ts, t=1, B0=1, n=None):
     """(B, n_new, 3) in the engine's row order -> TokenScores of (B, n) in the caller's"""
     ts = _from_group_major(ts, t, B0)
     return TokenScores(*(ts[:, :n, k].contiguous() for k in range(3)))
+
+
+class ExtendOutputs(NamedTuple):
+    """``extend_kept_cache`` with any of ``output_frame_hidden_states``, ``output_token_scores``, ``return_reward="frames"``
+    (include/ivg.h ivg_kv_extend_scored): what the model thinks of the tokens it was GIVEN.  ``token_nll`` (B, T) as ``return_nll``;
+    ``frame_rewards`` (B, F) and ``frame_hidden`` (B, F, hidden) for the F frames whose 16th token the call fed (``extend_frames``);
+    ``token_scores``: ``TokenScores`` of (B, T), column c scoring ``input_ids[:, keep + c + 1]``.  None what was not asked for."""
+    token_nll: Optional[torch.Tensor]
+    frame_rewards: Optional[torch.Tensor]
+    frame_hidden: Optional[torch.Tensor]
+    token_scores: Optional[TokenScores]
+
+
+def extend_frames(keep, L0, ctx):
+    """-> ``(i_first, F_out)``: the predicted frames (0-based after the ``ctx`` context frames) whose 16th token, position
+    ``257 * ctx + 17 * i + 15``, is among the positions [keep, L0 - 1) an ``extend_kept_cache(input_ids (B, L0), keep=keep)`` feeds --
+    frames ``i_first .. i_first + F_out - 1``, the columns of its frame outputs."""
+    q0 = 257 * int(ctx) + 15
+    first = 0 if keep <= q0 else (keep - q0 + 16) // 17
+    if L0 - 2 < q0:
+        return first, 0
+    return first, max(0, (L0 - 2 - q0) // 17 - first + 1)
 
 
 def _top_p_of(top_p, do_sample):
@@ -524,27 +546,36 @@ class LlamaForCausalLM:
             raise ValueError(f"restore_kept_cache: {err}") from None
         return self
 
-    def extend_kept_cache(self, input_ids, keep, return_nll=False, _actions=None, _ctx=1):
+    def extend_kept_cache(self, input_ids, keep, return_nll=False, output_frame_hidden_states=False, output_token_scores=False, _actions=None,
+                          _ctx=1, _frame_rewards=False):
         """Appends GIVEN tokens to the KV cache the last ``generate`` call kept (include/ivg.h ivg_kv_extend): afterwards it holds
         ``input_ids[:, :-1]``, of which positions [0, keep) are the kept rows as they were (verified on the device) and [keep, L0 - 1)
         are teacher-forced by this call -- a following ``generate`` on the kept cache (``HeadModelWithAction.generate(reuse_cache=True)``),
         ``select_kept_cache``, ``fan_out`` or another extend then accepts ``input_ids``.  ``keep == L0 - 1`` only rewinds the cache to
         that length.  ``return_nll=True``: -> float32 (B, L0 - 1 - keep), ``-log p(input_ids[:, p + 1] | input_ids[:, :p + 1])`` for
-        p = keep .. L0 - 2, the model's surprise at each given token; else None.  ValueError, with the kept cache untouched, where the
-        engine refuses: no kept cache built from ids, another batch, ``keep`` outside [1, min(kept length, L0 - 1)], other tokens."""
+        p = keep .. L0 - 2, the model's surprise at each given token; else None.  ``output_frame_hidden_states`` /
+        ``output_token_scores`` (include/ivg.h ivg_kv_extend_scored): -> ``ExtendOutputs`` instead.  ValueError, with the kept cache
+        untouched, where the engine refuses: no kept cache built from ids, another batch, ``keep`` outside [1, min(kept length, L0 - 1)],
+        other tokens."""
         if self._engine is None:
             raise ValueError("extend_kept_cache: no kept cache (the model has not generated yet)")
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
-        T = L0 - 1 - int(keep)
+        T = max(L0 - 1 - int(keep), 0)
         nll = torch.empty(B, T, dtype=torch.float32, device=self.device) if return_nll and T > 0 else None
+        F = extend_frames(int(keep), L0, _ctx)[1] if T > 0 else 0
+        ts = _token_scores_buffer(B, T, self.device) if output_token_scores else None
+        fr = torch.empty(B, F, dtype=torch.float32, device=self.device) if _frame_rewards else None
+        fh = torch.empty(B, F, self._cfg["hidden_size"], dtype=self.torch_dtype, device=self.device) if output_frame_hidden_states else None
         try:
-            self._engine.kv_extend(ids, keep, actions=_actions, ctx=_ctx, token_nll=nll)
+            self._engine.kv_extend(ids, keep, actions=_actions, ctx=_ctx, token_nll=nll, token_scores=ts, frame_rewards=fr, frame_hidden=fh)
         except (AssertionError, _lib.IvgError) as err:
             raise ValueError(f"extend_kept_cache: {err}") from None
-        if return_nll:
-            return nll if nll is not None else torch.empty(B, 0, dtype=torch.float32, device=self.device)
-        return None
+        if return_nll and nll is None:
+            nll = torch.empty(B, 0, dtype=torch.float32, device=self.device)
+        if ts is None and fr is None and fh is None:
+            return nll if return_nll else None
+        return ExtendOutputs(nll if return_nll else None, fr, fh, _token_scores_of(ts) if ts is not None else None)
 
     def _fan_out(self, ids, samples, act, ctx, gk, force_sdf=False):
         """``fan_out`` of both classes: ``ivg_generate_fanout`` under ``generate``'s keywords.  Rows b * samples + k throughout (the
@@ -826,15 +857,23 @@ class HeadModelWithAction:
         self.llm.restore_kept_cache(kept, parents)
         return self
 
-    def extend_kept_cache(self, inputs_token, action=None, keep=None, return_nll=False):
+    def extend_kept_cache(self, inputs_token, action=None, keep=None, return_nll=False, return_reward=False, output_frame_hidden_states=False,
+                          output_token_scores=False):
         """``LlamaForCausalLM.extend_kept_cache`` with ``action_linear(action[:, i + context - 1])`` added on the i-th sdf slot among
         the appended positions, as ``generate`` does; ``action`` (B, T, D) becomes the kept action table, and its rows of the slots
         before ``keep`` must equal the kept ones.  ``keep`` is required.  Continue with ``generate(inputs_token, action=action,
-        reuse_cache=True)``."""
+        reuse_cache=True)``.  ``return_reward="frames"``, ``output_frame_hidden_states``, ``output_token_scores``: -> ``ExtendOutputs``,
+        the values ``generate`` returns for imagined frames, here for the given ones (forced ``sdf`` columns score 0)."""
         if keep is None:
             raise ValueError("extend_kept_cache: keep (the number of kept positions to keep) is required")
+        if return_reward not in (False, "frames"):
+            raise ValueError("extend_kept_cache: return_reward must be False or 'frames'")
+        if return_reward == "frames" and not self.reward_prediction:
+            raise ValueError("return_reward='frames' needs a model with reward_prediction=True")
         act = action.to(device=self.llm.device, dtype=torch.float32).contiguous() if action is not None else None
-        return self.llm.extend_kept_cache(inputs_token, keep, return_nll=return_nll, _actions=act, _ctx=self.context)
+        return self.llm.extend_kept_cache(inputs_token, keep, return_nll=return_nll, output_frame_hidden_states=output_frame_hidden_states,
+                                          output_token_scores=output_token_scores, _actions=act, _ctx=self.context,
+                                          _frame_rewards=return_reward == "frames")
 
     @torch.no_grad()
     def fan_out(self, inputs_token, samples, action=None, **generate_kwargs):

@@ -16,6 +16,7 @@ Not in the reference: ``rollout_actions`` (open-loop plans in three calls) and `
 caller that acts, observes and re-plans, on the encoder's context cache and the transformer's kept cache."""
 import os
 import sys
+from typing import NamedTuple
 
 import torch
 
@@ -83,6 +84,18 @@ def load_models(args):
         else:
             model.load_state_dict(state_dict, strict=True)
     return model, tokenizer
+
+
+class Observation(NamedTuple):
+    """``TrackedEpisode.observe(..., return_outputs=True)``: the model's view of the frame it was just shown.  ``surprise`` (B,): the
+    sum of the frame's 16 token NLLs (the default return); ``reward`` (B, 1): ``reward_linear(hidden)``, through ``symexp`` under
+    ``symlog`` -- what ``plan`` reports for an imagined frame; ``hidden`` (B, H): the post-norm hidden state at the frame's 16th token,
+    the features at the root of the next plan; ``entropy`` (B,): the mean predictive entropy over the frame's 16 tokens
+    (``TokenScores.per_frame``), to set beside ``plan``'s uncertainty."""
+    surprise: torch.Tensor
+    reward: torch.Tensor
+    hidden: torch.Tensor
+    entropy: torch.Tensor
 
 
 class TrackedEpisode:
@@ -178,10 +191,12 @@ class TrackedEpisode:
         return self.tokens.shape[0]
 
     @torch.no_grad()
-    def observe(self, frame, action):
+    def observe(self, frame, action, return_outputs=False):
         """The environment's answer to ``action``: ``frame`` [B, 3, H, W] in 0..255, ``action`` [B, A].  The frame is tokenized against
         the encoder cache and teacher-forced onto the kept cache (``extend_kept_cache`` with the action on its sdf slot).
-        -> float32 (B,): the model's surprise at that frame, the sum of its 16 token NLLs (nats).  ``tokens`` and ``steps`` advance.
+        -> float32 (B,): the model's surprise at that frame, the sum of its 16 token NLLs (nats); with ``return_outputs=True`` an
+        ``Observation`` -- that surprise, the reward and hidden state the model assigns to the frame and its predictive entropy, from
+        the same extend (no prompt pass).  ``tokens`` and ``steps`` advance.
         When the positions are used up, the last ``ctx`` frames observed SO FAR become the new context first (real frames: the model's
         own episode start; ``reanchors`` counts it) and this frame is its first step -- or, with ``on_full="raise"``, RuntimeError
         with the session as it was."""
@@ -197,10 +212,22 @@ class TrackedEpisode:
         table = self.table.clone()
         table[:, self.steps + ctx - 1] = action.to(p.device).float()
         tokens = torch.cat([self.tokens, dyn], 1)
-        nll = p.model.extend_kept_cache(tokens, action=table, keep=self.tokens.shape[1] - 1, return_nll=True)   # (B, 17); column 16: the forced sdf
+        keep = self.tokens.shape[1] - 1
+        if return_outputs:   # one frame: its 16th token is fed at column 15
+            out = p.model.extend_kept_cache(tokens, action=table, keep=keep, return_nll=True, output_frame_hidden_states=True, output_token_scores=True)
+            nll = out.token_nll
+        else:
+            nll = p.model.extend_kept_cache(tokens, action=table, keep=keep, return_nll=True)   # (B, 17); column 16: the forced sdf
         self.tokens, self.table, self.steps = tokens, table, self.steps + 1
         self.stack = self.stack[1:] + [frame]
-        return nll[:, :TOKENS_PER_DYN].sum(1)
+        surprise = nll[:, :TOKENS_PER_DYN].sum(1)
+        if not return_outputs:
+            return surprise
+        hidden = out.frame_hidden[:, 0]
+        reward = p.model.reward_linear(hidden)                                # (B, 1)
+        if p.symlog:
+            reward = symexp(reward)
+        return Observation(surprise, reward.float(), hidden, out.token_scores.per_frame()[1][:, 0])
 
     @torch.no_grad()
     def plan(self, plans, samples=1, return_uncertainty=False, uniforms=None, generator=None):
