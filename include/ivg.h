@@ -804,6 +804,61 @@ int ivg_op_lpips_head(const float* f0, const float* f1, const float* lin, int n0
                       ivg_stream stream);
 int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const float* bias, float* Y, int n, int H, int W, ivg_stream stream);
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream);
+
+/* FVD detector: Kinetics-400 Inception-I3D (csrc/i3d.hip), inference only, fp32 arithmetic on the f32-input MFMA.  The weights are the
+ * caller's: the engine ships none.  Engine-free; a handle is bound to one device and borrows the weight tensors until ivg_i3d_destroy.
+ *   weights  float32, 16-byte aligned, packed by ivideogpt_amd/packing.py pack_i3d: per convolution unit "<unit>.weight" (Cout, K) with
+ *            batch norm folded in and K ordered (kd, kh, kw, c), "<unit>.bias" (Cout); "logits.weight" (400, C), "logits.bias".  Units:
+ *            Conv3d_1a_7x7, Conv3d_2b_1x1, Conv3d_2c_3x3, Mixed_{3b,3c,4b..4f,5b,5c}.{b0,b1a,b1b,b2a,b2b,b3b}.  Channel counts are read
+ *            from the shapes.  A missing tensor: IVG_ERR_MISSING; one whose shape does not fit its place: IVG_ERR_INVALID; the text
+ *            in ivg_last_error(NULL) names it.
+ *   resize   side S every frame is resized to (bilinear, align_corners = False, no antialias) before the trunk; 0: no resize (H == W)
+ *   video    (B, T, 3, H, W) in [0, 1], IVG_F32 or IVG_BF16.  S must be a multiple of 32 and T leave two time steps in front of the
+ *            average pool (T >= 9): IVG_ERR_INVALID otherwise.
+ *   features_out  (B, 400) float32: the pre-softmax logits
+ *   ws       scratch; ivg_i3d_ws_bytes(h, n, T, H, W): bytes that carry n clips per chunk (0 for a shape the detector refuses).  The
+ *            batch is walked in chunks of as many clips as the scratch holds; a clip's features do not depend on the chunking, bit
+ *            for bit.  Too small for one clip: IVG_ERR_CAPACITY.
+ * Nothing is written when a status other than IVG_OK / IVG_ERR_HIP is returned. */
+typedef struct ivg_i3d ivg_i3d;
+int ivg_i3d_create(const ivg_tensor* weights, int n_weights, int device, int resize, ivg_i3d** out);
+void ivg_i3d_destroy(ivg_i3d* p);
+size_t ivg_i3d_ws_bytes(ivg_i3d* p, int max_clips, int T, int H, int W);
+int ivg_i3d_features(ivg_i3d* p, const void* video, int dtype, int B, int T, int H, int W, float* features_out, void* ws, size_t ws_bytes,
+                     ivg_stream stream);
+
+/* I3D pieces (csrc/i3d.hip); tensors are channels-last float32 [clip][d][h][w][c].
+ * ivg_op_conv3d: Y[.., coff + co] = act(sum_k X[..] W[co][k] + bias[co]), W (Cout, kd kh kw Cin) with K ordered (kd, kh, kw, c); any
+ *   Cin, Cout >= 1, kernel extents 1 .. 7, strides 1 / 2; p = the FRONT pad per axis, taps outside the tensor read 0; ldx / ldy: channel
+ *   strides of input and output, coff: first output channel written (nothing else of Y is touched).
+ * ivg_op_pool3d: max-pool with the same geometry fields; taps outside the tensor count as 0 (TensorFlow SAME padding).
+ * ivg_op_i3d_head: X (n, D, P, C) -> mean over (2, P) windows with stride 1 in time -> W (Nout, C) + bias -> mean over the D - 1 steps ->
+ *   out (n, Nout); D >= 2; ws of n (D - 1) C floats.
+ * ivg_op_i3d_ingest: frames (F, 3, H, W) in [0, 1] (IVG_F32 / IVG_BF16) -> (F, S, S, 3) = 2 bilinear(x) - 1.
+ * ivg_op_i3d_tap: the activation after unit `unit_index` of a full forward of ivg_i3d_features' arguments, (B, D, H, W, C) contiguous.
+ *   Units are numbered in execution order, pools included (Mixed: b0, b1a, b1b, b2a, b2b, b3a (pool), b3b); -1 is the front end's output.
+ *   dims_out[8] (may be NULL) = D, H, W, C and the up to four units whose outputs, concatenated on channels, the unit reads (-1: the
+ *   front end, -2: none).  out == NULL: the dims alone, nothing is launched.  ivg_i3d_units: the number of units. */
+typedef struct {
+  const float* X; const float* W; const float* bias; float* Y;
+  int32_t n, D, H, Wd, Cin, ldx, Do, Ho, Wo;
+  int32_t k[3], s[3], p[3];
+  int32_t Cout, ldy, coff, relu;
+} ivg_conv3d_args;
+typedef struct {
+  const float* X; float* Y;
+  int32_t n, D, H, Wd, C, ldx, Do, Ho, Wo;
+  int32_t k[3], s[3], p[3];
+  int32_t ldy, coff;
+} ivg_pool3d_args;
+int ivg_op_conv3d(const ivg_conv3d_args* a, ivg_stream stream);
+int ivg_op_pool3d(const ivg_pool3d_args* a, ivg_stream stream);
+int ivg_op_i3d_head(const float* X, const float* W, const float* bias, float* out, int n, int D, int P, int C, int Nout, void* ws, size_t ws_bytes,
+                    ivg_stream stream);
+int ivg_op_i3d_ingest(const void* video, int dtype, int frames, int H, int W, int S, float* out, ivg_stream stream);
+int ivg_op_i3d_tap(ivg_i3d* p, const void* video, int dtype, int B, int T, int H, int W, int unit_index, float* out, int64_t* dims_out, void* ws,
+                   size_t ws_bytes, ivg_stream stream);
+int ivg_i3d_units(ivg_i3d* p);
 /* test hook: launches since the library was loaded of the kernel family `name` selects ("decode_gemm_gen3" / "decode_gemm_gen2":
  * decode-step GEMMs the dispatcher sent to dgemm3.hip / dgemm.hip; "conv3x3_subpixel": upsampling convolutions run as four 2x2 phase
  * convolutions; "decode_attn24" / "decode_attn8": decode-attention launches over the 24-bit / FP8 cache; "lpips_trunk_images": images sent through the VGG-16 trunk of the LPIPS metric; "frame_heads": decode steps whose frame_heads_kernel hit a frame; "token_scores": token_scores_kernel launches, one per step that ran the sampler of a scored call; "kv_select_direct" / "kv_select_staged": trajectory rows ivg_kv_select / ivg_op_kv_select moved in place / through scratch; "kv_snapshot_rows_saved" / "kv_snapshot_rows_restored": trajectory rows ivg_kv_snapshot_create / _restore (and ivg_op_kv_snapshot) copied out / in; "kv_extend_chunk_rows" / "kv_extend_step_rows": B * T of the ivg_kv_extend calls that took the chunk pass / the decode steps; "kv_extend_frame_rows" / "kv_extend_scored_rows": B * F_out of the ivg_kv_extend_scored calls / B * T of those that asked for scores; "enc_plain_images" / "enc_cond_images": images sent through the plain / the conditional encoder trunk; "enc_kv_projections": cross-attention K / V projections made for an encoder, one per site and call) -- lets a test assert WHICH kernel produced the tensor it checked; -1 for an unknown name */

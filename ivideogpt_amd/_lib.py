@@ -54,6 +54,19 @@ class IvgIgemmArgs(C.Structure):
     ]
 
 
+class IvgConv3dArgs(C.Structure):
+    _fields_ = [("X", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("Y", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("n", "D", "H", "Wd", "Cin", "ldx", "Do", "Ho", "Wo")] + \
+               [("k", C.c_int32 * 3), ("s", C.c_int32 * 3), ("p", C.c_int32 * 3)] + \
+               [(k, C.c_int32) for k in ("Cout", "ldy", "coff", "relu")]
+
+
+class IvgPool3dArgs(C.Structure):
+    _fields_ = [("X", C.c_void_p), ("Y", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("n", "D", "H", "Wd", "C", "ldx", "Do", "Ho", "Wo")] + \
+               [("k", C.c_int32 * 3), ("s", C.c_int32 * 3), ("p", C.c_int32 * 3), ("ldy", C.c_int32), ("coff", C.c_int32)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "ivg_version": (C.c_char_p, []),
@@ -131,6 +144,16 @@ EXPORTS = {
     "ivg_op_lpips_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ivg_op_lpips_conv_in": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "ivg_op_maxpool2": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "ivg_i3d_create": (C.c_int, [C.POINTER(IvgTensor), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ivg_i3d_destroy": (None, [C.c_void_p]),
+    "ivg_i3d_units": (C.c_int, [C.c_void_p]),
+    "ivg_i3d_ws_bytes": (C.c_size_t, [C.c_void_p] + [C.c_int] * 4),
+    "ivg_i3d_features": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_op_i3d_tap": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_op_conv3d": (C.c_int, [C.POINTER(IvgConv3dArgs), C.c_void_p]),
+    "ivg_op_pool3d": (C.c_int, [C.POINTER(IvgPool3dArgs), C.c_void_p]),
+    "ivg_op_i3d_head": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ivg_op_i3d_ingest": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "ivg_profile_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ivg_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(IvgProfileStats)]),
     "ivg_profile_attn_fit": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -13,6 +13,8 @@ static thread_local std::string g_create_err;
 
 namespace ivg {
 
+void set_create_error(const std::string& s) { g_create_err = s; }
+
 size_t dtype_size(DType d) { return d == BF16 ? 2 : 4; }
 
 struct Lookup {
@@ -1156,6 +1158,78 @@ int ivg_op_lpips_conv_in(const void* images, int dtype, const float* w, const fl
 int ivg_op_maxpool2(const float* X, float* Y, int N, int H, int W, int C, ivg_stream stream) {
   if (!X || !Y || N <= 0 || H < 2 || W < 2 || H % 2 || W % 2 || C <= 0 || C % 4 || ((uintptr_t)X & 15) || ((uintptr_t)Y & 15)) return IVG_ERR_INVALID;
   return lpips_status(launch_maxpool2(X, Y, N, H, W, C, (hipStream_t)stream));
+}
+
+// ---- I3D (i3d.hip): a handle owns the unit table built from the caller's weight tensors
+struct ivg_i3d {
+  I3dNet* net = nullptr;
+};
+
+int ivg_i3d_create(const ivg_tensor* weights, int n_weights, int device, int resize, ivg_i3d** out) {
+  if (!out) return IVG_ERR_INVALID;
+  *out = nullptr;
+  if (!weights || n_weights <= 0) { g_create_err = "no weight table"; return IVG_ERR_MISSING; }
+  if (resize < 0) { g_create_err = "I3D: resize must be 0 (off) or the side the frames are resized to"; return IVG_ERR_INVALID; }
+  int status = IVG_OK;
+  I3dNet* net = i3d_create(weights, n_weights, device, resize, &status);
+  if (!net) return status;
+  *out = new ivg_i3d{net};
+  return IVG_OK;
+}
+
+void ivg_i3d_destroy(ivg_i3d* p) {
+  if (p) i3d_destroy(p->net);
+  delete p;
+}
+
+int ivg_i3d_units(ivg_i3d* p) { return p ? i3d_units(p->net) : IVG_ERR_INVALID; }
+
+size_t ivg_i3d_ws_bytes(ivg_i3d* p, int max_clips, int T, int H, int W) { return p ? i3d_ws_bytes(p->net, max_clips, T, H, W) : 0; }
+
+static int i3d_status(int rc) { return rc == 0 ? IVG_OK : (rc == -4 ? IVG_ERR_CAPACITY : (rc == -1 ? IVG_ERR_INVALID : IVG_ERR_HIP)); }
+
+int ivg_i3d_features(ivg_i3d* p, const void* video, int dtype, int B, int T, int H, int W, float* features_out, void* ws, size_t ws_bytes,
+                     ivg_stream stream) {
+  if (!p || !video || !features_out || !ws || B <= 0 || (dtype != IVG_F32 && dtype != IVG_BF16)) return IVG_ERR_INVALID;
+  if (i3d_check_shape(p->net, T, H, W)) return IVG_ERR_INVALID;
+  if (ws_bytes < i3d_ws_bytes(p->net, 1, T, H, W)) return IVG_ERR_CAPACITY;
+  return i3d_status(i3d_features(p->net, video, (DType)dtype, B, T, H, W, features_out, ws, ws_bytes, (hipStream_t)stream));
+}
+
+int ivg_op_i3d_tap(ivg_i3d* p, const void* video, int dtype, int B, int T, int H, int W, int unit_index, float* out, int64_t* dims_out, void* ws,
+                   size_t ws_bytes, ivg_stream stream) {
+  if (!p || B <= 0 || (dtype != IVG_F32 && dtype != IVG_BF16) || i3d_check_shape(p->net, T, H, W)) return IVG_ERR_INVALID;
+  if (out && (!video || !ws)) return IVG_ERR_INVALID;
+  if (out && ws_bytes < i3d_ws_bytes(p->net, 1, T, H, W)) return IVG_ERR_CAPACITY;
+  return i3d_status(i3d_tap(p->net, video, (DType)dtype, B, T, H, W, unit_index, out, dims_out, ws, ws_bytes, (hipStream_t)stream));
+}
+
+int ivg_op_conv3d(const ivg_conv3d_args* a, ivg_stream stream) {
+  if (!a) return IVG_ERR_INVALID;
+  Conv3dArgs c{a->X, a->W, a->bias, a->Y, a->n, a->D, a->H, a->Wd, a->Cin, a->ldx, a->Do, a->Ho, a->Wo, {a->k[0], a->k[1], a->k[2]},
+               {a->s[0], a->s[1], a->s[2]}, {a->p[0], a->p[1], a->p[2]}, a->Cout, a->ldy, a->coff, a->relu};
+  const int rc = launch_conv3d(c, (hipStream_t)stream);
+  return rc == 0 ? IVG_OK : (rc == (int)hipErrorInvalidValue ? IVG_ERR_INVALID : IVG_ERR_HIP);
+}
+
+int ivg_op_pool3d(const ivg_pool3d_args* a, ivg_stream stream) {
+  if (!a) return IVG_ERR_INVALID;
+  Pool3dArgs c{a->X, a->Y, a->n, a->D, a->H, a->Wd, a->C, a->ldx, a->Do, a->Ho, a->Wo, {a->k[0], a->k[1], a->k[2]}, {a->s[0], a->s[1], a->s[2]},
+               {a->p[0], a->p[1], a->p[2]}, a->ldy, a->coff};
+  const int rc = launch_pool3d(c, (hipStream_t)stream);
+  return rc == 0 ? IVG_OK : (rc == (int)hipErrorInvalidValue ? IVG_ERR_INVALID : IVG_ERR_HIP);
+}
+
+int ivg_op_i3d_head(const float* X, const float* W, const float* bias, float* out, int n, int D, int P, int C, int Nout, void* ws, size_t ws_bytes,
+                    ivg_stream stream) {
+  if (!X || !W || !bias || !out || !ws || n <= 0 || D < 2 || P <= 0 || C <= 0 || Nout <= 0 || ((uintptr_t)ws & 3)) return IVG_ERR_INVALID;
+  if (ws_bytes < i3d_head_ws_bytes(n, D, C)) return IVG_ERR_CAPACITY;
+  return launch_i3d_head(X, W, bias, out, n, D, P, C, Nout, (float*)ws, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
+}
+
+int ivg_op_i3d_ingest(const void* video, int dtype, int frames, int H, int W, int S, float* out, ivg_stream stream) {
+  if (!video || !out || frames <= 0 || H <= 0 || W <= 0 || S <= 0 || (dtype != IVG_F32 && dtype != IVG_BF16)) return IVG_ERR_INVALID;
+  return launch_i3d_ingest(video, (DType)dtype, out, frames, H, W, S, (hipStream_t)stream) ? IVG_ERR_HIP : IVG_OK;
 }
 
 int ivg_profile_attn_fit(ivg_engine* e, double* fixed_us, double* gbps) {

@@ -1,5 +1,6 @@
 // Host-side launchers of every hand-written kernel (all return hipError_t as int, 0 = ok).
 #pragma once
+#include "../../include/ivg.h"
 #include "common.h"
 #include "igemm.h"
 #include "kv_select_plan.h"
@@ -233,5 +234,39 @@ int launch_lpips_features(const float* const* cw, const float* const* cb, const 
 int launch_lpips_rows(const float* const* cw, const float* const* cb, const float* const* lin, const void* gt, DType gt_dt, int B, int T_gt, int gt_t0,
                       const float* pred, int n_samples, int T_pr, int pr_t0, int T, int H, int W, float* frames, float* rows, void* ws, size_t ws_bytes,
                       hipStream_t st);
+
+// ---- i3d.hip (Kinetics-400 Inception-I3D, the FVD detector: fp32, channels-last [clip][d][h][w][c])
+// conv3d: implicit GEMM on the f32-input MFMA, K = (kd, kh, kw, c); W [Cout][K], bias [Cout]; p: FRONT pad per axis (the back pad is the
+// bounds check); input channel stride ldx, output channel stride ldy and offset coff; any Cin, Cout >= 1; kernel extents 1 .. 7, strides 1 / 2
+struct Conv3dArgs {
+  const float* X; const float* W; const float* bias; float* Y;
+  int n, D, H, Wd, Cin, ldx, Do, Ho, Wo;
+  int k[3], s[3], p[3];
+  int Cout, ldy, coff, relu;
+};
+int launch_conv3d(const Conv3dArgs& a, hipStream_t st);
+// pool3d: max-pool whose out-of-tensor taps read 0 (TensorFlow SAME padding: the zeros take part in the maximum)
+struct Pool3dArgs {
+  const float* X; float* Y;
+  int n, D, H, Wd, C, ldx, Do, Ho, Wo;
+  int k[3], s[3], p[3];
+  int ldy, coff;
+};
+int launch_pool3d(const Pool3dArgs& a, hipStream_t st);
+// head: X (n, D, P pixels, C) -> mean over (2, P) windows, stride 1 in time -> W [Nout][C] + bias -> mean over the D - 1 steps -> out (n, Nout)
+size_t i3d_head_ws_bytes(int n, int D, int C);
+int launch_i3d_head(const float* X, const float* W, const float* bias, float* out, int n, int D, int P, int C, int Nout, float* ws, hipStream_t st);
+// front end: frames (F, 3, H, W) in [0, 1] -> (F, S, S, 3) fp32 = 2 * bilinear(x) - 1 (align_corners = False)
+int launch_i3d_ingest(const void* video, DType dt, float* Y, long frames, int H, int W, int S, hipStream_t st);
+struct I3dNet;
+I3dNet* i3d_create(const ivg_tensor* weights, int n_weights, int device, int resize, int* status_out);   // failure: nullptr, the text set through set_create_error
+void i3d_destroy(I3dNet* p);
+int i3d_features_dim(const I3dNet* p);
+int i3d_units(const I3dNet* p);
+int i3d_check_shape(const I3dNet* p, int T, int H, int W);
+size_t i3d_ws_bytes(const I3dNet* p, int max_clips, int T, int H, int W);
+int i3d_features(const I3dNet* p, const void* video, DType dt, int B, int T, int H, int W, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+int i3d_tap(const I3dNet* p, const void* video, DType dt, int B, int T, int H, int W, int unit, float* out, int64_t* dims, void* ws, size_t ws_bytes,
+            hipStream_t st);
 
 }  // namespace ivg

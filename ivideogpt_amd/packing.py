@@ -135,6 +135,51 @@ def unpack_lpips_conv(w_packed, cin):
     return w_packed.reshape(w_packed.shape[0], 3, 3, cin).permute(0, 3, 1, 2).contiguous()
 
 
+# Convolution units of the Kinetics-400 Inception-I3D in execution order (names only: kernel sizes live in csrc/i3d.hip's table,
+# channel counts in the weight shapes)
+I3D_MIXED = ("Mixed_3b", "Mixed_3c", "Mixed_4b", "Mixed_4c", "Mixed_4d", "Mixed_4e", "Mixed_4f", "Mixed_5b", "Mixed_5c")
+I3D_CONV_UNITS = ("Conv3d_1a_7x7", "Conv3d_2b_1x1", "Conv3d_2c_3x3") + tuple(f"{m}.{b}" for m in I3D_MIXED
+                                                                             for b in ("b0", "b1a", "b1b", "b2a", "b2b", "b3b"))
+I3D_BN_EPS = 1e-3
+
+
+def i3d_source_keys():
+    keys = [f"{u}.{t}" for u in I3D_CONV_UNITS for t in ("conv3d.weight", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")]
+    return keys + ["logits.conv3d.weight", "logits.conv3d.bias"]
+
+
+def pack_i3d(sd):
+    """State dict of the public PyTorch port of Kinetics I3D (``InceptionI3d``; ``<unit>.conv3d.weight``, ``<unit>.bn.*``,
+    ``logits.conv3d.{weight,bias}``), with or without the common prefix a torchscript wrapper puts in front of the names ->
+    {canonical name: fp32 CPU tensor} for ``ivg_i3d_create``: per unit ``<unit>.weight`` (Cout, kd kh kw Cin), K ordered
+    (kd, kh, kw, c), with the eval-mode batch norm (eps 1e-3) folded in fp64 -- w' = w gamma / sqrt(var + eps),
+    b' = beta - mean gamma / sqrt(var + eps) -- and ``<unit>.bias`` (Cout); ``logits.weight`` (400, C), ``logits.bias``.
+    KeyError lists every missing key."""
+    need = i3d_source_keys()
+    prefix = next((k[:-len(n)] for n in need for k in sd if k.endswith(n)), "")   # the first expected name that occurs sets it
+    missing = [k for k in need if prefix + k not in sd]
+    if missing:
+        raise KeyError(f"I3D: {len(missing)} tensors missing" + (f" (under the prefix {prefix!r})" if prefix else "") + ": " + ", ".join(missing))
+    get = lambda k: sd[prefix + k].detach().cpu().double()
+    out = {}
+    for u in I3D_CONV_UNITS:
+        w = get(f"{u}.conv3d.weight")
+        if w.dim() != 5:
+            raise ValueError(f"I3D: {u}.conv3d.weight has shape {tuple(w.shape)}, expected (Cout, Cin, kd, kh, kw)")
+        g, beta, mean, var = (get(f"{u}.bn.{t}") for t in ("weight", "bias", "running_mean", "running_var"))
+        if any(tuple(v.shape) != (w.shape[0],) for v in (g, beta, mean, var)):
+            raise ValueError(f"I3D: the batch-norm tensors of {u} do not have {w.shape[0]} elements")
+        scale = g / torch.sqrt(var + I3D_BN_EPS)
+        out[f"{u}.weight"] = (w * scale[:, None, None, None, None]).permute(0, 2, 3, 4, 1).reshape(w.shape[0], -1).float().contiguous()
+        out[f"{u}.bias"] = (beta - mean * scale).float().contiguous()
+    w, b = get("logits.conv3d.weight"), get("logits.conv3d.bias")
+    if w.dim() != 5 or tuple(w.shape[2:]) != (1, 1, 1) or tuple(b.shape) != (w.shape[0],):
+        raise ValueError(f"I3D: logits.conv3d has shapes {tuple(w.shape)} / {tuple(b.shape)}, expected (N, C, 1, 1, 1) / (N,)")
+    out["logits.weight"] = w.reshape(w.shape[0], w.shape[1]).float().contiguous()
+    out["logits.bias"] = b.float().contiguous()
+    return out
+
+
 def pack_tokenizer(sd, cfg, device, enc_code, dec_code, dec_x3=False):
     """DF state dict of CompressiveVQModel -> {name: device tensor} for ivg_create.  dec_x3: the 3x3 convolutions of the two
     decoders also get their weights pre-split for the split-bf16 kernels (``<name>.x3``, beside the fp32 matrix other shapes use)."""

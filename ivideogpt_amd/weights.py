@@ -211,6 +211,56 @@ def random_llama_state_dict(cfg, seed=0, action_dim=None, reward_prediction=Fals
     return random_state_dict(llama_param_shapes(cfg, action_dim, reward_prediction, action_recon), seed)
 
 
+# Kinetics-400 Inception-I3D widths (the public PyTorch port, ``InceptionI3d``): stem convolutions (name, Cout, kernel) and per Mixed
+# block [b0, b1a, b1b, b2a, b2b, b3b].  Used to DRAW weights; the engine reads the widths from the tensors it is given.
+I3D_STEM = (("Conv3d_1a_7x7", 64, 7), ("Conv3d_2b_1x1", 64, 1), ("Conv3d_2c_3x3", 192, 3))
+I3D_MIXED_WIDTHS = (("Mixed_3b", (64, 96, 128, 16, 32, 32)), ("Mixed_3c", (128, 128, 192, 32, 96, 64)),
+                    ("Mixed_4b", (192, 96, 208, 16, 48, 64)), ("Mixed_4c", (160, 112, 224, 24, 64, 64)),
+                    ("Mixed_4d", (128, 128, 256, 24, 64, 64)), ("Mixed_4e", (112, 144, 288, 32, 64, 64)),
+                    ("Mixed_4f", (256, 160, 320, 32, 128, 128)), ("Mixed_5b", (256, 160, 320, 32, 128, 128)),
+                    ("Mixed_5c", (384, 192, 384, 48, 128, 128)))
+I3D_CLASSES = 400
+
+
+def i3d_param_shapes(width_div=1):
+    """{``<unit>.conv3d.weight``: (Cout, Cin, k, k, k)} plus ``logits.conv3d.{weight,bias}``, every width divided by ``width_div``
+    (the 3 input channels and the 400 classes stay)."""
+    d = lambda c: max(1, c // width_div)
+    shapes, c = OrderedDict(), 3
+    for name, cout, k in I3D_STEM:
+        shapes[f"{name}.conv3d.weight"] = (d(cout), c, k, k, k)
+        c = d(cout)
+    for name, (o0, o1, o2, o3, o4, o5) in I3D_MIXED_WIDTHS:
+        for unit, cin, cout, k in (("b0", c, d(o0), 1), ("b1a", c, d(o1), 1), ("b1b", d(o1), d(o2), 3), ("b2a", c, d(o3), 1),
+                                   ("b2b", d(o3), d(o4), 3), ("b3b", c, d(o5), 1)):
+            shapes[f"{name}.{unit}.conv3d.weight"] = (cout, cin, k, k, k)
+        c = d(o0) + d(o2) + d(o4) + d(o5)
+    shapes["logits.conv3d.weight"] = (I3D_CLASSES, c, 1, 1, 1)
+    shapes["logits.conv3d.bias"] = (I3D_CLASSES,)
+    return shapes
+
+
+def random_i3d_state_dict(seed=0, width_div=1):
+    """Seeded state dict of the I3D detector: He-initialised convolutions (std = sqrt(2 / fan_in)) and non-trivial batch-norm
+    statistics -- gamma 1 +- 0.1, beta and running mean 0 +- 0.1, running variance uniform in [0.5, 1.5]."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    sd = OrderedDict()
+    for name, shape in i3d_param_shapes(width_div).items():
+        if name.endswith("conv3d.bias"):
+            sd[name] = 0.1 * torch.randn(shape, generator=g)
+            continue
+        sd[name] = torch.randn(shape, generator=g) * math.sqrt(2.0 / math.prod(shape[1:]))
+        if name.startswith("logits."):
+            continue
+        unit, n = name[:-len(".conv3d.weight")], shape[0]
+        sd[f"{unit}.bn.weight"] = 1.0 + 0.1 * torch.randn(n, generator=g)
+        sd[f"{unit}.bn.bias"] = 0.1 * torch.randn(n, generator=g)
+        sd[f"{unit}.bn.running_mean"] = 0.1 * torch.randn(n, generator=g)
+        sd[f"{unit}.bn.running_var"] = 0.5 + torch.rand(n, generator=g)
+    return sd
+
+
 def validate_state_dict(sd, shapes, what):
     missing = [k for k in shapes if k not in sd]
     unexpected = [k for k in sd if k not in shapes]

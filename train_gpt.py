@@ -10,8 +10,10 @@ Same names, arguments and op sequence as the reference, so the loop reads like t
   * ``accelerator`` is any object with ``device / num_processes / is_main_process / is_local_main_process / gather / unwrap_model /
     log`` -- ``ivideogpt_amd.parallel.LocalAccelerator`` (torch.distributed over RCCL, no ``accelerate`` dependency) or HF's
     ``Accelerator`` itself;
-  * FVD needs detector weights that do not ship (``args.use_fvd`` raises); the LPIPS column needs the VGG-16 / LPIPS weights:
-    with ``--lpips_vgg_path`` and ``--lpips_lin_path`` (``Evaluator(lpips=...)``) ``eval/lpips`` is computed on the device and
+  * FVD needs the I3D detector's weights, which do not ship: ``args.use_fvd`` with an ``Evaluator(i3d=...)`` computes the features
+    of the real and of all t * B generated clips on the device (ivideogpt_amd/i3d.py), gathers them and logs ``eval/fvd``
+    (:341-355, :456-470, :495-497); without a detector it raises.  The LPIPS column needs the VGG-16 / LPIPS weights: with
+    ``--lpips_vgg_path`` and ``--lpips_lin_path`` (``Evaluator(lpips=...)``) ``eval/lpips`` is computed on the device and
     gathered like the other three, without them it is NaN;
   * GIF dumps (``imageio``) are not written; the ``eval/mse`` fallback of that branch is kept (:447-449).
 The only collectives are the all-gathers of per-sample loss / metric rows (train_gpt.py:376, 476-479).
@@ -93,14 +95,27 @@ def _prompt_and_budget(args, tokens):
 def evaluate(args, accelerator, tokenizer, model, eval_dataloader, evaluator, completed_steps):
     """train_gpt.py:321-512.  ``eval_dataloader`` yields ``pixel_values [B, T, 3, H, W]`` in [0, 1] (or ``(pixel_values, actions)``
     when ``args.action_conditioned``).  Returns the eval logs on the main process, None elsewhere."""
-    if getattr(args, "use_fvd", False):
-        raise NotImplementedError("FVD needs the I3D detector weights, which do not ship with the reference (out of scope)")
+    use_fvd = getattr(args, "use_fvd", False)
+    scorer = accelerator.unwrap_model(evaluator) if use_fvd else None
+    if use_fvd and getattr(scorer, "i3d", None) is None:
+        raise NotImplementedError("FVD needs the I3D detector weights, which do not ship with the reference: Evaluator(i3d=...)")
     tok, net = accelerator.unwrap_model(tokenizer), accelerator.unwrap_model(model)
     dev, ctx = accelerator.device, args.context_length
     rows = {k: [] for k in ("loss", "mse", "psnr", "ssim", "lpips")}   # per-sample values, gathered over the ranks batch by batch
 
     def keep(name, value, n):
         rows[name].append(accelerator.gather(value.repeat(n)))
+
+    from ivideogpt_amd.metrics import FeatureStats
+    real_feats, gen_feats = FeatureStats(capture_mean_cov=True), FeatureStats(capture_mean_cov=True)
+
+    def keep_features(stats, clips):
+        # :341-355 / :456-470: detector features chunked by max_decode_batchsize, gathered, accumulated on the main process
+        chunk = args.max_decode_batchsize
+        feats = batch_forward(chunk, clips, scorer.i3d_features) if chunk is not None and clips.shape[0] > chunk else scorer.i3d_features(clips)
+        feats = accelerator.gather(feats)
+        if accelerator.is_main_process:
+            stats.append_torch(feats)
 
     for it, batch in enumerate(eval_dataloader):
         if it == args.max_eval_iters:
@@ -109,6 +124,8 @@ def evaluate(args, accelerator, tokenizer, model, eval_dataloader, evaluator, co
         frames = frames.to(dev, non_blocking=True)
         actions = actions.to(dev, non_blocking=True) if actions is not None else None
         n = frames.shape[0]
+        if use_fvd:
+            keep_features(real_feats, frames)
 
         # teacher-forced loss over the whole clip (:356-376)
         tokens, labels = tok.tokenize(frames, ctx)
@@ -121,7 +138,7 @@ def evaluate(args, accelerator, tokenizer, model, eval_dataloader, evaluator, co
         # rollout from the context frames, t samples per trajectory, decoded back to pixels (:390-430)
         show = it % args.log_gif_interval == 0 and accelerator.is_main_process
         recon = None
-        if show or args.use_frame_metrics:
+        if show or args.use_frame_metrics or use_fvd:
             prompt, budget = _prompt_and_budget(args, tokens)
             sampled = generate_multiple_times(args.eval_generate_times, accelerator, model, prompt, actions,
                                               gen_kwargs=dict(do_sample=True, temperature=1.0, top_k=100, max_new_tokens=budget),
@@ -134,6 +151,9 @@ def evaluate(args, accelerator, tokenizer, model, eval_dataloader, evaluator, co
             chunk = args.max_decode_batchsize
             recon = batch_forward(chunk, sampled, decode) if chunk is not None and sampled.shape[0] > chunk else decode(sampled)
             recon = recon.clamp(0.0, 1.0)
+
+        if use_fvd:
+            keep_features(gen_feats, recon)
 
         if args.use_frame_metrics:
             # the ground truth is clamped too: resized frames overshoot 1.0 by an ulp (:470-471)
@@ -154,6 +174,8 @@ def evaluate(args, accelerator, tokenizer, model, eval_dataloader, evaluator, co
     eval_logs = {"eval/eval_loss": eval_loss, "eval/perplexity": perplexity, "eval/mse": mean("mse")}
     if args.use_frame_metrics:
         eval_logs.update({f"eval/{k}": mean(k) for k in ("psnr", "ssim", "lpips")})
+    if use_fvd:
+        eval_logs["eval/fvd"] = scorer.compute_fvd(real_feats, gen_feats)
     accelerator.log(eval_logs, step=completed_steps)
     return eval_logs
 
@@ -184,6 +206,11 @@ def main(argv=None):
     ap.add_argument("--max_decode_batchsize", type=int, default=None)
     ap.add_argument("--lpips_vgg_path", default=None, help="torchvision vgg16 weights (features.N.* keys; .pth or .safetensors)")
     ap.add_argument("--lpips_lin_path", default=None, help="the lpips package's vgg.pth (lin{k}.model.1.weight); both paths: eval/lpips is real")
+    ap.add_argument("--use_fvd", action="store_true", help="log eval/fvd (needs --i3d_path or --i3d_random)")
+    ap.add_argument("--i3d_path", default=None, help="the I3D detector: the torchscript file of the reference, or a state-dict file")
+    ap.add_argument("--i3d_random", type=int, default=None, metavar="SEED", help="seeded random I3D weights (synthetic runs)")
+    ap.add_argument("--i3d_width_div", type=int, default=1, help="with --i3d_random: divide every width of the detector (quick runs)")
+    ap.add_argument("--i3d_resize", type=int, default=224, help="side the detector resizes frames to (a multiple of 32)")
     a = ap.parse_args(argv)
     rank, world, local = parallel.init_from_env()
     dev = torch.device("cuda", local)
@@ -201,10 +228,17 @@ def main(argv=None):
     g = torch.Generator().manual_seed(1234)
     batches = [torch.rand(a.batch, a.segment_length, 3, res, res, generator=g) for _ in range(a.iters * world)][rank::world]
     args = eval_args(context_length=a.context_length, segment_length=a.segment_length, eval_generate_times=a.eval_generate_times,
-                     max_generate_batchsize=a.max_generate_batchsize, max_decode_batchsize=a.max_decode_batchsize)
+                     max_generate_batchsize=a.max_generate_batchsize, max_decode_batchsize=a.max_decode_batchsize, use_fvd=a.use_fvd)
     if bool(a.lpips_vgg_path) != bool(a.lpips_lin_path):
         ap.error("--lpips_vgg_path and --lpips_lin_path go together")
-    evaluator = Evaluator(lpips=(a.lpips_vgg_path, a.lpips_lin_path) if a.lpips_vgg_path else None)
+    i3d = a.i3d_path
+    if a.i3d_random is not None:
+        from ivideogpt_amd.i3d import I3D
+        i3d = I3D.from_state_dict(W.random_i3d_state_dict(a.i3d_random, a.i3d_width_div), resize=a.i3d_resize)
+    elif i3d is not None:
+        from ivideogpt_amd.i3d import I3D
+        i3d = I3D.from_file(i3d, resize=a.i3d_resize)
+    evaluator = Evaluator(lpips=(a.lpips_vgg_path, a.lpips_lin_path) if a.lpips_vgg_path else None, i3d=i3d)
     logs = evaluate(args, parallel.LocalAccelerator(dev), tok, llm, batches, evaluator, 0)
     if logs is not None:
         print(json.dumps(logs))
