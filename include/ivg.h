@@ -488,8 +488,8 @@ int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
  * are exactly 0.0 in all three: the forced sdf tokens (j % 17 == 0 under the forced schedule); the j = 0 step of kept-cache and
  * shared-context calls writes nothing at all.  A row whose maximum is not finite (NaN, +inf, all -inf) gives NaN in all three (such a
  * row decides token 0); nothing is read outside the row.
- * Out of scope: the probability under the FILTERED distribution actually drawn from (HF `scores`): it would need a second
- * instantiation of the sampler, whose instances stay instruction-identical.  The scores come from a kernel of their own
+ * The probability under the FILTERED distribution actually drawn from (HF `scores`) is ivg_generate_filtered's output, defined with
+ * that entry below; the sampler's instances stay instruction-identical under both.  The scores come from a kernel of their own
  * (token_scores_kernel, one workgroup per trajectory) launched inside the decode steps right after the sampler and captured with the
  * step graphs: fp32 with max subtraction, entropy as log s - (sum e_i (z_i - m)) / s, every sum in one fixed order -- the same bits
  * run to run, eager or replayed, in one call or step by step on the kept cache.  Engine-owned buffer, copied out per cache chunk.
@@ -524,6 +524,55 @@ int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
  *                       synchronisation), only the last row is fed instead of a prefill of the grown prompt; *reused_out says which.
  * ivg_reward_linear     reward_linear (action_model.py:41; mbrl/video_predictor.py:313) on post-norm hidden rows (rows, hidden) llm
  *                       dtype -> float32 (rows). */
+/* Scores of every decided new token under the distribution it was DRAWN from: the row after temperature, top-k and top-p (HF generate's
+ * output_scores = True with compute_transition_scores(..., normalize_logits = True)): the proposal log-probability an importance weight
+ * or a likelihood ratio over candidates needs, without the (B, V) logits leaving the device.
+ *
+ * Definition.  z, tok and j as for ivg_generate_scored; temperature, top_k, top_p the engine's settings in force for the call.
+ *   l = z / temperature, an fp32 IEEE division, skipped when temperature == 1 (as the sampler's).
+ *   K: the top-k kept set: the entries >= the top_k-th largest, ties at that threshold kept, -inf entries never; top_k <= 0 or
+ *      top_k >= V keeps every finite entry.
+ *   S: the survivors of ivg_set_top_p step 3: with e_i = exp((double)(l_i - max)) (the subtraction in fp32) and Z = sum of e_i over K,
+ *      token i survives iff the mass of the kept tokens not above it exceeds (1 - (double)top_p) * Z; the maximum always survives;
+ *      top_p >= 1 gives S = K.
+ *   filtered_logprob = (l_tok - max) - log(sum_S e_i), -inf when tok is not in S
+ *   filtered_entropy = the entropy of e_i / sum_S e over S
+ *   kept_logmass     = log(sum_S e_i) - log(sum over all finite entries of e_i): at most 0, exactly 0 when nothing is filtered -- the
+ *                      share of the tempered softmax that survived
+ *   support          = |S| as a float
+ * Natural logarithms; every sum in fp64 in one fixed order (no atomics: the same bits run to run, eager or replayed, in one call or
+ * step by step on the kept cache), results rounded to fp32.  filtered_logprob + kept_logmass is the tempered raw log-probability.
+ * Greedy calls (uniforms == NULL): HF builds no warpers -- S is every finite entry and the temperature is ignored: the four describe
+ * the raw row.  Forced sdf columns are exactly 0 in all four; the j = 0 step writes nothing.  A row whose maximum is not finite, or that
+ * holds a NaN, gives NaN in all four, an id outside [0, V) a NaN logprob without a read (ivg_generate_scored's rules).  V up to the
+ * sampler's 256 * 72.
+ * The scores come from filtered_scores_kernel, one workgroup of 256 threads per trajectory, launched inside the decode steps directly
+ * after token_scores_kernel's slot -- after the sampler stored its id, before this step's lm_head overwrites the row -- and captured
+ * with the step graphs.  It restates the filter (bisection of both thresholds over the key space, as the sampler's general path); the
+ * sampler and token_scores_kernel are untouched.  Engine-owned buffer, copied out per cache chunk.
+ *
+ * ivg_generate_filtered = ivg_generate_scored plus filtered_scores_out, and stands for the same three entries; ivg_generate_fanout_filtered
+ * and ivg_generate_embeds_filtered likewise.  With filtered_scores_out NULL each launches exactly what the entry it stands for launches
+ * (ivg_debug_counter("filtered_scores") counts this kernel's launches, "token_scores" is unaffected).  Rows are in the engine's order
+ * (group-major for a shared context).  Refusals are those of the entry it stands for, before anything is launched or written.
+ *   filtered_scores_out  float32 (B, n_new, 4): filtered_logprob, filtered_entropy, kept_logmass, support; or NULL
+ * Not covered: filtered scores of GIVEN tokens (ivg_kv_extend_scored has no sampler settings of its own). */
+int ivg_generate_filtered(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new,
+                          const float* actions, int act_T, int ctx, const float* uniforms, int top_k,
+                          int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
+                          float* frame_rewards_out /* (B, n_new / 17) or NULL */,
+                          void* frame_hidden_out /* (B, n_new / 17, hidden) llm dtype or NULL */,
+                          float* token_scores_out /* (B, n_new, 3) or NULL */,
+                          float* filtered_scores_out /* (B, n_new, 4) or NULL */, ivg_stream stream);
+int ivg_generate_fanout_filtered(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
+                                 const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out,
+                                 float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out /* (n_groups * group_size, n_new, 3) or NULL */,
+                                 float* filtered_scores_out /* (n_groups * group_size, n_new, 4) or NULL */, ivg_stream stream);
+int ivg_generate_embeds_filtered(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k,
+                                 int64_t* new_ids_out, void* hidden_out, int allow_reuse, int* reused_out,
+                                 float* token_scores_out /* (B, n_new, 3) or NULL */,
+                                 float* filtered_scores_out /* (B, n_new, 4) or NULL */, ivg_stream stream);
+
 int ivg_embed_tokens(ivg_engine* e, const int64_t* ids, int64_t ids_stride, int B, int L, void* out, ivg_stream stream);
 int ivg_action_linear(ivg_engine* e, const float* actions, int rows, void* out, ivg_stream stream);
 /* Fan candidates out of the kept cache: ivg_generate_scored with group_size > 1 whose shared prefix is not prefilled -- it IS the kept
@@ -787,6 +836,11 @@ int ivg_op_sample_top_p(const float* logits, int B, int V, int top_k, float temp
  * chosen token of each row (not forced, j >= 1), out (B, 3) = logprob, entropy, max_logprob; V <= 256 * 72; an id outside [0, V) gives
  * a NaN logprob without a read */
 int ivg_op_token_scores(const float* logits, const int64_t* ids, int B, int V, float* out, ivg_stream stream);
+/* the arithmetic of filtered_scores_kernel (ivg_generate_filtered has the definition) on given rows under the given sampler settings:
+ * logits (B, V) float32, ids (B), greedy != 0 as a call without uniforms; out (B, 4) float32.  IVG_ERR_INVALID for V outside
+ * [1, 256 * 72], a temperature that is not positive and finite, a top_p outside [0, 1] */
+int ivg_op_filtered_scores(const float* logits, const int64_t* ids, int B, int V, int top_k, float temperature, float top_p, int greedy,
+                           float* out, ivg_stream stream);
 /* token_scores_rows_kernel (ivg_kv_extend_scored): the same arithmetic per row of a chunk of `rows` logits rows (rows, V); chunk row i is
  * row r = row0 + i of (B, Tc) rows, (b, c) = (r / Tc, r % Tc), its target id ids[b * ids_stride + c], its scores out[(b * out_ld + c) * 3 ..];
  * column c is three zeros when period > 0, c >= first_forced and (c - first_forced) % period == 0.  Nothing else is written. */

@@ -6,7 +6,7 @@ non-GPU device, raises.
 """
 from .vq_model import CompressiveVQModel, DetokenizeCache  # noqa: F401
 from .engine import KeptCache  # noqa: F401
-from .transformer import ExtendOutputs, HeadModelWithAction, LlamaForCausalLM, TokenScores, extend_frames  # noqa: F401
+from .transformer import ExtendOutputs, FilteredTokenScores, HeadModelWithAction, LlamaForCausalLM, TokenScores, extend_frames  # noqa: F401
 from . import switches, weights  # noqa: F401
 
-__all__ = ["CompressiveVQModel", "DetokenizeCache", "ExtendOutputs", "HeadModelWithAction", "KeptCache", "LlamaForCausalLM", "TokenScores", "switches", "weights"]
+__all__ = ["CompressiveVQModel", "DetokenizeCache", "ExtendOutputs", "FilteredTokenScores", "HeadModelWithAction", "KeptCache", "LlamaForCausalLM", "TokenScores", "switches", "weights"]

@@ -948,29 +948,53 @@ int ivg_generate_frames(ivg_engine* e, const int64_t* prompt, int64_t prompt_str
 int ivg_generate_scored(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
                         int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
                         float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
+  return ivg_generate_filtered(e, prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, group_size, kept_cache, force_sdf, ids_out,
+                               frame_rewards_out, frame_hidden_out, token_scores_out, nullptr, stream);
+}
+
+int ivg_generate_filtered(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int B, int L0, int n_new, const float* actions, int act_T,
+                          int ctx, const float* uniforms, int top_k, int group_size, int kept_cache, int force_sdf, int64_t* ids_out,
+                          float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, float* filtered_scores_out, ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   GenerateReq q = id_request(prompt, prompt_stride, B, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
   q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
+  q.filtered_scores_out = filtered_scores_out;
   return generate_checked(e, q, frames_rules(e, q, frame_rewards_out || frame_hidden_out, group_size, kept_cache, force_sdf, false), stream);
 }
 
 int ivg_generate_fanout(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
                         const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out,
                         float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, ivg_stream stream) {
+  return ivg_generate_fanout_filtered(e, prompt, prompt_stride, n_groups, group_size, L0, n_new, actions, act_T, ctx, uniforms, top_k, force_sdf, ids_out,
+                                      frame_rewards_out, frame_hidden_out, token_scores_out, nullptr, stream);
+}
+
+int ivg_generate_fanout_filtered(ivg_engine* e, const int64_t* prompt, int64_t prompt_stride, int n_groups, int group_size, int L0, int n_new,
+                                 const float* actions, int act_T, int ctx, const float* uniforms, int top_k, int force_sdf, int64_t* ids_out,
+                                 float* frame_rewards_out, void* frame_hidden_out, float* token_scores_out, float* filtered_scores_out,
+                                 ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   const bool sized = n_groups > 0 && group_size > 0 && (long)n_groups * group_size <= INT32_MAX;
   GenerateReq q = id_request(prompt, prompt_stride, sized ? n_groups * group_size : 0, L0, n_new, actions, act_T, ctx, uniforms, top_k, ids_out);
   q.frame_rewards_out = frame_rewards_out; q.frame_hidden_out = frame_hidden_out; q.token_scores_out = token_scores_out;
+  q.filtered_scores_out = filtered_scores_out;
   return generate_checked(e, q, frames_rules(e, q, frame_rewards_out || frame_hidden_out, sized ? group_size : 0, 0, force_sdf, true), stream);
 }
 
 int ivg_generate_embeds(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                         void* hidden_out, int allow_reuse, int* reused_out, ivg_stream stream) {
-  return ivg_generate_embeds_scored(e, embeds, B, L0, n_new, uniforms, top_k, new_ids_out, hidden_out, allow_reuse, reused_out, nullptr, stream);
+  return ivg_generate_embeds_filtered(e, embeds, B, L0, n_new, uniforms, top_k, new_ids_out, hidden_out, allow_reuse, reused_out, nullptr, nullptr, stream);
 }
 
 int ivg_generate_embeds_scored(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
                                void* hidden_out, int allow_reuse, int* reused_out, float* token_scores_out, ivg_stream stream) {
+  return ivg_generate_embeds_filtered(e, embeds, B, L0, n_new, uniforms, top_k, new_ids_out, hidden_out, allow_reuse, reused_out, token_scores_out, nullptr,
+                                      stream);
+}
+
+int ivg_generate_embeds_filtered(ivg_engine* e, const void* embeds, int B, int L0, int n_new, const float* uniforms, int top_k, int64_t* new_ids_out,
+                                 void* hidden_out, int allow_reuse, int* reused_out, float* token_scores_out, float* filtered_scores_out,
+                                 ivg_stream stream) {
   if (!e) return IVG_ERR_INVALID;
   if (reused_out) *reused_out = 0;
   IVG_TRY(check_generate(e, GEN_EMBEDS, embeds && new_ids_out ? nullptr : "generate_embeds: null argument", B, L0, n_new, nullptr, 0, 1));
@@ -979,6 +1003,7 @@ int ivg_generate_embeds_scored(ivg_engine* e, const void* embeds, int B, int L0,
   if (reused_out) *reused_out = reuse ? 1 : 0;
   GenerateReq q; q.B = B; q.L0 = L0; q.n_new = n_new; q.uniforms = uniforms; q.top_k = top_k;
   q.reuse_kv = reuse; q.embeds = embeds; q.new_ids_out = new_ids_out; q.hidden_out = hidden_out; q.token_scores_out = token_scores_out;
+  q.filtered_scores_out = filtered_scores_out;
   return run_generate(e, q, stream);
 }
 
@@ -1493,6 +1518,7 @@ int64_t ivg_debug_counter(const char* name) {
   if (name && !strcmp(name, "lpips_trunk_images")) return lpips_trunk_images();
   if (name && !strcmp(name, "frame_heads")) return frame_heads_hits();
   if (name && !strcmp(name, "token_scores")) return token_scores_launches();
+  if (name && !strcmp(name, "filtered_scores")) return filtered_scores_launches();
   if (name && !strcmp(name, "kv_select_direct")) return kv_select_rows(0);
   if (name && !strcmp(name, "kv_select_staged")) return kv_select_rows(1);
   if (name && !strcmp(name, "kv_snapshot_rows_saved")) return kv_snapshot_rows(0);
@@ -1720,6 +1746,17 @@ int ivg_op_token_scores(const float* logits, const int64_t* ids, int B, int V, f
   if (!logits || !ids || !out || B <= 0 || V < 1 || V > 256 * 72) return IVG_ERR_INVALID;
   // the rollout's score kernel on given rows and ids: new token j = 1 of a prompt of length 0, no forced schedule, one column
   return one_step(0, stream, [&](StepState* state, hipStream_t st) { return launch_token_scores(logits, V, state, ids, 1, 0, 0, out, 1, B, st); });
+}
+
+int ivg_op_filtered_scores(const float* logits, const int64_t* ids, int B, int V, int top_k, float temperature, float top_p, int greedy, float* out,
+                           ivg_stream stream) {
+  if (!logits || !ids || !out || B <= 0 || V < 1 || V > 256 * 72) return IVG_ERR_INVALID;
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return IVG_ERR_INVALID;   // as ivg_set_temperature
+  if (!(top_p >= 0.0f && top_p <= 1.0f)) return IVG_ERR_INVALID;                       // as ivg_set_top_p
+  // the rollout's kernel on given rows and ids: new token j = 1 of a prompt of length 0, no forced schedule, one column
+  return one_step(0, stream, [&](StepState* state, hipStream_t st) {
+    return launch_filtered_scores(logits, V, state, ids, 1, 0, 0, top_k, temperature, top_p, greedy != 0, out, 1, B, st);
+  });
 }
 
 int ivg_op_token_scores_rows(const float* logits, const int64_t* ids, int64_t ids_stride, int64_t row0, int rows, int Tc, int V, int first_forced,

@@ -59,6 +59,8 @@ struct GenerateReq {
   float* frame_rewards_out = nullptr; void* frame_hidden_out = nullptr;
   // ivg_generate_scored / ivg_generate_embeds_scored: [B][n_new][3] = logprob, entropy, max logprob of every decided new token
   float* token_scores_out = nullptr;
+  // ivg_generate_filtered and its siblings: [B][n_new][4] = filtered logprob, filtered entropy, kept log-mass, support of every decided new token
+  float* filtered_scores_out = nullptr;
 };
 
 struct Run {

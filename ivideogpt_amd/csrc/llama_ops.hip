@@ -2272,6 +2272,163 @@ static std::atomic<long long> g_token_scores_launches{0};
 void token_scores_note(int launches) { g_token_scores_launches += launches; }
 long long token_scores_launches() { return g_token_scores_launches.load(); }
 
+// Filtered scores of a rollout (include/ivg.h ivg_generate_filtered): the probability of the sampled token under the distribution it was
+// DRAWN from -- the row after temperature, top-k and top-p -- one launch per decode step in token_scores_kernel's slot (after the sampler
+// stored its id, before this step's lm_head overwrites the row).  A kernel of its own that restates the sampler's filter (ivg_set_top_p
+// steps 1-3) in the arithmetic of the sampler's general path; the sampler's instances are untouched.  Element i of the row belongs to
+// thread i % 256 (register slot i / 256), every sum is fp64 in one fixed order (slots ascending, wave butterfly, waves 0..3): no atomics,
+// the same bits on every run, eager or replayed, for a row at any place in the batch.
+__device__ __forceinline__ int block_sum_i32(int x, int* s_c, int lane, int wv) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if (lane == 0) s_c[wv] = x;
+  __syncthreads();
+  const int t = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+  __syncthreads();
+  return t;
+}
+
+// The four scores of one logits row against the id `tok`, by a workgroup of 256 threads; thread 0 writes o[0..3] = { filtered logprob,
+// filtered entropy, kept log-mass, support }.  greedy: no warpers (HF builds none): S is every finite entry of the raw row.
+template <int KPT>  // KPT logits per thread: V <= 256 * KPT
+__device__ __forceinline__ void filtered_scores_row(const float* __restrict__ row, int V, long tok, int top_k, float temperature, float top_p,
+                                                    bool greedy, float* __restrict__ o, double* s_w, int* s_c, float* s_f) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const bool scale = !greedy && temperature != 1.0f;
+  auto key2f = [](unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); };   // inverse of f2key
+  unsigned key[KPT];   // f2key of the tempered entry; 0 past the row (below every entry: never counted, never kept)
+  float mx = -INFINITY;
+  int nans = 0;
+#pragma unroll
+  for (int q = 0; q < KPT; ++q) {
+    const int i = q * 256 + tid;
+    key[q] = 0u;
+    if (i < V) {
+      float l = row[i];
+      if (scale) l = l / temperature;
+      key[q] = f2key(l);
+      mx = fmaxf(mx, l);
+      nans += l != l ? 1 : 0;
+    }
+  }
+  mx = wave_max(mx);
+  if (lane == 0) s_f[wv] = mx;
+  nans = block_sum_i32(nans, s_c, lane, wv);   // (synchronises: s_f is complete)
+  mx = fmaxf(fmaxf(s_f[0], s_f[1]), fmaxf(s_f[2], s_f[3]));
+  const float nan = __int_as_float(0x7fc00000);
+  if (nans > 0 || !(mx > -INFINITY && mx < INFINITY)) {   // (uniform) a NaN, +inf or all -inf: token_scores_kernel's rows of NaN
+    if (tid < 4) o[tid] = nan;
+    return;
+  }
+  // K: the key of the top_k-th largest entry = the largest T with #{key_i >= T} >= top_k, by bisection over the key space with integer
+  // block counts (-inf entries count, as in the sampler's select); everything >= it is kept (ties included), -inf never
+  unsigned thr = 0u;
+  if (!greedy && top_k > 0 && top_k < V) {
+    unsigned lo = 0u, hi = 0xffffffffu;
+    while (lo < hi) {   // uniform: every thread holds the same counts
+      const unsigned mid = lo + ((hi - lo) >> 1) + ((hi - lo) & 1u);
+      int cnt = 0;
+#pragma unroll
+      for (int q = 0; q < KPT; ++q) cnt += key[q] >= mid ? 1 : 0;
+      if (block_sum_i32(cnt, s_c, lane, wv) >= top_k) lo = mid; else hi = mid - 1u;
+    }
+    thr = lo;
+  }
+  // e_i = exp(l_i - max) in fp64, the subtraction in fp32; from here on v / e hold the KEPT entries only (-inf / 0 elsewhere)
+  float v[KPT];
+  double e[KPT];
+  double za = 0.0, zk = 0.0;
+#pragma unroll
+  for (int q = 0; q < KPT; ++q) {
+    const float l = key2f(key[q]);
+    const double ea = l > -INFINITY ? exp((double)(l - mx)) : 0.0;   // (NaN entries and the slots past the row: 0)
+    const bool kept = l > -INFINITY && key[q] >= thr;
+    za += ea;
+    e[q] = kept ? ea : 0.0;
+    v[q] = kept ? l : -INFINITY;
+    zk += e[q];
+  }
+  const double all = block_sum_f64(za, s_w, lane, wv);
+  // S: the kept tokens not below tau, the smallest value whose mass G of kept tokens not above it exceeds the cut (the sampler's general
+  // path: bisection over the key space, each round one fixed-order fp64 block sum).  Keys decode to floats for the comparison: float order
+  // is nkey order (-0.0 folded onto +0.0), and no round looks above the maximum, which always survives
+  float tauf = -INFINITY;
+  if (!greedy && top_p < 1.0f) {
+    const double Z = block_sum_f64(zk, s_w, lane, wv);
+    const double cut = (1.0 - (double)top_p) * Z;
+    unsigned lo = 0u, hi = f2key(mx);
+    if (!(Z > cut)) lo = hi;   // top_p = 0: the maximum alone
+    while (lo < hi) {
+      const unsigned mid = lo + ((hi - lo) >> 1);
+      const float midf = key2f(mid);
+      double m = 0.0;
+#pragma unroll
+      for (int q = 0; q < KPT; ++q) m += v[q] <= midf ? e[q] : 0.0;
+      if (block_sum_f64(m, s_w, lane, wv) > cut) hi = mid; else lo = mid + 1u;
+    }
+    tauf = key2f(lo);
+  }
+  double sp = 0.0, tp = 0.0;
+  int np = 0;
+#pragma unroll
+  for (int q = 0; q < KPT; ++q) {
+    const bool in = v[q] > -INFINITY && v[q] >= tauf;
+    if (in && e[q] > 0.0) { sp += e[q]; tp = fma(e[q], (double)(v[q] - mx), tp); }
+    np += in ? 1 : 0;
+  }
+  const double s = block_sum_f64(sp, s_w, lane, wv);
+  const double t = block_sum_f64(tp, s_w, lane, wv);
+  const int n = block_sum_i32(np, s_c, lane, wv);
+  if (tid == 0) {
+    const double ls = log(s);
+    float lp = nan;
+    if (tok >= 0 && tok < V) {
+      float l = row[tok];
+      if (scale) l = l / temperature;   // (the same IEEE division: the bits of the entry above)
+      lp = (l > -INFINITY && f2key(l) >= thr && l >= tauf) ? (float)((double)(l - mx) - ls) : -INFINITY;
+    }
+    o[0] = lp;
+    o[1] = (float)(ls - t / s);
+    o[2] = (float)(ls - log(all));   // (nothing filtered: s and all are the same terms in the same order, exactly 0)
+    o[3] = (float)n;
+  }
+}
+
+template <int KPT>
+__global__ __launch_bounds__(256) void filtered_scores_kernel(const float* __restrict__ logits, int V, const StepState* __restrict__ state,
+                                                              const int64_t* __restrict__ ids, long ids_stride, int L0, int forced_period, int top_k,
+                                                              float temperature, float top_p, int greedy, float* __restrict__ out, int cols) {
+  const int j = state->j;
+  if (j < 1 || j > cols) return;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  float* o = out + ((long)b * cols + (j - 1)) * 4;
+  if (forced_period > 0 && j % forced_period == 0) {
+    if (tid < 4) o[tid] = 0.f;
+    return;
+  }
+  __shared__ double s_w[4];
+  __shared__ int s_c[4];
+  __shared__ float s_f[4];
+  filtered_scores_row<KPT>(logits + (long)b * V, V, ids[(long)b * ids_stride + L0 + (j - 1)], top_k, temperature, top_p, greedy != 0, o, s_w, s_c, s_f);
+}
+
+int launch_filtered_scores(const float* logits, int V, const StepState* state, const int64_t* ids, long ids_stride, int L0, int forced_period, int top_k,
+                           float temperature, float top_p, bool greedy, float* out, int cols, int B, hipStream_t st) {
+  if (B <= 0 || cols <= 0) return 0;
+  if (!logits || !ids || !out || V < 1 || V > 256 * 72 || !(temperature > 0.0f) || !(top_p >= 0.0f && top_p <= 1.0f)) return (int)hipErrorInvalidValue;
+  if (V <= 256 * 36)
+    hipLaunchKernelGGL(filtered_scores_kernel<36>, dim3(B), dim3(256), 0, st, logits, V, state, ids, ids_stride, L0, forced_period, top_k, temperature, top_p,
+                       greedy ? 1 : 0, out, cols);
+  else
+    hipLaunchKernelGGL(filtered_scores_kernel<72>, dim3(B), dim3(256), 0, st, logits, V, state, ids, ids_stride, L0, forced_period, top_k, temperature, top_p,
+                       greedy ? 1 : 0, out, cols);
+  return (int)hipGetLastError();
+}
+
+static std::atomic<long long> g_filtered_scores_launches{0};
+void filtered_scores_note(int launches) { g_filtered_scores_launches += launches; }
+long long filtered_scores_launches() { return g_filtered_scores_launches.load(); }
+
 // ------------------------------------------------------------------------------------------------ eval heads
 // Shifted cross-entropy of teacher-forced logits (HF ForCausalLM loss, train_gpt.py:356-376): row r = (b, l) of a chunk of logits
 // [rows][V] fp32 predicts labels[b][l + 1]; nll[r] = logsumexp(logits[r]) - logits[r][target], 0 where the target is -100 (or l is

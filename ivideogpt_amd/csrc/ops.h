@@ -166,6 +166,14 @@ int launch_token_scores_rows(const float* logits, const int64_t* ids, long ids_s
                              float* out, long out_ld, hipStream_t st);
 void token_scores_note(int launches);   // the host's count of the launches above (test hook, ivg_debug_counter("token_scores"))
 long long token_scores_launches();
+// filtered scores of a rollout (ivg_generate_filtered), launched in launch_token_scores' slot: out[b][j - 1][0..3] = { logprob of the id the
+// sampler stored for new token j = state->j under the row after temperature, top-k and top-p (-inf outside the survivors), the entropy of
+// that distribution, log of the share of the tempered softmax that survived, the number of survivors }; greedy: the raw row, no filter;
+// four zeros on a forced column, nothing for j = 0 or j > cols.  out: [B][cols][4] floats
+int launch_filtered_scores(const float* logits, int V, const StepState* state, const int64_t* ids, long ids_stride, int L0, int forced_period, int top_k,
+                           float temperature, float top_p, bool greedy, float* out, int cols, int B, hipStream_t st);
+void filtered_scores_note(int launches);   // the host's count of the launches above (test hook, ivg_debug_counter("filtered_scores"))
+long long filtered_scores_launches();
 // eval heads: shifted cross-entropy per row of a logits chunk, per-trajectory (sum, count), action reconstruction squared error
 int launch_ce_rows(const float* logits, const int64_t* labels, long row0, int rows, int L, int V, float* nll, hipStream_t st);
 // ce_rows_kernel's arithmetic for rows whose targets are given ids: chunk row i = row r = row0 + i of [B][Tc] rows, target

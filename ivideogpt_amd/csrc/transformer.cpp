@@ -37,6 +37,8 @@ struct GenBuf {  // persistent decode-step buffers (fixed addresses so the captu
   // token scores (ivg_generate_scored): [Bc][ids_ld][3] floats, column j - 1 written by token_scores_kernel right after the sampler
   // decided new token j; copied to the caller per chunk
   float* tok_scores;
+  // filtered scores (ivg_generate_filtered): [Bc][ids_ld][4] floats, column j - 1 written by filtered_scores_kernel in the same slot
+  float* filt_scores;
 };
 
 // What the decode steps of one chunk of a call do beyond the fixed sequence (step_key names every field)
@@ -46,6 +48,7 @@ struct StepOpts {
   int sh_P = 0, sh_G = 1, sh_row0 = 0;
   bool fr_rew = false, fr_hid = false;   // the steps carry frame_heads_kernel, writing GenBuf::frame_rew / frame_hid
   bool scored = false;                   // the steps carry token_scores_kernel
+  bool filtered = false;                 // the steps carry filtered_scores_kernel
 };
 
 static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base = null: only the size
@@ -71,6 +74,7 @@ static size_t gen_layout(const ivg_engine* e, GenBuf& g, char* base) {   // base
   g.frame_rew = (float*)take((size_t)Bc * g.F_max * 4);
   g.frame_hid = take((size_t)Bc * g.F_max * H * esz(dt));
   g.tok_scores = (float*)take((size_t)Bc * g.ids_ld * 3 * 4);
+  g.filt_scores = (float*)take((size_t)Bc * g.ids_ld * 4 * 4);
   return off;
 }
 
@@ -248,6 +252,10 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, const StepO
   // token scores: the row the sampler just read is still whole (this step's lm_head overwrites it), the id it stored is in the id row
   if (!skip_sample && o.scored)
     CK(launch_token_scores(sa.logits, V, state, sa.ids_out, sa.ids_stride, sa.L0, sa.forced_period, g.tok_scores, g.ids_ld, B, st));
+  // filtered scores: the same row and id under the sampler's own temperature, top-k and top-p (greedy: none of them)
+  if (!skip_sample && o.filtered)
+    CK(launch_filtered_scores(sa.logits, V, state, sa.ids_out, sa.ids_stride, sa.L0, sa.forced_period, sa.top_k, sa.temperature, sa.top_p,
+                              sa.uniforms == nullptr, g.filt_scores, g.ids_ld, B, st));
   if (!forward) return 0;
   // 5 launches per layer: RMSNorms are fused into the consuming GEMMs (weights pre-multiplied by the norm weight,
   // row scale computed from the activations the GEMM streams anyway), residual adds into the producing GEMMs.
@@ -355,6 +363,7 @@ static std::string step_key(const ivg_engine* e, const StepOpts& o, const Sample
   if (o.sh_P > 0) k += ":sh" + std::to_string(o.sh_G) + ":" + std::to_string(o.sh_row0);   // decode attention: the groups' shared rows
   if (o.fr_rew || o.fr_hid) k += std::string(":f") + (o.fr_rew ? "r" : "") + (o.fr_hid ? "h" : "");   // frame_heads_kernel and its outputs
   if (o.scored) k += ":ts";                                 // token_scores_kernel after the sampler
+  if (o.filtered) k += ":fs";                               // filtered_scores_kernel after it
   return k + e->kvc.graph_key();                            // decode attention: the cache format and its scales
 }
 
@@ -499,7 +508,7 @@ static int run_steps(Run& r, const GenerateReq& q, const GenBuf& g, const Chunk&
     frame_heads_note(hits);
   };
   // steps of this call that ran the sampler, and token_scores_kernel after it (test hook)
-  auto note_scores = [&](int n) { if (o.scored) token_scores_note(n); };
+  auto note_scores = [&](int n) { if (o.scored) token_scores_note(n); if (o.filtered) filtered_scores_note(n); };
   int j = 1;
   // step 1 eagerly (also performs every kernel's one-time attribute setup), then replay a captured step graph
   if (feed_last) { IVG_TRY(step_body(e, st, g, o, Bc, sa, true, q.embeds != nullptr)); if (!q.embeds) note_scores(1); }   // j = 0: feed the prompt's last token
@@ -550,6 +559,9 @@ static int copy_chunk_out(Run& r, const GenerateReq& q, const GenBuf& g, const C
   if (k.o.scored)
     CK((int)hipMemcpy2DAsync(q.token_scores_out + (long)b0 * n_new * 3, (size_t)n_new * 12, g.tok_scores, (size_t)g.ids_ld * 12, (size_t)n_new * 12, Bc,
                              hipMemcpyDeviceToDevice, st));
+  if (k.o.filtered)
+    CK((int)hipMemcpy2DAsync(q.filtered_scores_out + (long)b0 * n_new * 4, (size_t)n_new * 16, g.filt_scores, (size_t)g.ids_ld * 16, (size_t)n_new * 16, Bc,
+                             hipMemcpyDeviceToDevice, st));
   if (k.o.fr_hid)
     CK((int)hipMemcpy2DAsync((char*)q.frame_hidden_out + (size_t)b0 * F_out * H * es, (size_t)F_out * H * es, g.frame_hid, (size_t)g.F_max * H * es,
                              (size_t)F_out * H * es, Bc, hipMemcpyDeviceToDevice, st));
@@ -584,6 +596,7 @@ int Run::generate(const GenerateReq& q) {
     Chunk k{b0, std::min(g.Bc, B - b0), StepOpts()};
     if (shared) { k.o.sh_P = L0 - 1; k.o.sh_G = group; k.o.sh_row0 = b0 / group * group - b0; }
     k.o.fr_rew = q.frame_rewards_out != nullptr; k.o.fr_hid = q.frame_hidden_out != nullptr; k.o.scored = q.token_scores_out != nullptr;
+    k.o.filtered = q.filtered_scores_out != nullptr;
     IVG_TRY(stage_chunk(*this, q, g, k));
     IVG_TRY(run_steps(*this, q, g, k));
     IVG_TRY(copy_chunk_out(*this, q, g, k));

@@ -26,6 +26,10 @@ _ROLLOUT_ENTRIES = (
 )
 
 
+# the entry that stands for one of the above and also takes filtered_scores_out (include/ivg.h ivg_generate_filtered)
+_FILTERED_ENTRY = {"ivg_generate_scored": "ivg_generate_filtered", "ivg_generate_fanout": "ivg_generate_fanout_filtered"}
+
+
 def rollout_entry(fanout=False, token_scores=False, frame_outputs=False, group_size=1, reuse_kv=False, force_sdf=False, reward=False,
                   actions=False):
     """The libivg entry that serves a rollout with these inputs (each but ``group_size`` a truth value: asked for / present).
@@ -395,34 +399,39 @@ class Engine:
         return self
 
     def rollout(self, prompt, n_new, out, *, actions=None, ctx=1, uniforms=None, top_k=100, group_size=1, reuse_kv=False, force_sdf=False,
-                fanout=False, reward=None, frame_rewards=None, frame_hidden=None, token_scores=None):
+                fanout=False, reward=None, frame_rewards=None, frame_hidden=None, token_scores=None, filtered_scores=None):
         """One rollout from an id prompt through the entry ``rollout_entry`` names: ``prompt`` (B, L0) -> ``out`` (B, L0 + n_new).
         ``group_size`` > 1 (ivg_generate_shared) and ``fanout`` (ivg_generate_fanout, the groups' prefix is the kept K / V cache):
         ``prompt`` holds one row per group and everything else B = groups * group_size rows, row g * group_size + k = sample k of
         prompt g.  ``reuse_kv``: ivg_generate_continue's kept cache.  ``force_sdf``: the forced-sdf schedule without actions.
         Outputs beside the tokens: ``reward`` (B) float32 at the last forward pass; ``frame_rewards`` (B, n_new // 17) float32 and
         ``frame_hidden`` (B, n_new // 17, hidden) in the llm dtype at the 16th token of every frame that was fed; ``token_scores``
-        (B, n_new, 3) float32, logprob, entropy and max_logprob of every decided new token (zeros on forced columns)."""
-        name = rollout_entry(fanout, token_scores is not None, frame_rewards is not None or frame_hidden is not None, group_size, reuse_kv,
-                             force_sdf, reward is not None, actions is not None)
+        (B, n_new, 3) float32, logprob, entropy and max_logprob of every decided new token (zeros on forced columns);
+        ``filtered_scores`` (B, n_new, 4) float32, the same tokens under the temperature / top-k / top-p distribution they were drawn
+        from: the entry is then the ``_filtered`` sibling of the scored or fan-out entry (include/ivg.h ivg_generate_filtered)."""
+        filtered = filtered_scores is not None
+        name = rollout_entry(fanout, filtered or token_scores is not None, frame_rewards is not None or frame_hidden is not None, group_size,
+                             reuse_kv, force_sdf, reward is not None, actions is not None)
         rows, L0 = prompt.shape
         act = (_ptr(actions), actions.shape[1] if actions is not None else 0, int(ctx))
         sample = (_ptr(uniforms), int(top_k))
         if name == "ivg_generate_fanout" or name == "ivg_generate_shared":
             args = (rows, int(group_size), L0, int(n_new), *act, *sample, int(bool(force_sdf)), _ptr(out))
             args += (_ptr(reward),) if name == "ivg_generate_shared" else (_ptr(frame_rewards), _ptr(frame_hidden), _ptr(token_scores))
+            args += (_ptr(filtered_scores),) if filtered else ()
         elif name == "ivg_generate_scored" or name == "ivg_generate_frames":
             args = (out.shape[0], L0, int(n_new), *act, *sample, int(group_size), int(bool(reuse_kv)), int(bool(force_sdf)), _ptr(out),
                     _ptr(frame_rewards), _ptr(frame_hidden))
             args += (_ptr(token_scores),) if name == "ivg_generate_scored" else ()
+            args += (_ptr(filtered_scores),) if filtered else ()
         elif name == "ivg_generate_forced_sdf":
             args = (rows, L0, int(n_new), int(ctx), *sample, _ptr(out))
         else:   # ivg_generate, ivg_generate_continue
             args = (rows, L0, int(n_new), *act, *sample, _ptr(out), _ptr(reward))
         with self.stream() as s:
-            self.check(getattr(self.lib, name)(self.h, _ptr(prompt), prompt.stride(0), *args, s),
+            self.check(getattr(self.lib, _FILTERED_ENTRY[name] if filtered else name)(self.h, _ptr(prompt), prompt.stride(0), *args, s),
                        "generate" if name == "ivg_generate_continue" else name[4:])
-            self._record(prompt, out, actions, uniforms, reward, frame_rewards, frame_hidden, token_scores)
+            self._record(prompt, out, actions, uniforms, reward, frame_rewards, frame_hidden, token_scores, filtered_scores)
 
     def embed_tokens(self, ids, out):
         B, L = ids.shape
@@ -440,20 +449,25 @@ class Engine:
             self.check(self.lib.ivg_reward_linear(self.h, _ptr(hidden), hidden.numel() // hidden.shape[-1], _ptr(out), s), "reward_linear")
             hidden.record_stream(self._run); out.record_stream(self._run)
 
-    def generate_embeds(self, embeds, n_new, out, hidden=None, uniforms=None, top_k=100, allow_reuse=True, token_scores=None):
+    def generate_embeds(self, embeds, n_new, out, hidden=None, uniforms=None, top_k=100, allow_reuse=True, token_scores=None, filtered_scores=None):
         """-> True when the kept KV cache was reused (only the last row of ``embeds`` was fed).  ``token_scores`` (B, n_new, 3) float32:
-        ivg_generate_embeds_scored instead, which also leaves logprob, entropy and max_logprob of every new token."""
+        ivg_generate_embeds_scored instead, which also leaves logprob, entropy and max_logprob of every new token; ``filtered_scores``
+        (B, n_new, 4) float32: ivg_generate_embeds_filtered, which takes both."""
         B, L0 = embeds.shape[:2]
         reused = C.c_int(0)
         with self.stream() as s:
-            if token_scores is None:
+            if filtered_scores is not None:
+                self.check(self.lib.ivg_generate_embeds_filtered(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
+                                                                 _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), _ptr(token_scores),
+                                                                 _ptr(filtered_scores), s), "generate_embeds_filtered")
+            elif token_scores is None:
                 self.check(self.lib.ivg_generate_embeds(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
                                                         _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), s), "generate_embeds")
             else:
                 self.check(self.lib.ivg_generate_embeds_scored(self.h, _ptr(embeds), B, L0, int(n_new), _ptr(uniforms), int(top_k), _ptr(out),
                                                                _ptr(hidden), int(bool(allow_reuse)), C.byref(reused), _ptr(token_scores), s),
                            "generate_embeds_scored")
-            self._record(embeds, out, hidden, uniforms, token_scores)
+            self._record(embeds, out, hidden, uniforms, token_scores, filtered_scores)
         return bool(reused.value)
 
     def logits(self, ids, out, actions=None, ctx=1):

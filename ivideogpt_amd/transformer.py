@@ -133,6 +133,25 @@ class TokenScores(NamedTuple):
         return lp, en / 16
 
 
+class FilteredTokenScores(NamedTuple):
+    """``generate(..., output_filtered_scores=True)``: every new token under the distribution it was DRAWN from -- the logits row after
+    temperature, top-k and top-p (include/ivg.h ivg_generate_filtered; HF's ``output_scores`` /
+    ``compute_transition_scores(..., normalize_logits=True)``), each float32 (B, max_new_tokens), natural logarithms: ``logprob`` of the
+    token under the filtered distribution (the proposal log-probability of an importance weight), ``entropy`` of that distribution,
+    ``kept_logmass`` = log of the share of the tempered softmax the filter kept (<= 0; ``logprob + kept_logmass`` is the tempered raw
+    log-probability), ``support`` = the number of tokens that could have been drawn.  Greedy calls: no filter, the raw row.  Forced
+    ``sdf`` columns are exactly 0 in all four."""
+    logprob: torch.Tensor
+    entropy: torch.Tensor
+    kept_logmass: torch.Tensor
+    support: torch.Tensor
+
+    def per_frame(self):
+        """-> ``(frame_logprob, frame_entropy)``, each (B, F): the SUM of ``logprob`` and the MEAN of ``entropy`` over each frame's 16
+        sampled tokens, in the column order of ``TokenScores.per_frame``."""
+        return TokenScores.per_frame(self)
+
+
 def _token_scores_buffer(B, n_new, device):
     return torch.empty(B, n_new, 3, dtype=torch.float32, device=device)
 
@@ -141,6 +160,12 @@ def _token_scores_of(ts, t=1, B0=1, n=None):
     """(B, n_new, 3) in the engine's row order -> TokenScores of (B, n) in the caller's"""
     ts = _from_group_major(ts, t, B0)
     return TokenScores(*(ts[:, :n, k].contiguous() for k in range(3)))
+
+
+def _filtered_scores_of(fs, t=1, B0=1, n=None):
+    """(B, n_new, 4) in the engine's row order -> FilteredTokenScores of (B, n) in the caller's"""
+    fs = _from_group_major(fs, t, B0)
+    return FilteredTokenScores(*(fs[:, :n, k].contiguous() for k in range(4)))
 
 
 class ExtendOutputs(NamedTuple):
@@ -581,7 +606,7 @@ class LlamaForCausalLM:
         """``fan_out`` of both classes: ``ivg_generate_fanout`` under ``generate``'s keywords.  Rows b * samples + k throughout (the
         engine's group-major order is the public one here)."""
         known = {"do_sample", "temperature", "top_k", "max_new_tokens", "pad_token_id", "generator", "uniforms", "top_p", "output_token_scores",
-                 "return_reward", "output_frame_hidden_states"}
+                 "return_reward", "output_frame_hidden_states", "output_filtered_scores"}
         if set(gk) - known:
             raise TypeError(f"fan_out: unexpected keyword(s) {sorted(set(gk) - known)}")
         do_sample, temperature, top_k = gk.get("do_sample", True), gk.get("temperature", 1.0), gk.get("top_k", 100)
@@ -607,10 +632,10 @@ class LlamaForCausalLM:
         try:
             r = self._rollout(ids, n, (do_sample, temperature, top_k, top_p, gk.get("generator"), gk.get("uniforms")), act=act, ctx=ctx, fan=samples,
                               force_sdf=act is None and (frames or force_sdf), sdf_tail=frames, frame_rewards=rr == "frames", frame_hidden=want_h,
-                              scores=want_s)
+                              scores=want_s, filtered=gk.get("output_filtered_scores", False))
         except (AssertionError, _lib.IvgError) as err:
             raise ValueError(f"fan_out: {err}") from None
-        return r.result(r.tokens.contiguous(), r.frame_rewards, r.frame_hidden, r.token_scores)
+        return r.result(r.tokens.contiguous(), r.frame_rewards, r.frame_hidden, r.token_scores, r.filtered_scores)
 
     @torch.no_grad()
     def fan_out(self, input_ids, samples, **generate_kwargs):
@@ -618,7 +643,8 @@ class LlamaForCausalLM:
         (B, L0) is what the kept cache was built from plus the token to feed next, and row ``b * samples + k`` of every result is
         candidate k of row b.  No prompt pass: the candidates read the kept rows in place, and the kept cache is afterwards exactly
         what it was -- fan out again, continue, or ``extend_kept_cache``.  ``generate``'s keywords (``do_sample``, ``temperature``,
-        ``top_k``, ``top_p``, ``max_new_tokens``, ``uniforms`` (B * samples, n), ``generator``, ``output_token_scores``); results as
+        ``top_k``, ``top_p``, ``max_new_tokens``, ``uniforms`` (B * samples, n), ``generator``, ``output_token_scores``,
+        ``output_filtered_scores``); results as
         ``generate``'s.  ValueError where the engine refuses (no such kept cache, more candidates than the engine holds)."""
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         return self._fan_out(ids, samples, None, 1, generate_kwargs)
@@ -635,7 +661,7 @@ class LlamaForCausalLM:
         return eng.set_temperature(temperature).set_top_p(top_p)
 
     def _rollout(self, ids, n, sampling, act=None, ctx=1, groups=None, fan=0, reuse_kv=False, force_sdf=False, sdf_tail=False, reward=False,
-                 frame_rewards=False, frame_hidden=False, scores=False):
+                 frame_rewards=False, frame_hidden=False, scores=False, filtered=False):
         """One ``Engine.rollout`` of ``n`` new tokens after ``ids``, from the uniforms to the results, for every id-prompt entry of both
         classes.  ``sampling``: (do_sample, temperature, top_k, top_p, generator, uniforms).  ``groups`` = (t, B0): ``ids`` is
         ``prompts.repeat(t, 1)``, run as B0 groups of t -- inputs and results stay in the caller's row order, translated to and from
@@ -644,7 +670,7 @@ class LlamaForCausalLM:
         asked for one token more, the forced sdf that feeds the last frame's 16th token: the uniforms get a column (never read) and a
         table that ends with the last frame's action a zero row (the token is dropped and never fed, the row reaches no output).
         -> namespace(tokens (B, L0 + n), reward (B), frame_rewards (B, F), frame_hidden (B, F, hidden), token_scores: TokenScores of
-        (B, n)), None what was not asked for; ``.result(*values)``: the values that are not None, a single one bare."""
+        (B, n), filtered_scores: FilteredTokenScores of (B, n)), None what was not asked for; ``.result(*values)``: the values that are not None, a single one bare."""
         do_sample, temperature, top_k, top_p, generator, u = sampling
         L0 = ids.shape[1]
         B = ids.shape[0] * fan if fan else ids.shape[0]
@@ -667,14 +693,16 @@ class LlamaForCausalLM:
         fr = torch.empty(B, F, dtype=torch.float32, device=dev) if frame_rewards else None
         fh = torch.empty(B, F, self._cfg["hidden_size"], dtype=self.torch_dtype, device=dev) if frame_hidden else None
         ts = _token_scores_buffer(B, n_new, dev) if scores else None
+        fs = torch.empty(B, n_new, 4, dtype=torch.float32, device=dev) if filtered else None
         self._sampling_engine(B, act.shape[1] if act is not None else 32, temperature, top_p, existing=bool(fan)).rollout(
             ids[:B0].contiguous() if t > 1 else ids, n_new, out, actions=_to_group_major(act, t, B0), ctx=ctx, uniforms=_to_group_major(u, t, B0),
             top_k=top_k or self._cfg["vocab_size"], group_size=fan or t, reuse_kv=reuse_kv, force_sdf=force_sdf, fanout=bool(fan), reward=rw,
-            frame_rewards=fr, frame_hidden=fh, token_scores=ts)
+            frame_rewards=fr, frame_hidden=fh, token_scores=ts, filtered_scores=fs)
         tokens = _from_group_major(out, t, B0)
         return SimpleNamespace(tokens=tokens[:, :-1] if sdf_tail else tokens, reward=_from_group_major(rw, t, B0),
                                frame_rewards=_from_group_major(fr, t, B0), frame_hidden=_from_group_major(fh, t, B0),
-                               token_scores=_token_scores_of(ts, t, B0, n) if scores else None, result=_result)
+                               token_scores=_token_scores_of(ts, t, B0, n) if scores else None,
+                               filtered_scores=_filtered_scores_of(fs, t, B0, n) if filtered else None, result=_result)
 
     def get_input_embeddings(self):
         return _Embedding(self)
@@ -682,11 +710,14 @@ class LlamaForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=None,
                  generator=None, uniforms=None, inputs_embeds=None, return_dict_in_generate=False, output_hidden_states=False,
-                 use_cache=True, shared_context=None, top_p=None, output_token_scores=False, **unused):
+                 use_cache=True, shared_context=None, top_p=None, output_token_scores=False, output_filtered_scores=False, **unused):
         """``input_ids`` prompt -> int64 (B, L0 + max_new_tokens), prompt included (HF convention).
         ``output_token_scores=True`` (HF: ``output_logits`` + ``compute_transition_scores(normalize_logits=True)``, computed on the device
         inside the decode steps): the result becomes ``(tokens, TokenScores)``; on the ``inputs_embeds`` path with
         ``return_dict_in_generate`` the field ``.token_scores``.  The tokens are those of the call without it.
+        ``output_filtered_scores=True`` (HF: ``output_scores`` + ``compute_transition_scores(normalize_logits=True)``) appends the
+        ``FilteredTokenScores`` -- the tokens under the temperature / top-k / top-p distribution they were drawn from -- after it
+        (field ``.filtered_scores``).
         ``top_p``: HF's nucleus filter after the top-k filter (include/ivg.h ivg_set_top_p); ``None`` / 1.0: none, ignored without
         ``do_sample``, ValueError outside [0, 1] or NaN (``_top_p_of``).
         ``shared_context`` (not in HF; round 6): ``t`` or ``"auto"`` when ``input_ids`` is ``prompts.repeat(t, 1)`` -- what
@@ -708,22 +739,28 @@ class LlamaForCausalLM:
             hidden = torch.empty(B, 1, emb.shape[-1], dtype=self.torch_dtype, device=self.device) if output_hidden_states else None
             u = uniforms if uniforms is not None else self._uniforms(B, max_new_tokens, do_sample, generator)
             ts = _token_scores_buffer(B, max_new_tokens, self.device) if output_token_scores else None
+            fs = torch.empty(B, max_new_tokens, 4, dtype=torch.float32, device=self.device) if output_filtered_scores else None
             self.last_generate_reused_cache = self._sampling_engine(B, 32, temperature, top_p).generate_embeds(
-                emb, max_new_tokens, out, hidden=hidden, uniforms=u, top_k=top_k or self._cfg["vocab_size"], allow_reuse=use_cache, token_scores=ts)
+                emb, max_new_tokens, out, hidden=hidden, uniforms=u, top_k=top_k or self._cfg["vocab_size"], allow_reuse=use_cache, token_scores=ts,
+                filtered_scores=fs)
             scores = _token_scores_of(ts) if output_token_scores else None
+            filtered = _filtered_scores_of(fs) if output_filtered_scores else None
             if not return_dict_in_generate:
-                return (out, scores) if output_token_scores else out
+                return _result(out, scores, filtered)
             res = SimpleNamespace(sequences=out, hidden_states=((hidden,),) if output_hidden_states else None)
             if output_token_scores:
                 res.token_scores = scores
+            if output_filtered_scores:
+                res.filtered_scores = filtered
             return res
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
         t, B0 = shared_prompt_groups(ids, shared_context) if shared_context else (1, B)
         if not (t > 1 and L0 >= 2):   # (nothing to share)
             t, B0 = 1, B
-        r = self._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), groups=(t, B0), scores=output_token_scores)
-        return r.result(r.tokens, r.token_scores)
+        r = self._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), groups=(t, B0), scores=output_token_scores,
+                          filtered=output_filtered_scores)
+        return r.result(r.tokens, r.token_scores, r.filtered_scores)
 
     @torch.no_grad()
     def logits(self, input_ids):
@@ -919,7 +956,7 @@ class HeadModelWithAction:
     @torch.no_grad()
     def generate(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, pad_token_id=50256,
                  action=None, generator=None, uniforms=None, return_reward=False, reuse_cache=False, shared_context=None, top_p=None,
-                 output_frame_hidden_states=False, output_token_scores=False):
+                 output_frame_hidden_states=False, output_token_scores=False, output_filtered_scores=False):
         """action_model.py:56-121: action (B, T, D); new token j is the forced sdf when j % 17 == 0; the i-th sdf slot's
         embedding gets ``action_linear(action[:, i + context - 1])``.  -> int64 (B, L0 + max_new_tokens).
         ``shared_context``: as ``LlamaForCausalLM.generate`` -- ``inputs_token`` is ``prompts.repeat(t, 1)`` (train_gpt.py:170, VP2's
@@ -941,8 +978,11 @@ class HeadModelWithAction:
         ``(logprob, entropy, max_logprob)``, each float32 (B, max_new_tokens), of the model's distribution at every new token, forced
         ``sdf`` columns 0 (include/ivg.h ivg_generate_scored); the other results are those of the call without it.  With
         ``return_reward=True`` the single reward is read off the per-frame rewards of the same call, which needs
-        ``max_new_tokens`` a positive multiple of 17 (the step-wise callers' 17; ValueError otherwise)."""
+        ``max_new_tokens`` a positive multiple of 17 (the step-wise callers' 17; ValueError otherwise).
+        ``output_filtered_scores=True`` appends the ``FilteredTokenScores`` after it, under the same conditions (include/ivg.h
+        ivg_generate_filtered)."""
         _check_temperature(temperature)
+        scored = output_token_scores or output_filtered_scores   # (either output goes through the scored entry)
         top_p = _top_p_of(top_p, do_sample)
         per_frame = isinstance(return_reward, str)
         if per_frame and return_reward != "frames":
@@ -953,9 +993,10 @@ class HeadModelWithAction:
                 raise ValueError("return_reward='frames' needs a model with reward_prediction=True")
             if return_reward is True:   # (its value is read one token earlier than a frame's: no single call yields both)
                 raise ValueError("output_frame_hidden_states goes with return_reward='frames' or False, not True")
-        if output_token_scores and return_reward is True and not (isinstance(max_new_tokens, int) and max_new_tokens >= 17 and max_new_tokens % 17 == 0):
+        if scored and return_reward is True and not (isinstance(max_new_tokens, int) and max_new_tokens >= 17 and max_new_tokens % 17 == 0):
             # (the scored entry has the per-frame rewards only; the last of them is reward_out iff the call ends with a frame's sdf)
-            raise ValueError(f"output_token_scores with return_reward=True needs max_new_tokens a positive multiple of 17, not {max_new_tokens!r}")
+            raise ValueError(f"output_{'token' if output_token_scores else 'filtered'}_scores with return_reward=True needs max_new_tokens a positive "
+                             f"multiple of 17, not {max_new_tokens!r}")
         llm = self.llm
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         B, L0 = ids.shape
@@ -966,21 +1007,24 @@ class HeadModelWithAction:
         if not (t > 1 and L0 == 257 * self.context):   # (a shared prefix ends before the first action slot)
             t, B0 = 1, B
         r = llm._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), act=act, ctx=self.context, groups=(t, B0),
-                         reuse_kv=reuse_cache, sdf_tail=frames, reward=single and not output_token_scores,
-                         frame_rewards=per_frame or (single and output_token_scores), frame_hidden=output_frame_hidden_states, scores=output_token_scores)
-        rewards = r.frame_rewards[:, -1].contiguous() if single and output_token_scores else r.frame_rewards
-        return r.result(r.tokens, r.reward, rewards, r.frame_hidden, r.token_scores)
+                         reuse_kv=reuse_cache, sdf_tail=frames, reward=single and not scored,
+                         frame_rewards=per_frame or (single and scored), frame_hidden=output_frame_hidden_states, scores=output_token_scores,
+                         filtered=output_filtered_scores)
+        rewards = r.frame_rewards[:, -1].contiguous() if single and scored else r.frame_rewards
+        return r.result(r.tokens, r.reward, rewards, r.frame_hidden, r.token_scores, r.filtered_scores)
 
     @torch.no_grad()
     def generate_without_action(self, inputs_token, do_sample=True, temperature=1.0, top_k=100, max_new_tokens=None, generator=None,
-                                uniforms=None, top_p=None, output_frame_hidden_states=False, output_token_scores=False):
+                                uniforms=None, top_p=None, output_frame_hidden_states=False, output_token_scores=False,
+                                output_filtered_scores=False):
         """action_model.py:123-152 (no caller in the reference): per future frame 16 sampled tokens, then the forced ``sdf`` -- the
         schedule of ``generate`` without any action embedding; the last forced ``sdf`` is dropped.  -> int64 (B, L0 + max_new_tokens).
         One prefill + cached steps instead of the reference's per-frame re-prefill (token-identical: same argument as ``generate``).
         ``top_p`` (an extension, as in ``generate``): as ``LlamaForCausalLM.generate``.
         ``output_frame_hidden_states=True``: -> ``(tokens, hidden (B, F, hidden))``, the post-norm hidden state at every predicted
         frame's 16th token (as ``generate``); the tokens are those of the plain call.
-        ``output_token_scores=True`` appends the ``TokenScores`` as the last element (as ``generate``)."""
+        ``output_token_scores=True`` appends the ``TokenScores`` as the last element (as ``generate``), ``output_filtered_scores=True`` the
+        ``FilteredTokenScores`` after it."""
         _check_temperature(temperature)
         top_p = _top_p_of(top_p, do_sample)
         if output_frame_hidden_states:
@@ -989,8 +1033,9 @@ class HeadModelWithAction:
         ids = inputs_token.to(device=llm.device, dtype=torch.int64).contiguous()
         assert (max_new_tokens + 1) % (self.segment_length - self.context) == 0, "max_new_tokens must be (tokens_per_dyna + 1) * frames - 1"
         r = llm._rollout(ids, max_new_tokens, (do_sample, temperature, top_k, top_p, generator, uniforms), ctx=self.context, force_sdf=True,
-                         sdf_tail=output_frame_hidden_states, frame_hidden=output_frame_hidden_states, scores=output_token_scores)
-        return r.result(r.tokens, r.frame_hidden, r.token_scores)
+                         sdf_tail=output_frame_hidden_states, frame_hidden=output_frame_hidden_states, scores=output_token_scores,
+                         filtered=output_filtered_scores)
+        return r.result(r.tokens, r.frame_hidden, r.token_scores, r.filtered_scores)
 
     @torch.no_grad()
     def __call__(self, input_ids=None, attention_mask=None, labels=None, position_ids=None, action=None):

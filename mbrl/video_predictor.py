@@ -230,13 +230,13 @@ class TrackedEpisode:
         return Observation(surprise, reward.float(), hidden, out.token_scores.per_frame()[1][:, 0])
 
     @torch.no_grad()
-    def plan(self, plans, samples=1, return_uncertainty=False, uniforms=None, generator=None):
+    def plan(self, plans, samples=1, return_uncertainty=False, uniforms=None, generator=None, return_proposal_logprob=False):
         """Imagines ``samples`` action plans per tracked history: ``plans`` [B * samples, horizon, A], rows ``b * samples + k`` the
         candidates of history b (``rollout_actions``' order, also of ``uniforms`` [B * samples, 17 * horizon - 1] and every result).
         One ``fan_out`` of the kept cache and one ``detokenize`` of the imagined frames; the kept cache is afterwards what it was.
         -> (obss [B * samples, horizon + 1, 9, H, W], actions [B * samples, horizon + 1, A], rewards [B * samples, horizon + 1, 1])
-        and, with ``return_uncertainty``, uncertainty [B * samples, horizon + 1, 1]: ``rollout_actions``' results, step 0 being the
-        observed stack."""
+        and, with ``return_uncertainty``, uncertainty [B * samples, horizon + 1, 1]; with ``return_proposal_logprob``, after it, the
+        proposal log-probability [B * samples, horizon + 1, 1]: ``rollout_actions``' results, step 0 being the observed stack."""
         p, ctx, model, k = self.p, self.p.context_length, self.p.model, int(samples)
         p._activate(self)
         B, horizon = self.batch, plans.shape[1]
@@ -251,7 +251,8 @@ class TrackedEpisode:
         L0 = self.tokens.shape[1]
         tokens, hidden, *scores = model.fan_out(self.tokens, k, action=table, do_sample=True, temperature=1.0, top_k=100,
                                                 max_new_tokens=17 * horizon - 1, uniforms=uniforms, generator=generator,
-                                                output_frame_hidden_states=True, output_token_scores=return_uncertainty)
+                                                output_frame_hidden_states=True, output_token_scores=return_uncertainty,
+                                                output_filtered_scores=return_proposal_logprob)
         rewards = model.reward_linear(hidden).squeeze(-1)                      # (B * samples, horizon)
         # every frame is decoded against the context alone: the imagined frames directly behind the context tokens
         clip = p.tokenizer.detokenize(torch.cat([tokens[:, :257 * ctx], tokens[:, L0:]], 1), ctx)
@@ -261,10 +262,12 @@ class TrackedEpisode:
         rewards = torch.cat([torch.zeros_like(rewards[:, :1]), rewards], 1).unsqueeze(-1)
         if p.symlog:
             rewards = symexp(rewards)
+        extra = []
         if return_uncertainty:
-            unc = scores[0].per_frame()[1]                                     # (B * samples, horizon)
-            return obss, actions, rewards.float(), torch.cat([torch.zeros_like(unc[:, :1]), unc], 1).unsqueeze(-1).float()
-        return obss, actions, rewards.float()
+            extra.append(scores[0].per_frame()[1])                             # (B * samples, horizon)
+        if return_proposal_logprob:
+            extra.append(scores[-1].per_frame()[0])
+        return (obss, actions, rewards.float(), *(torch.cat([torch.zeros_like(x[:, :1]), x], 1).unsqueeze(-1).float() for x in extra))
 
     def _grow(self, rows):
         """The kept cache in an engine that holds ``rows`` trajectories.  ``grow="prefill"``: one prompt pass over ``tokens`` brings it
@@ -414,7 +417,7 @@ class VideoPredictor:
         return TrackedEpisode(self, obs, max_steps=max_steps, on_full=on_full, grow=grow)
 
     @torch.no_grad()
-    def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None, return_uncertainty=False):
+    def rollout_actions(self, obs, actions, samples=1, generator=None, uniforms=None, return_uncertainty=False, return_proposal_logprob=False):
         """Open-loop rollout of given action sequences (a CEM / MPPI / MPC planner's candidates, MBPO with a fixed plan) in three calls
         instead of ``horizon`` steps: one ``encode_context``, one ``generate`` that also returns the hidden state at every frame's
         16th token, where the reward head is trained (include/ivg.h ivg_generate_frames), and one ``detokenize``.  The rewards are
@@ -426,7 +429,11 @@ class VideoPredictor:
         -> (obss [B * samples, horizon + 1, 9, H, W], actions [B * samples, horizon + 1, A], rewards [B * samples, horizon + 1, 1]):
         ``rollout``'s layout, with its dummy step 0 and ``symexp``.  ``return_uncertainty=True`` appends ``uncertainty
         [B * samples, horizon + 1, 1]`` as ``rollout`` does: the per-frame mean predictive entropy from the same ``generate`` call
-        (``output_token_scores``), equal to ``rollout``'s bit for bit on the same actions and uniforms."""
+        (``output_token_scores``), equal to ``rollout``'s bit for bit on the same actions and uniforms.
+        ``return_proposal_logprob=True`` appends, after it, ``proposal_logprob [B * samples, horizon + 1, 1]``: per imagined frame the
+        summed log-probability of its 16 sampled tokens under the temperature / top-k / top-p distribution they were drawn from
+        (``FilteredTokenScores.per_frame``, ``output_filtered_scores``), 0 for step 0 -- the proposal term of an importance weight or a
+        likelihood ratio over candidates."""
         from ivideogpt_amd.transformer import _from_group_major, _to_group_major
         self._suspend_active()
         ctx, model = self.context_length, self.model
@@ -444,7 +451,7 @@ class VideoPredictor:
         tokens, hidden, *scores = model.generate(prompt.repeat(t, 1), do_sample=True, temperature=1.0, top_k=100, max_new_tokens=17 * horizon - 1,
                                                  action=_from_group_major(table.contiguous(), t, B), generator=generator, uniforms=u,
                                                  output_frame_hidden_states=True, shared_context=t if t > 1 else None,
-                                                 output_token_scores=return_uncertainty)
+                                                 output_token_scores=return_uncertainty, output_filtered_scores=return_proposal_logprob)
         rewards = model.reward_linear(hidden).squeeze(-1)                      # (B * samples, horizon)
         clip = self.tokenizer.detokenize(tokens, ctx, shared_context=t if t > 1 else None)
         rewards, clip = _to_group_major(rewards, t, B), _to_group_major(clip, t, B)
@@ -454,7 +461,9 @@ class VideoPredictor:
         rewards = torch.cat([torch.zeros_like(rewards[:, :1]), rewards], 1).unsqueeze(-1)
         if self.symlog:
             rewards = symexp(rewards)
+        extra = []
         if return_uncertainty:
-            unc = _to_group_major(scores[0].per_frame()[1], t, B)             # (B * samples, horizon)
-            return obss, actions, rewards.float(), torch.cat([torch.zeros_like(unc[:, :1]), unc], 1).unsqueeze(-1).float()
-        return obss, actions, rewards.float()
+            extra.append(_to_group_major(scores[0].per_frame()[1], t, B))     # (B * samples, horizon)
+        if return_proposal_logprob:
+            extra.append(_to_group_major(scores[-1].per_frame()[0], t, B))
+        return (obss, actions, rewards.float(), *(torch.cat([torch.zeros_like(x[:, :1]), x], 1).unsqueeze(-1).float() for x in extra))
