@@ -787,7 +787,13 @@ __device__ __forceinline__ float group_sum(float d, int lpk) {
 // exists: a key row t is read from the group's cache row when t < P and from the trajectory's otherwise.  The same arithmetic in the
 // same order as the un-shared kernel on the same bytes; the prefix rows use default-policy loads (the other rows of the group ask for
 // the same lines: they are served from L2 / Infinity Cache instead of HBM).
-template <typename T, bool NT, int HD, bool SHARED = false>
+// WINDOW (the default body of the bf16 head_dim-64 instances; IVG_DECODE_ATTN_WINDOW=0 under IVG_DEV=1 selects the two-buffer body):
+// ONE buffer of UNR chunks as a rolling window over the rows -- chunk u of the next round is requested into the registers chunk u of
+// the current round was just consumed from.  Memory returns in order, so with the round unrolled every wait is a counted vmcnt and a
+// lane has UNR loads outstanding at all times (the two-buffer body: UNR to 2 x UNR, in 64 registers of row data instead of 32).  The
+// key -> lane-group map, the instructions per key, the order of a lane group's value rows and everything around the two passes are
+// the two-buffer body's: the outputs are bit-identical.  Half the registers: twice the waves of OTHER launches fit beside it.
+template <typename T, bool NT, int HD, bool SHARED = false, bool WINDOW = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                           T* __restrict__ out, const float* __restrict__ cosT,
                                                           const float* __restrict__ sinT, int heads, int hd_arg, int Lmax,
@@ -826,18 +832,29 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
   // out before the step counter is even read (limit = Lmax: the rows exist in the cache buffer whatever they hold; rows >= pos are
   // never used -- the score and value passes test t < pos) -- the counter's load, a dependent memory round trip at the head of every
   // launch, then overlaps that round instead of preceding it (round 6)
-  auto load_rows = [&](Chunk16 (&dst)[UNR], const T* base, int t0, int limit) {
-    const char* bb = (const char*)base;
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int t = t0 + u * gpb + grp;
-      const char* rb = bb;
-      if constexpr (SHARED) rb = t < sh_P ? bb + sh_delta : bb;
-      const Chunk16* src = (const Chunk16*)(rb + ((unsigned)(t * hd) * (unsigned)sizeof(T) + lane_off));
-      dst[u] = t < limit ? ((NT && !SHARED) ? __builtin_nontemporal_load(src) : *src) : Chunk16{0u, 0u, 0u, 0u};
-    }
+  auto load_row = [&](Chunk16& dst, const T* base, int t, int limit) {
+    const char* rb = (const char*)base;
+    if constexpr (SHARED) rb = t < sh_P ? rb + sh_delta : rb;
+    const Chunk16* src = (const Chunk16*)(rb + ((unsigned)(t * hd) * (unsigned)sizeof(T) + lane_off));
+    dst = t < limit ? ((NT && !SHARED) ? __builtin_nontemporal_load(src) : *src) : Chunk16{0u, 0u, 0u, 0u};
   };
-  Chunk16 cur[UNR], nxt[UNR];
+  auto load_rows = [&](Chunk16 (&dst)[UNR], const T* base, int t0, int limit) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) load_row(dst[u], base, t0 + u * gpb + grp, limit);
+  };
+  // WINDOW: the rows through a buffer descriptor (wave-uniform: head base, bytes below `limit`) and a 32-bit lane offset -- its range
+  // check returns the zeros of rows >= limit without a branch around the load (a load under a branch cannot be waited for by
+  // count), and the address is one register.  SHARED: the descriptor starts at the GROUP's head base (sh_delta <= 0: a group's slot
+  // is never behind its trajectories); a trajectory's own rows lie own_off bytes above it (the launcher checks that this fits).
+  const unsigned own_off = (unsigned)(-sh_delta);
+  auto win_load = [&](Chunk16& dst, const T* base, int t, int limit) {
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + sh_delta), 0,
+                                                        (int)(own_off + (unsigned)(limit * hd) * (unsigned)sizeof(T)), 0x00020000);
+    unsigned off = (unsigned)(t * hd) * (unsigned)sizeof(T) + lane_off;
+    if constexpr (SHARED) off += t < sh_P ? 0u : own_off;
+    dst = __builtin_bit_cast(Chunk16, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, (NT && !SHARED) ? 2 : 0));
+  };
+  Chunk16 cur[UNR], nxt[WINDOW ? 1 : UNR];
   // the few loads of the RoPE step go out BEFORE the first round of key rows: memory returns in order, so issued after them
   // they (and the barrier behind them) would wait for the whole 32 KiB round
   float rc = 0.f, rs = 0.f, q1 = 0.f, q2 = 0.f, k1 = 0.f, k2 = 0.f;
@@ -848,7 +865,12 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
     k1 = to_f32(row[H + tid]); k2 = to_f32(row[H + tid + half]);
     va = row[2 * H + tid]; vb2 = row[2 * H + tid + half];
   }
-  load_rows(cur, kb, 0, Lmax);  // the first key rows are in flight while the step counter arrives and q is roped
+  if constexpr (WINDOW) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) win_load(cur[u], kb, u * gpb + grp, Lmax);
+  } else {
+    load_rows(cur, kb, 0, Lmax);  // the first key rows are in flight while the step counter arrives and q is roped
+  }
   const int pos = state->pos;        // position of the token being fed = number of cached keys
   const int n_keys = pos + 1;
   if (tid < half) { rc = cosT[(long)pos * half + tid]; rs = sinT[(long)pos * half + tid]; }
@@ -881,7 +903,23 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
       if (t < pos && sub == 0) sc[t] = d * scale;
     }
   };
-  {
+  if constexpr (WINDOW) {
+    // the window: chunk u scored, then chunk u of the next round (key rows, or the first value rows behind the last key round)
+    // requested into its registers
+    for (int t0 = 0; t0 < pos; t0 += step) {
+      const bool more = t0 + step < pos;
+      const T* nb = more ? kb : vb;
+      const int nt0 = more ? t0 + step : 0;
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int t = t0 + u * gpb + grp;
+        float d = qp.dot(qf, cur[u]);
+        d = group_sum(d, lpk);
+        if (t < pos && sub == 0) sc[t] = d * scale;
+        win_load(cur[u], nb, nt0 + u * gpb + grp, pos);
+      }
+    }
+  } else {
     int t0 = 0;
     bool in_nxt = false;   // the rows to consume next are in `nxt`
     while (t0 < pos) {
@@ -932,6 +970,23 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
       if (t < pos) axpy_chunk<T>(of, sc[t], rows[u]);
     }
   };
+  if constexpr (WINDOW) {   // cur holds value rows [0, step); every round but the last refills the window behind itself
+    int t0 = 0;
+    for (; t0 + step < pos; t0 += step) {
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int t = t0 + u * gpb + grp;
+        axpy_chunk<T>(of, sc[t], cur[u]);   // t < t0 + step < pos
+        // a straight-line round: the sums pinned here and the scheduler fenced below, or the optimiser regroups the round's
+        // multiply-adds by output element behind all of its requests -- into a second buffer of registers
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) asm volatile("" : "+v"(of[j]));
+        win_load(cur[u], vb, t + step, pos);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (pos > 0) weighted(cur, t0);
+  } else {
     for (int t0 = 0; t0 < pos; t0 += 2 * step) {  // cur holds value rows [t0, t0 + step) (requested during pass A / the last iteration)
       if (t0 + step < pos) load_rows(nxt, vb, t0 + step, pos);
       weighted(cur, t0);
@@ -939,6 +994,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
       if (t0 + 2 * step < pos) load_rows(cur, vb, t0 + 2 * step, pos);
       weighted(nxt, t0 + step);
     }
+  }
   if (grp == 0) {
     const float pw = sc[pos];
 #pragma unroll
@@ -971,6 +1027,7 @@ int launch_decode_attn(const void* qkv, void* kc, void* vc, void* out, const flo
   const int gpb = 256 / (hd / vec);
   const size_t smem = (size_t)(3 * hd + Lmax + gpb * hd) * sizeof(float);
   dim3 g(B * heads);
+  const bool window = sw().decode_attn_window != 0;   // bf16, head_dim 64: the rolling-window body (development switch: the two-buffer one)
   // non-temporal cache-row loads (bf16): 5.57 -> 6.28 TB/s on a pure stream, 203 -> 191 ms per rollout
 #define IVG_DA(T, NTv, HDv) \
   hipLaunchKernelGGL((decode_attn_kernel<T, NTv, HDv>), g, dim3(256), smem, st, (const T*)qkv, (T*)kc, (T*)vc, (T*)out, cosT, sinT, heads, hd, Lmax, state, prof, 0, 1, 0)
@@ -978,12 +1035,18 @@ int launch_decode_attn(const void* qkv, void* kc, void* vc, void* out, const flo
     if (sh_P < 0 || sh_row0 > 0) return (int)hipErrorInvalidValue;
 #define IVG_DAS(T, NTv, HDv) \
   hipLaunchKernelGGL((decode_attn_kernel<T, NTv, HDv, true>), g, dim3(256), smem, st, (const T*)qkv, (T*)kc, (T*)vc, (T*)out, cosT, sinT, heads, hd, Lmax, state, prof, sh_P, sh_G, sh_row0)
-    if (dt == BF16) { if (hd == 64) IVG_DAS(bf16_t, true, 64); else IVG_DAS(bf16_t, true, 0); }
+    // the window body addresses a trajectory's rows from its GROUP's head base: the slot not behind the row, 32-bit distances
+    const bool near = sh_row0 > -sh_G && (long)B * heads * Lmax * hd * 2 < (1l << 32);
+    if (dt == BF16 && hd == 64 && window && near)
+      hipLaunchKernelGGL((decode_attn_kernel<bf16_t, true, 64, true, true>), g, dim3(256), smem, st, (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, (bf16_t*)out, cosT, sinT, heads, hd, Lmax, state, prof, sh_P, sh_G, sh_row0);
+    else if (dt == BF16) { if (hd == 64) IVG_DAS(bf16_t, true, 64); else IVG_DAS(bf16_t, true, 0); }
     else { if (hd == 64) IVG_DAS(float, false, 64); else IVG_DAS(float, false, 0); }
 #undef IVG_DAS
     return (int)hipGetLastError();
   }
-  if (dt == BF16) { if (hd == 64) IVG_DA(bf16_t, true, 64); else IVG_DA(bf16_t, true, 0); }
+  if (dt == BF16 && hd == 64 && window)
+    hipLaunchKernelGGL((decode_attn_kernel<bf16_t, true, 64, false, true>), g, dim3(256), smem, st, (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, (bf16_t*)out, cosT, sinT, heads, hd, Lmax, state, prof, 0, 1, 0);
+  else if (dt == BF16) { if (hd == 64) IVG_DA(bf16_t, true, 64); else IVG_DA(bf16_t, true, 0); }
   else { if (hd == 64) IVG_DA(float, false, 64); else IVG_DA(float, false, 0); }
 #undef IVG_DA
   return (int)hipGetLastError();

@@ -38,6 +38,7 @@ static Switches read_env() {
   s.dg2_mf_cap = dv("IVG_DG2_MF_CAP", 0);
   if (s.dg2_mf_cap != 1 && s.dg2_mf_cap != 2) s.dg2_mf_cap = 0;
   s.inflight_gemm256 = dv("IVG_INFLIGHT_GEMM256", 1) != 0;
+  s.decode_attn_window = dv("IVG_DECODE_ATTN_WINDOW", 1) != 0;
   if (const char* v = dev ? getenv("IVG_INFLIGHT_KB") : nullptr) {
     int k[5] = {0, 0, 0, 0, 0};
     if (sscanf(v, "%d,%d,%d,%d,%d", &k[0], &k[1], &k[2], &k[3], &k[4]) == 5)
@@ -53,7 +54,7 @@ bool Switches::operator==(const Switches& o) const {
   return conv3x3 == o.conv3x3 && subpixel == o.subpixel && gemm256 == o.gemm256 && dg3 == o.dg3 && flash_prefill == o.flash_prefill &&
          flash_xatt == o.flash_xatt && gn_fuse == o.gn_fuse && gn_apply_fuse == o.gn_apply_fuse && x3 == o.x3 && gemm256x3 == o.gemm256x3 && kv24 == o.kv24 && kv_extend_chunk == o.kv_extend_chunk && graph == o.graph &&
          dg3_warm == o.dg3_warm && warm_gate_up == o.warm_gate_up && conv_cap == o.conv_cap && decode_lds_kb == o.decode_lds_kb && decode_w_shared == o.decode_w_shared &&
-         inflight_warm == o.inflight_warm && dg2_mf_cap == o.dg2_mf_cap && inflight_gemm256 == o.inflight_gemm256 &&
+         inflight_warm == o.inflight_warm && dg2_mf_cap == o.dg2_mf_cap && inflight_gemm256 == o.inflight_gemm256 && decode_attn_window == o.decode_attn_window &&
          std::equal(inflight_kb, inflight_kb + 5, o.inflight_kb);
 }
 

@@ -40,13 +40,15 @@
 //                                        gate/up, down, lm_head): which GEMMs may keep their whole K range in flight (one memory round trip)
 //   IVG_INFLIGHT_GEMM256     1        the same engines: 0 = prompt-pass GEMMs on the 256-thread implicit-GEMM kernel instead of the 1024-thread /
 //                                        128 KiB gemm256l workgroups (which wait for a whole CU to drain while other batches are in flight)
+//   IVG_DECODE_ATTN_WINDOW   1        0: bf16 head_dim-64 decode attention on the two-buffer body (1: one row buffer as a rolling window, half the
+//                                        registers; bit-identical outputs -- llama_ops.hip decode_attn_kernel WINDOW)
 #pragma once
 
 namespace ivg {
 
 struct Switches {
   int conv3x3 = 1, subpixel = 1, gemm256 = 1, dg3 = 1, flash_prefill = 1, flash_xatt = 1, gn_fuse = 1, gn_apply_fuse = 1, x3 = 1, gemm256x3 = 1, kv24 = 1, kv_extend_chunk = 1;
-  int graph = 0, dg3_warm = 1, warm_gate_up = 0, conv_cap = 0, decode_lds_kb = 160, decode_w_shared = 1, inflight_warm = 0, dg2_mf_cap = 0, inflight_gemm256 = 1;
+  int graph = 0, dg3_warm = 1, warm_gate_up = 0, conv_cap = 0, decode_lds_kb = 160, decode_w_shared = 1, inflight_warm = 0, dg2_mf_cap = 0, inflight_gemm256 = 1, decode_attn_window = 1;
   int inflight_kb[5] = {0, 0, 0, 0, 0};
   bool operator==(const Switches& o) const;
 };
