@@ -467,7 +467,6 @@ static bool dg_plan(const SkinnyArgs& a, DType dtype, DgPlan& pl) {
     nburst = total / lgv;
   }
   while (MF > 1 && waves * lgv * (MF + FN) * 2048 > budget) MF >>= 1;
-  if (a.w_shared && sw().dg2_mf_cap > 0) MF = std::min(MF, sw().dg2_mf_cap);   // development A/B (IVG_DG2_MF_CAP)
   const int wmax = dg_wmax(MF, FN, waves);
   if (!wmax || dg_smem(MF, FN, lgv, waves) > 160 * 1024) return false;
   pl = DgPlan{MF, FN, waves, lgv, nburst, wmax};
@@ -481,7 +480,7 @@ int launch_dgemm(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
   const int MF = pl.mf, FN = pl.fn, waves = pl.waves, lgv = pl.lg, nburst = pl.nburst;
   DgDev d{a.X, a.W, a.Y, a.M, a.N, a.K, a.ldx, a.ldw, a.ldy, a.flags, a.eps, a.bump, nburst, a.pos ? a.prof : nullptr, a.pos, a.prof_ld, a.dbg,
           nullptr, 0u, 0, 0, a.w_shared ? 0 : 1};
-  if (a.next_W && a.next_tile_bytes >= 1024 && a.next_tiles > 0 && sw().dg3_warm) {
+  if (a.next_W && a.next_tile_bytes >= 1024 && a.next_tiles > 0) {
     const long grid = (long)cdiv(a.N, 16 * FN) * cdiv(a.M, 16 * MF);
     const long waves_per_xcd = std::max(1L, grid / 8) * waves;
     const long units_per_xcd = (long)cdiv(a.next_tiles, 8) * (a.next_tile_bytes >> 10);

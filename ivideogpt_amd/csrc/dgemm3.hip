@@ -517,7 +517,7 @@ int launch_dgemm3(const SkinnyArgs& a, DType dtype, hipStream_t stream) {
   d.x3 = (a.x3 && dtype == F32) ? 1 : 0;
   d.prof = a.pos ? a.prof : nullptr; d.pos = a.pos; d.prof_ld = a.prof_ld;
   d.dbg = a.dbg;
-  if (a.next_W && a.next_tile_bytes >= 1024 && a.next_tiles > 0 && sw().dg3_warm) {   // IVG_DG3_WARM=0: no warm-up of the next launch's weights
+  if (a.next_W && a.next_tile_bytes >= 1024 && a.next_tiles > 0) {
     const long grid = (long)cdiv(a.N, pl.wr) * cdiv(a.M, 16 * pl.mf);
     const long waves_per_xcd = std::max(1L, grid / 8) * pl.waves;
     const long units_per_xcd = (long)cdiv(a.next_tiles, 8) * (a.next_tile_bytes >> 10);

@@ -678,7 +678,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(const bf16_t* __restrict__ q
 
 // one predicate for the planner and the launcher: which (dtype, shape) the one-pass kernel covers
 bool xattn_covers(int P, int kv, int C, int nh, DType dt) {
-  if (!sw().flash_xatt || dt != BF16 || nh <= 0 || C % nh != 0 || P % 64 != 0 || kv % 64 != 0 || (C & 7)) return false;
+  if (dt != BF16 || nh <= 0 || C % nh != 0 || P % 64 != 0 || kv % 64 != 0 || (C & 7)) return false;
   const int hd = C / nh;
   return hd == 32 || hd == 64 || hd == 128 || hd == 192 || hd == 512 || hd == 768;
 }

@@ -1,9 +1,7 @@
 // The switch table of libivg (switches.h): read from the environment, published through one atomic pointer.
 #include "switches.h"
 
-#include <algorithm>
 #include <atomic>
-#include <cstdio>
 #include <cstdlib>
 #include <mutex>
 
@@ -14,48 +12,42 @@ static int env_int(const char* name, int dflt) {
   return (v && v[0]) ? atoi(v) : dflt;
 }
 
+// One row per switch; read_env and operator== are loops over it.
+enum Class { POLICY, DEV };              // DEV: a development (A/B) switch, inert without IVG_DEV=1
+enum Norm { NONZERO, IS_ONE, RANGE };    // raw value -> field: v != 0, v == 1, or v itself inside [lo, hi] (else the default)
+struct Row { const char* env; int Switches::*field; int dflt; Class cls; Norm norm; int lo, hi; };
+static const Row kRows[] = {
+  {"IVG_GRAPH", &Switches::graph, 0, POLICY, IS_ONE},
+  {"IVG_DECODE_LDS_KB", &Switches::decode_lds_kb, 160, POLICY, RANGE, 16, 160},
+  {"IVG_CONV3X3", &Switches::conv3x3, 1, DEV, NONZERO},
+  {"IVG_SUBPIXEL", &Switches::subpixel, 1, DEV, NONZERO},
+  {"IVG_GEMM256", &Switches::gemm256, 1, DEV, NONZERO},
+  {"IVG_GEMM256X3", &Switches::gemm256x3, 1, DEV, NONZERO},
+  {"IVG_KV24", &Switches::kv24, 1, DEV, NONZERO},
+  {"IVG_DG3", &Switches::dg3, 1, DEV, NONZERO},
+  {"IVG_FLASH_PREFILL", &Switches::flash_prefill, 1, DEV, NONZERO},
+  {"IVG_KV_EXTEND_CHUNK", &Switches::kv_extend_chunk, 1, DEV, NONZERO},
+  {"IVG_GN_APPLY_FUSE", &Switches::gn_apply_fuse, 1, DEV, NONZERO},
+  {"IVG_X3", &Switches::x3, 1, DEV, NONZERO},
+  {"IVG_CONV_CAP", &Switches::conv_cap, 0, DEV, IS_ONE},
+  {"IVG_DECODE_ATTN_WINDOW", &Switches::decode_attn_window, 1, DEV, NONZERO},
+};
+static_assert(sizeof(Switches) == sizeof(kRows) / sizeof(kRows[0]) * sizeof(int), "a field of Switches without a row (or a row too many)");
+
 static Switches read_env() {
-  Switches s;
-  const bool dev = env_int("IVG_DEV", 0) == 1;   // the A/B switches are development tools: inert without it
-  auto dv = [&](const char* name, int dflt) { return dev ? env_int(name, dflt) : dflt; };
-  s.conv3x3 = dv("IVG_CONV3X3", 1) != 0;
-  s.subpixel = dv("IVG_SUBPIXEL", 1) != 0;
-  s.gemm256 = dv("IVG_GEMM256", 1) != 0;
-  s.gemm256x3 = dv("IVG_GEMM256X3", 1) != 0;
-  s.kv24 = dv("IVG_KV24", 1) != 0;
-  s.dg3 = dv("IVG_DG3", 1) != 0;
-  s.flash_prefill = dv("IVG_FLASH_PREFILL", 1) != 0;
-  s.kv_extend_chunk = dv("IVG_KV_EXTEND_CHUNK", 1) != 0;
-  s.flash_xatt = dv("IVG_FLASH_XATT", 1) != 0;
-  s.gn_fuse = dv("IVG_GN_FUSE", 1) != 0;
-  s.gn_apply_fuse = dv("IVG_GN_APPLY_FUSE", 1) != 0;
-  s.x3 = dv("IVG_X3", 1) != 0;
-  s.dg3_warm = dv("IVG_DG3_WARM", 1) != 0;
-  s.warm_gate_up = dv("IVG_WARM_GATE_UP", 0) != 0;
-  s.conv_cap = dv("IVG_CONV_CAP", 0) == 1;
-  s.decode_w_shared = dv("IVG_DECODE_W_SHARED", 1) != 0;
-  s.inflight_warm = dv("IVG_INFLIGHT_WARM", 0) != 0;
-  s.dg2_mf_cap = dv("IVG_DG2_MF_CAP", 0);
-  if (s.dg2_mf_cap != 1 && s.dg2_mf_cap != 2) s.dg2_mf_cap = 0;
-  s.inflight_gemm256 = dv("IVG_INFLIGHT_GEMM256", 1) != 0;
-  s.decode_attn_window = dv("IVG_DECODE_ATTN_WINDOW", 1) != 0;
-  if (const char* v = dev ? getenv("IVG_INFLIGHT_KB") : nullptr) {
-    int k[5] = {0, 0, 0, 0, 0};
-    if (sscanf(v, "%d,%d,%d,%d,%d", &k[0], &k[1], &k[2], &k[3], &k[4]) == 5)
-      for (int i = 0; i < 5; ++i) s.inflight_kb[i] = (k[i] >= 16 && k[i] <= 160) ? k[i] : 0;
+  Switches s{};
+  const bool dev = env_int("IVG_DEV", 0) == 1;
+  for (const Row& r : kRows) {
+    const int v = (r.cls == DEV && !dev) ? r.dflt : env_int(r.env, r.dflt);
+    s.*r.field = r.norm == NONZERO ? v != 0 : r.norm == IS_ONE ? v == 1 : (v >= r.lo && v <= r.hi) ? v : r.dflt;
   }
-  s.graph = env_int("IVG_GRAPH", 0) == 1;
-  s.decode_lds_kb = env_int("IVG_DECODE_LDS_KB", 160);
-  if (s.decode_lds_kb < 16 || s.decode_lds_kb > 160) s.decode_lds_kb = 160;
   return s;
 }
 
 bool Switches::operator==(const Switches& o) const {
-  return conv3x3 == o.conv3x3 && subpixel == o.subpixel && gemm256 == o.gemm256 && dg3 == o.dg3 && flash_prefill == o.flash_prefill &&
-         flash_xatt == o.flash_xatt && gn_fuse == o.gn_fuse && gn_apply_fuse == o.gn_apply_fuse && x3 == o.x3 && gemm256x3 == o.gemm256x3 && kv24 == o.kv24 && kv_extend_chunk == o.kv_extend_chunk && graph == o.graph &&
-         dg3_warm == o.dg3_warm && warm_gate_up == o.warm_gate_up && conv_cap == o.conv_cap && decode_lds_kb == o.decode_lds_kb && decode_w_shared == o.decode_w_shared &&
-         inflight_warm == o.inflight_warm && dg2_mf_cap == o.dg2_mf_cap && inflight_gemm256 == o.inflight_gemm256 && decode_attn_window == o.decode_attn_window &&
-         std::equal(inflight_kb, inflight_kb + 5, o.inflight_kb);
+  for (const Row& r : kRows)
+    if (this->*r.field != o.*r.field) return false;
+  return true;
 }
 
 // A reload that CHANGES the table publishes a new immutable one through one atomic pointer and never frees or rewrites the old

@@ -25,32 +25,20 @@
 //   IVG_FLASH_PREFILL        1        0: prompt attention as score GEMM + softmax + P.V GEMM (what the fp32 engine mode runs)
 //   IVG_KV_EXTEND_CHUNK      1        0: ivg_kv_extend appends by decode steps with given inputs on every engine (1: one chunk pass over the
 //                                        given tokens where the cache is native bf16 at head_dim 64, transformer.cpp Run::extend)
-//   IVG_FLASH_XATT           1        0: tokenizer attention as score GEMM + softmax + P.V GEMM
-//   IVG_GN_FUSE              1        0: every GroupNorm computes its own statistics (1: reduced by the producing conv3x3's epilogue)
 //   IVG_GN_APPLY_FUSE        1        0: GroupNorm + SiLU as a separate apply pass (1: inside the consuming conv3x3's halo staging)
 //   IVG_X3                   1        0: the fp32 decode path of the tokenizer on f32-input MFMAs (1: split-bf16 "x3" convolutions)
-//   IVG_DG3_WARM             1        0: decode GEMMs do not pull the next launch's weights toward the chip
-//   IVG_WARM_GATE_UP         0        1: o-proj also warms the gate/up matrix (round 5's behaviour; measured neutral in time, 1.6 x the traffic)
 //   IVG_CONV_CAP             0        1: conv3x3 grids at ONE workgroup per CU (LDS padded past half a CU's 160 KiB)
-//   IVG_DECODE_W_SHARED      1        engines with the batches-in-flight profile: 0 = non-temporal weight requests as for one batch alone
-//   IVG_INFLIGHT_WARM        0        the same engines: 1 = keep warming the next launch's weights
-//   IVG_DG2_MF_CAP           0        the same engines: > 0 caps the row tiles per workgroup of the second-generation decode GEMMs (smaller
-//                                        workgroups, more of them co-resident per CU; row grouping only -- never a summation order)
-//   IVG_INFLIGHT_KB          -        "q,o,g,d,l": per-kind LDS budgets (KiB, 0 = the engine's) of the same engines' decode GEMMs (q/k/v, o-proj,
-//                                        gate/up, down, lm_head): which GEMMs may keep their whole K range in flight (one memory round trip)
-//   IVG_INFLIGHT_GEMM256     1        the same engines: 0 = prompt-pass GEMMs on the 256-thread implicit-GEMM kernel instead of the 1024-thread /
-//                                        128 KiB gemm256l workgroups (which wait for a whole CU to drain while other batches are in flight)
 //   IVG_DECODE_ATTN_WINDOW   1        0: bf16 head_dim-64 decode attention on the two-buffer body (1: one row buffer as a rolling window, half the
 //                                        registers; bit-identical outputs -- llama_ops.hip decode_attn_kernel WINDOW)
 #pragma once
 
 namespace ivg {
 
+// A new switch is a field here, a row of the table in switches.cpp (name, default, class, normalisation) and a line above.
 struct Switches {
-  int conv3x3 = 1, subpixel = 1, gemm256 = 1, dg3 = 1, flash_prefill = 1, flash_xatt = 1, gn_fuse = 1, gn_apply_fuse = 1, x3 = 1, gemm256x3 = 1, kv24 = 1, kv_extend_chunk = 1;
-  int graph = 0, dg3_warm = 1, warm_gate_up = 0, conv_cap = 0, decode_lds_kb = 160, decode_w_shared = 1, inflight_warm = 0, dg2_mf_cap = 0, inflight_gemm256 = 1, decode_attn_window = 1;
-  int inflight_kb[5] = {0, 0, 0, 0, 0};
-  bool operator==(const Switches& o) const;
+  int graph, decode_lds_kb;
+  int conv3x3, subpixel, gemm256, gemm256x3, kv24, dg3, flash_prefill, kv_extend_chunk, gn_apply_fuse, x3, conv_cap, decode_attn_window;
+  bool operator==(const Switches& o) const;   // over the rows of the table
 };
 
 const Switches& sw();             // the published table: immutable, never freed or rewritten (a reload that changes it publishes a NEW one)

@@ -26,8 +26,6 @@ namespace ivg {
 static size_t esz(DType d) { return d == BF16 ? 2 : 4; }
 
 // -------------------------------------------------------------------------------------------- primitive wrappers
-static bool gn_fuse_enabled() { return sw().gn_fuse != 0; }   // IVG_GN_FUSE=0: every GroupNorm computes its own statistics (A/B runs)
-
 size_t Run::gn_stats_bytes(int N, int H, int W, int C) const {
   return (size_t)N * conv3x3_gn_chunks_bound(H, W, C) * e->cfg.norm_num_groups * sizeof(double) * 2;
 }
@@ -50,7 +48,7 @@ int Run::conv(DType dt, const void* X, int N, int H, int W, const ConvW& c, void
   a.c_img = (long)Ho * Wo * c.cout; a.c_pix = c.cout; a.c_ch = 1;
   a.flags = flags | (c.b ? IG_BIAS_N : 0) | (Rres ? IG_RESIDUAL : 0) | (out_f32 ? IG_OUT_F32 : 0);
   if (planning) return 0;
-  if (out_stats && out_stats->part && gn_fuse_enabled()) { a.gn_part = out_stats->part; a.gn_groups = e->cfg.norm_num_groups; }
+  if (out_stats && out_stats->part) { a.gn_part = out_stats->part; a.gn_groups = e->cfg.norm_num_groups; }
   a.gn_in_coef = in_coef;
   if (dt == F32 && x3 && sw().x3) { a.x3 = true; a.W_x3 = c.w3; }   // split-bf16 arithmetic (IVG_F32X3 decode; IVG_X3=0: f32-input MFMAs)
   if (ups) { a.W_sub = c.wsub; a.W_sub_x3 = a.W_x3 ? c.wsub3 : nullptr; }   // upsampling convolutions in sub-pixel form (conv3x3.hip SUBPIX)
@@ -81,8 +79,7 @@ int Run::gemm(DType dt, const IgemmArgs& a0, double flops, double bytes) {
   IgemmArgs a = a0;
   a.x3 = dt == F32 && x3 && sw().x3;
   prof_begin(dt, flops, bytes);
-  int rc = -1;
-  if (!(e->in_flight() && !sw().inflight_gemm256)) rc = launch_gemm256(a, dt, st);   // large dense GEMMs (prompt pass); -1 = not covered
+  int rc = launch_gemm256(a, dt, st);   // large dense GEMMs (prompt pass); -1 = not covered
   if (rc == -1) rc = launch_igemm(a, dt, st);
   CK(rc);
   prof_end(dt);

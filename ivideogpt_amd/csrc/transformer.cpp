@@ -229,7 +229,7 @@ int Run::prefill(const PrefillReq& q) {
     SkinnyArgs s;
     s.X = q.hidden_last; s.W = e->lm_head; s.Y = q.logits_last; s.M = B; s.N = V; s.K = H; s.ldx = H; s.ldw = H; s.ldy = V;
     s.flags = IG_OUT_F32 | SK_NORM; s.eps = c.rms_norm_eps; s.lds_kb = e->decode_lds_kb;
-    s.w_shared = e->in_flight() && sw().decode_w_shared;   // (the same policy as the steps' lm_head: one copy of the weights under several engines)
+    s.w_shared = e->in_flight();   // (the same policy as the steps' lm_head: one copy of the weights under several engines)
     CK(launch_skinny(s, dt, st));
   }
   e->ws.reset(m);
@@ -266,13 +266,13 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, const StepO
   };
   // The batches-in-flight profile of an engine (an LDS budget below a whole CU, set per engine -- ivg_config.decode_lds_kb -- or process-wide
   // -- IVG_DECODE_LDS_KB: it shares the GPU -- and ONE copy of the weights -- with other engines, bench.py --lanes): beside the LDS budget, (1) the weight requests of the decode GEMMs use the default cache policy
-  // instead of non-temporal ones -- the other engines ask for the same lines within microseconds (+1.7 %, IVG_DECODE_W_SHARED=0 for
-  // A/B) -- and (2) no launch warms the next launch's weights: with (1) the other lanes' launches already do, and the extra requests
-  // only compete with three attention streams (+2.0 % on top, IVG_INFLIGHT_WARM=1 for A/B; profiles/r05_lanes_policy.txt).  One batch
-  // alone keeps non-temporal weights + warm-up (rounds 2 / 3: each byte is read once per token, the warm-up hides its first touch).
+  // instead of non-temporal ones -- the other engines ask for the same lines within microseconds (+1.7 %) -- and (2) no launch warms
+  // the next launch's weights: with (1) the other lanes' launches already do, and the extra requests only compete with three attention
+  // streams (+2.0 % on top; profiles/r05_lanes_policy.txt).  One batch alone keeps non-temporal weights + warm-up (rounds 2 / 3: each
+  // byte is read once per token, the warm-up hides its first touch).
   const bool in_flight = e->in_flight();
-  const bool w_shared = in_flight && sw().decode_w_shared;
-  const bool warm = !in_flight || sw().inflight_warm;
+  const bool w_shared = in_flight;
+  const bool warm = !in_flight;
   // every launch also pulls the weight tiles of the NEXT launch of the chain toward the CUs that will consume them (dgemm3.hip): the
   // dependent GEMM then starts on (Infinity-)cache hits instead of a cold HBM stream
   // Conditional per shape (round 6, profiles/r06_warmup_by_kind.txt): the gate/up matrix -- half of a layer's weight bytes -- is NOT warmed:
@@ -281,7 +281,7 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, const StepO
   // and lm_head keep their warm-up (0.4 - 1.8 us per launch each).
   auto link_next = [&](SkinnyArgs& cur, const SkinnyArgs& nxt) {
     if (!warm) return;
-    if ((nxt.flags & IG_GLU) && !sw().warm_gate_up) return;
+    if (nxt.flags & IG_GLU) return;
     int rows = dgemm3_w_rows_per_block(nxt, dt);
     if (rows <= 0) rows = dgemm_w_rows_per_block(nxt, dt);   // the next launch runs on the second-generation kernel
     if (rows <= 0 || nxt.ldw != nxt.K) return;
@@ -289,10 +289,7 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, const StepO
   };
   auto layer_args = [&](int l, SkinnyArgs* g) {
     const LayerW& w = e->layers[l];
-    for (int k = 0; k < 4; ++k) {
-      g[k].x3 = e->llm_x3 && sw().x3; g[k].lds_kb = e->decode_lds_kb; g[k].w_shared = w_shared; g[k].kind = k;
-      if (in_flight && sw().inflight_kb[k] > 0) g[k].lds_kb = sw().inflight_kb[k];
-    }
+    for (int k = 0; k < 4; ++k) { g[k].x3 = e->llm_x3 && sw().x3; g[k].lds_kb = e->decode_lds_kb; g[k].w_shared = w_shared; g[k].kind = k; }
     SkinnyArgs& s = g[0];
     s.X = x; s.W = w.wqkv; s.Y = qkv; s.M = B; s.N = 3 * H; s.K = H; s.ldx = H; s.ldw = H; s.ldy = 3 * H;
     s.flags = SK_NORM; s.eps = c.rms_norm_eps;
@@ -307,7 +304,6 @@ static int step_body(ivg_engine* e, hipStream_t st, const GenBuf& g, const StepO
   SkinnyArgs lm;
   lm.X = x; lm.W = e->lm_head; lm.Y = logits; lm.M = B; lm.N = V; lm.K = H; lm.ldx = H; lm.ldw = H; lm.ldy = V;
   lm.flags = IG_OUT_F32 | SK_NORM; lm.eps = c.rms_norm_eps; lm.lds_kb = e->decode_lds_kb; lm.w_shared = w_shared; lm.kind = 4;
-  if (in_flight && sw().inflight_kb[4] > 0) lm.lds_kb = sw().inflight_kb[4];
   lm.bump = (int*)state;  // pos += 1, j += 1 once the last reader of this chain's state (its last attention) is done
   SkinnyArgs cur[4], nxt[4];
   layer_args(0, cur);

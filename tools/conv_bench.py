@@ -1,4 +1,5 @@
 """Time one conv shape through the C ABI (development aid).  python tools/conv_bench.py H Cin Cout [ups] [N] [dtype] [gn]
+IVG_CONV3X3=0 in the environment times the generic implicit GEMM instead of the 3x3 kernel (the tool sets IVG_DEV=1 itself).
 gn = 1: conv3x3(silu(GroupNorm(x))) with the normalisation inside the staging (ivg_op_gn_conv)."""
 import ctypes as C
 import os
@@ -17,6 +18,7 @@ def main():
     dt = sys.argv[6] if len(sys.argv) > 6 else "bf16"
     gn = int(sys.argv[7]) if len(sys.argv) > 7 else 0
     tdt = torch.bfloat16 if dt == "bf16" else torch.float32
+    os.environ["IVG_DEV"] = "1"   # IVG_CONV3X3 (printed below) is a development switch: inert without it
     lib = _lib.load()
     dev = "cuda:0"
     Ho = 2 * H if ups else H

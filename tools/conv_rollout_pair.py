@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from ivideogpt_amd import CompressiveVQModel, LlamaForCausalLM, switches, weights as W  # noqa: E402
 
+os.environ["IVG_DEV"] = "1"   # IVG_CONV_CAP is a development switch: without it the "capped" arms would run the uncapped kernel
 T_MEAS = float(sys.argv[1]) if len(sys.argv) > 1 else 2.0
 dev = torch.device("cuda:0")
 tcfg = W.tokenizer_config(**W.CTX_VAE64)

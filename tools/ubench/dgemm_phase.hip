@@ -6,7 +6,8 @@
 //   * with the kernel's development stamps on (SkinnyArgs::dbg): where a launch's time goes -- entry -> DMA issued -> first line
 //     group landed -> last group landed -> MFMAs done -> combine -> stores issued, per wave, min / median / max over the
 //     workgroups, plus the spread of the workgroups' start and end times on the 100 MHz wall clock.
-// Usage: dgemm_phase [small|medium] [M]      (IVG_DG3 / IVG_DG3_WARM / IVG_DECODE_LDS_KB act as in the product: csrc/switches.h)
+// Usage: dgemm_phase [small|medium] [M]      (GEN=2|3 / GENMASK: kernel generation, WARM=0: no warm-up of the next launch's weights -- the
+//        tool's own variables; IVG_DECODE_LDS_KB acts as in the product: csrc/switches.h)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
