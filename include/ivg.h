@@ -631,6 +631,21 @@ int ivg_action_recon_sqerr(ivg_engine* e, const void* hidden, const float* actio
 int ivg_ingest_frames(const uint8_t* frames, int T, int H, int W, int center_crop, void* clip_out, int out_dtype, int resolution,
                       ivg_stream stream);
 
+/* The batched form: B clips that lie in ONE device buffer (the upload of a loader's pinned staging buffer), each with its own
+ * frame count and frame size, in one launch.
+ *   out[b][t] == bit for bit what ivg_ingest_frames writes for stored frame min(t, frames_b - 1) of clip b (its own H, W; the same
+ *   crop, resolution and dtype): a clip longer than T is truncated, a shorter one repeats its last frame (EvalDataset.get_segment,
+ *   simple_dataloader.py:522-526) -- on the device, from source bytes that are still read once.
+ * `clips` is a HOST array of B entries: it travels in the kernel arguments (64 clips per launch; a larger B takes ceil(B / 64)
+ * launches), so there is no device table to keep alive and no host synchronisation.  The kernel's aligned 32-bit loads stay inside
+ * [staging, staging + staging_bytes).  Engine-free.
+ * IVG_ERR_INVALID, before anything is launched or written: B <= 0, T <= 0 (or above 65535); a clip with frames, H or W < 1, an
+ * offset that is negative or no multiple of 16, or offset + frames * H * W * 3 > staging_bytes; any clip ivg_ingest_frames refuses
+ * (a downscale beyond 15, resolution above 1024). */
+typedef struct { int64_t offset; int32_t frames, H, W; } ivg_clip_desc;   /* offset: bytes from `staging` to the clip's first stored frame */
+int ivg_ingest_clips(const uint8_t* staging /* device */, size_t staging_bytes, const ivg_clip_desc* clips /* HOST, B entries */, int B, int T,
+                     int center_crop, void* out /* (B, T, 3, R, R) */, int out_dtype, int resolution, ivg_stream stream);
+
 /* Frame metrics of predicted clips on the device: Evaluator.forward of the reference without LPIPS
  * (ivideogpt/utils/video_metric.py:63-100; piqa PSNR(epsilon 1e-8, range 1) and SSIM(11 x 11 Gaussian, sigma 1.5, no padding)):
  * per frame mse / psnr / ssim, mean over the T frames of a trajectory, then the best of its t = n_samples / B samples

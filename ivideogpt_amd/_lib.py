@@ -67,6 +67,10 @@ class IvgPool3dArgs(C.Structure):
                [("k", C.c_int32 * 3), ("s", C.c_int32 * 3), ("p", C.c_int32 * 3), ("ldy", C.c_int32), ("coff", C.c_int32)]
 
 
+class IvgClipDesc(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "ivg_version": (C.c_char_p, []),
@@ -140,6 +144,7 @@ EXPORTS = {
     "ivg_action_recon_sqerr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p]),
     "ivg_ingest_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ivg_ingest_clips": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(IvgClipDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ivg_frame_metrics_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ivg_frame_metrics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

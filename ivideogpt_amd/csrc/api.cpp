@@ -1079,6 +1079,16 @@ int ivg_ingest_frames(const uint8_t* frames, int T, int H, int W, int center_cro
   return rc == 0 ? IVG_OK : (rc == (int)hipErrorInvalidValue ? IVG_ERR_INVALID : IVG_ERR_HIP);
 }
 
+int ivg_ingest_clips(const uint8_t* staging, size_t staging_bytes, const ivg_clip_desc* clips, int B, int T, int center_crop, void* out, int out_dtype,
+                     int resolution, ivg_stream stream) {
+  static_assert(sizeof(ivg_clip_desc) == sizeof(IngestClipDesc) && offsetof(ivg_clip_desc, frames) == offsetof(IngestClipDesc, frames) &&
+                offsetof(ivg_clip_desc, W) == offsetof(IngestClipDesc, W), "ivg_clip_desc is passed through as IngestClipDesc");
+  if (!staging || !clips || !out || (out_dtype != IVG_F32 && out_dtype != IVG_BF16)) return IVG_ERR_INVALID;
+  const int rc = launch_ingest_clips(staging, staging_bytes, reinterpret_cast<const IngestClipDesc*>(clips), B, T, center_crop, out, (DType)out_dtype,
+                                     resolution, (hipStream_t)stream);
+  return rc == 0 ? IVG_OK : (rc == (int)hipErrorInvalidValue ? IVG_ERR_INVALID : IVG_ERR_HIP);
+}
+
 size_t ivg_frame_metrics_ws_bytes(int n_samples, int T, int H, int W) { return frame_metrics_ws_bytes(n_samples, T, H, W); }
 
 int ivg_frame_metrics(const void* gt, int gt_dtype, int B, int T_gt, int gt_t0, const float* pred, int n_samples, int T_pr, int pr_t0, int T, int H,

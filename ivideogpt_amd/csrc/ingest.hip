@@ -11,6 +11,8 @@
 // One workgroup = one frame x a block of output rows.  HBM-bound, every source byte is read once: the source rows the block
 // needs arrive as aligned 32-bit words (an interleaved RGB row is one contiguous run), the horizontal pass goes LDS -> LDS,
 // the vertical pass LDS -> planar output with the x index fastest (coalesced stores).
+// Two kernels over that one body: ingest_kernel (T frames of one size) and ingest_clips_kernel (a batch of clips of one staging
+// buffer, each with its own frame count and size: what an eval loader uploads).
 #include <cmath>
 
 #include "ops.h"
@@ -49,8 +51,10 @@ __device__ __forceinline__ void aa_taps(int i, int in_size, float scale, float s
     for (int j = 0; j < xsize; ++j) w[j] /= total;
 }
 
+// One workgroup's work: block `blk` of output rows of the source frame at `frame`, written to `copies` consecutive output frames
+// from `out` on (copies > 1: a short clip's last frame, repeated).  p.src / p.total_bytes bound the aligned word loads.
 template <typename TO>
-__global__ __launch_bounds__(256) void ingest_kernel(const IngestDev p) {
+__device__ __forceinline__ void ingest_block(const IngestDev& p, const unsigned char* frame, TO* out, int blk, int copies) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // layout: wx [R][MAXT] f32 | xmin [R] | xsize [R] | wy [rows][MAXT] | ymin [rows] | ysize [rows] | hbuf [in_rows][R][3] f32 | bytes
   float* wx = (float*)smem;
@@ -63,7 +67,6 @@ __global__ __launch_bounds__(256) void ingest_kernel(const IngestDev p) {
   unsigned char* bytes = (unsigned char*)(hbuf + (size_t)p.in_rows_cap * p.R * 3);
   __shared__ int s_y0, s_y1;
   const int tid = threadIdx.x;
-  const int t = blockIdx.x / p.blocks_per_frame, blk = blockIdx.x % p.blocks_per_frame;
   const int r0 = blk * p.rows_per_wg, r1 = min(r0 + p.rows_per_wg, p.R);
   const float sx = (float)p.cw / (float)p.R, sy = (float)p.ch / (float)p.R;
   const float supx = sx >= 1.0f ? sx : 1.0f, supy = sy >= 1.0f ? sy : 1.0f;
@@ -78,7 +81,6 @@ __global__ __launch_bounds__(256) void ingest_kernel(const IngestDev p) {
   __syncthreads();
   const int y0 = s_y0, ny = s_y1 - s_y0;
   // ---- stage the source rows: aligned 32-bit words covering bytes [row start, row start + cw * 3)
-  const unsigned char* frame = p.src + (size_t)t * p.H * p.W * 3;
   for (int y = 0; y < ny; ++y) {
     const size_t b0 = ((size_t)(p.y_off + y0 + y) * p.W + p.x_off) * 3;
     const unsigned char* rp = frame + b0;
@@ -115,7 +117,6 @@ __global__ __launch_bounds__(256) void ingest_kernel(const IngestDev p) {
   }
   __syncthreads();
   // ---- vertical pass -> planar output [t][c][r][x]
-  TO* out = (TO*)p.dst + (size_t)t * 3 * p.R * p.R;
   for (int i = tid; i < (r1 - r0) * p.R * 3; i += 256) {
     const int x = i % p.R, r = (i / p.R) % (r1 - r0), c = i / (p.R * (r1 - r0));
     const float* w = wy + (size_t)r * ING_MAXT;
@@ -125,16 +126,60 @@ __global__ __launch_bounds__(256) void ingest_kernel(const IngestDev p) {
       acc = hbuf[((size_t)ym * p.R + x) * 3 + c] * w[0];
       for (int j = 1; j < n; ++j) acc += hbuf[((size_t)(ym + j) * p.R + x) * 3 + c] * w[j];
     }
-    out[((size_t)c * p.R + (r0 + r)) * p.R + x] = from_f32<TO>(acc);
+    const TO v = from_f32<TO>(acc);
+    TO* o = out + ((size_t)c * p.R + (r0 + r)) * p.R + x;
+    for (int k = 0; k < copies; ++k) o[(size_t)k * 3 * p.R * p.R] = v;
   }
 }
 
+template <typename TO>
+__global__ __launch_bounds__(256) void ingest_kernel(const IngestDev p) {
+  const int t = blockIdx.x / p.blocks_per_frame, blk = blockIdx.x % p.blocks_per_frame;
+  ingest_block<TO>(p, p.src + (size_t)t * p.H * p.W * 3, (TO*)p.dst + (size_t)t * 3 * p.R * p.R, blk, 1);
+}
+
+// ---- the batched form: B clips of one staging buffer, each with its own frame count and frame size, in one launch.  The clip
+// table travels in the kernel arguments (as KvMoves does for kv_select): no device table to fill, no host synchronisation.
+constexpr int ING_MAX_CLIPS = 64;   // per launch; 40 B each, well inside the 4 KiB of kernel arguments
+struct IngestClip {
+  long long offset;            // bytes from the staging buffer to the clip's first stored frame
+  int frames, H, W;            // stored frames and their size
+  int x_off, y_off;            // crop window origin (its side follows from H, W and the crop flag)
+  int rows_per_wg, in_rows_cap;
+};
+struct IngestBatch {
+  const unsigned char* src; void* dst;
+  size_t total_bytes;          // of the staging buffer
+  int T, R, crop;
+  IngestClip clip[ING_MAX_CLIPS];
+};
+
+// grid (most blocks any clip needs per frame, T, clips).  Output frame t of clip b is stored frame min(t, frames - 1): the block of
+// the last stored frame writes every output frame from there on, so a short clip's source bytes are still read once.
+template <typename TO>
+__global__ __launch_bounds__(256) void ingest_clips_kernel(const IngestBatch q) {
+  const IngestClip& c = q.clip[blockIdx.z];
+  const int t = blockIdx.y, blk = blockIdx.x;
+  if (t >= c.frames || blk * c.rows_per_wg >= q.R) return;   // whole workgroups leave, before any barrier
+  IngestDev p;
+  p.src = q.src; p.total_bytes = q.total_bytes;   // (the block body takes its frame and its output from its arguments)
+  p.H = c.H; p.W = c.W; p.R = q.R;
+  const int s = c.H < c.W ? c.H : c.W;
+  p.x_off = c.x_off; p.y_off = c.y_off; p.cw = q.crop ? s : c.W; p.ch = q.crop ? s : c.H;
+  p.rows_per_wg = c.rows_per_wg; p.in_rows_cap = c.in_rows_cap; p.blocks_per_frame = (q.R + c.rows_per_wg - 1) / c.rows_per_wg;
+  p.pitch = ((p.cw * 3 + 3 + 3) / 4) * 4 + 4;
+  const int copies = t == c.frames - 1 ? q.T - t : 1;
+  ingest_block<TO>(p, q.src + c.offset + (size_t)t * c.H * c.W * 3, (TO*)q.dst + ((size_t)blockIdx.z * q.T + t) * 3 * q.R * q.R, blk, copies);
+}
+
+constexpr int kMaxDyn = 160 * 1024 - 64;   // (the kernels also have 8 bytes of static LDS: the dynamic part may take 160 KiB minus that)
+
 // crop: 0 = none (aspect ratio squashed, inference/utils.py:12-16), 1 = centre crop to the short side first
 // (simple_dataloader.py:512-516 for tfds_robonet; torchvision center_crop: top = round((H - s) / 2), left likewise)
-int launch_ingest(const unsigned char* src, int T, int H, int W, int crop, void* dst, DType dst_dt, int R, hipStream_t st) {
-  if (T <= 0 || H <= 0 || W <= 0 || R <= 0 || R > 1024) return (int)hipErrorInvalidValue;
-  IngestDev d;
-  d.src = src; d.dst = dst; d.T = T; d.H = H; d.W = W; d.R = R;
+// -> the geometry of one H x W frame in d and the dynamic LDS a workgroup needs; hipErrorInvalidValue for what the kernel cannot do
+static int plan_ingest(int H, int W, int crop, int R, IngestDev& d, size_t& smem) {
+  if (H <= 0 || W <= 0 || R <= 0 || R > 1024) return (int)hipErrorInvalidValue;
+  d.H = H; d.W = W; d.R = R;
   d.x_off = 0; d.y_off = 0; d.cw = W; d.ch = H;
   if (crop) {
     const int s = H < W ? H : W;
@@ -154,12 +199,18 @@ int launch_ingest(const unsigned char* src, int T, int H, int W, int crop, void*
   };
   int cap = 0;
   while (rows > 1 && smem_for(rows, cap) > 96 * 1024) rows >>= 1;
-  const size_t smem = smem_for(rows, cap);
+  smem = smem_for(rows, cap);
   d.rows_per_wg = rows; d.in_rows_cap = cap; d.blocks_per_frame = cdiv(R, rows);
+  return smem > (size_t)kMaxDyn ? (int)hipErrorInvalidValue : 0;
+}
+
+int launch_ingest(const unsigned char* src, int T, int H, int W, int crop, void* dst, DType dst_dt, int R, hipStream_t st) {
+  if (T <= 0) return (int)hipErrorInvalidValue;
+  IngestDev d;
+  size_t smem = 0;
+  if (int rc = plan_ingest(H, W, crop, R, d, smem)) return rc;
+  d.src = src; d.dst = dst; d.T = T;
   d.total_bytes = (size_t)T * H * W * 3;
-  // (the kernel also has 8 bytes of static LDS: the dynamic part may take 160 KiB minus that)
-  constexpr int kMaxDyn = 160 * 1024 - 64;
-  if (smem > (size_t)kMaxDyn) return (int)hipErrorInvalidValue;
   static DynLdsOnce once_f, once_b;
   if (dst_dt == BF16) {
     if (hipError_t e = ensure_dyn_lds(once_b, (const void*)ingest_kernel<bf16_t>, kMaxDyn); e != hipSuccess) return (int)e;
@@ -169,6 +220,50 @@ int launch_ingest(const unsigned char* src, int T, int H, int W, int crop, void*
     hipLaunchKernelGGL(ingest_kernel<float>, dim3((unsigned)(T * d.blocks_per_frame)), dim3(256), smem, st, d);
   }
   return (int)hipGetLastError();
+}
+
+int launch_ingest_clips(const unsigned char* src, size_t total_bytes, const IngestClipDesc* clips, int B, int T, int crop, void* dst, DType dst_dt,
+                        int R, hipStream_t st) {
+  if (B <= 0 || T <= 0 || T > 65535) return (int)hipErrorInvalidValue;   // (T is the grid's y extent)
+  // every clip is checked before the first launch: a refused batch writes nothing
+  for (int b = 0; b < B; ++b) {
+    const IngestClipDesc& c = clips[b];
+    IngestDev d;
+    size_t smem = 0;
+    if (c.frames < 1 || c.offset < 0 || (c.offset & 15) || (size_t)c.offset > total_bytes) return (int)hipErrorInvalidValue;
+    if (int rc = plan_ingest(c.H, c.W, crop, R, d, smem)) return rc;
+    const unsigned long long frame_bytes = (unsigned long long)c.H * c.W * 3;
+    if (frame_bytes > (total_bytes - (size_t)c.offset) / (unsigned)c.frames) return (int)hipErrorInvalidValue;
+  }
+  const size_t esz = dst_dt == BF16 ? 2 : 4;
+  static DynLdsOnce once_f, once_b;
+  for (int b0 = 0; b0 < B; b0 += ING_MAX_CLIPS) {   // one launch up to ING_MAX_CLIPS clips
+    IngestBatch q;
+    const int n = B - b0 < ING_MAX_CLIPS ? B - b0 : ING_MAX_CLIPS;
+    q.src = src; q.dst = (char*)dst + (size_t)b0 * T * 3 * R * R * esz; q.total_bytes = total_bytes; q.T = T; q.R = R; q.crop = crop ? 1 : 0;
+    size_t smem = 0;
+    int blocks = 0;
+    for (int i = 0; i < n; ++i) {
+      const IngestClipDesc& c = clips[b0 + i];
+      IngestDev d;
+      size_t need = 0;
+      plan_ingest(c.H, c.W, crop, R, d, need);
+      q.clip[i] = IngestClip{c.offset, c.frames, c.H, c.W, d.x_off, d.y_off, d.rows_per_wg, d.in_rows_cap};
+      if (need > smem) smem = need;                 // LDS is sized for the largest clip
+      if (d.blocks_per_frame > blocks) blocks = d.blocks_per_frame;
+    }
+    for (int i = n; i < ING_MAX_CLIPS; ++i) q.clip[i] = IngestClip{0, 0, 1, 1, 0, 0, 1, 1};
+    const dim3 grid((unsigned)blocks, (unsigned)T, (unsigned)n);
+    if (dst_dt == BF16) {
+      if (hipError_t e = ensure_dyn_lds(once_b, (const void*)ingest_clips_kernel<bf16_t>, kMaxDyn); e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(ingest_clips_kernel<bf16_t>, grid, dim3(256), smem, st, q);
+    } else {
+      if (hipError_t e = ensure_dyn_lds(once_f, (const void*)ingest_clips_kernel<float>, kMaxDyn); e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(ingest_clips_kernel<float>, grid, dim3(256), smem, st, q);
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
+  }
+  return 0;
 }
 
 }  // namespace ivg

@@ -217,6 +217,12 @@ long long kv_select_rows(int staged);
 // ---- ingest.hip
 // uint8 frames [T][H][W][3] -> planar [T][3][R][R] in [0, 1]: / 255, optional centre crop, antialiased bilinear resize (ATen semantics)
 int launch_ingest(const unsigned char* src, int T, int H, int W, int crop, void* dst, DType dst_dt, int R, hipStream_t st);
+// the batched form (ivg_ingest_clips): B clips inside one buffer of total_bytes, clip b = `frames` stored H x W frames from byte `offset`
+// (a multiple of 16) on -> dst [B][T][3][R][R], output frame t = what launch_ingest writes for stored frame min(t, frames - 1).
+// `clips` is a host array; everything is checked before the first launch (hipErrorInvalidValue), nothing synchronises the host
+struct IngestClipDesc { int64_t offset; int32_t frames, H, W; };   // == ivg_clip_desc
+int launch_ingest_clips(const unsigned char* src, size_t total_bytes, const IngestClipDesc* clips, int B, int T, int crop, void* dst, DType dst_dt,
+                        int R, hipStream_t st);
 
 // ---- metrics.hip
 // per-trajectory (mse, psnr, ssim) of predicted frames, mean over frames, best of the n_samples / B samples per trajectory

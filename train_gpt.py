@@ -15,6 +15,8 @@ Same names, arguments and op sequence as the reference, so the loop reads like t
     (:341-355, :456-470, :495-497); without a detector it raises.  The LPIPS column needs the VGG-16 / LPIPS weights: with
     ``--lpips_vgg_path`` and ``--lpips_lin_path`` (``Evaluator(lpips=...)``) ``eval/lpips`` is computed on the device and
     gathered like the other three, without them it is NaN;
+  * ``--use_eval_dataset`` feeds the loop from ``ivideogpt_amd.data.EvalDataLoader`` (the reference's ``EvalDataLoader`` after
+    ``accelerator.prepare``, train_gpt.py:102-113) instead of synthetic clips;
   * GIF dumps (``imageio``) are not written; the ``eval/mse`` fallback of that branch is kept (:447-449).
 The only collectives are the all-gathers of per-sample loss / metric rows (train_gpt.py:376, 476-479).
 """
@@ -189,9 +191,40 @@ def eval_args(**overrides):
     return argparse.Namespace(**d)
 
 
+def build_eval_model(a, vocab, dev):
+    """The transformer of a ``--use_eval_dataset`` run, built as inference/predict.py builds it (reference train_gpt.py:597-616): the
+    checkpoint of ``--pretrained_transformer_path`` (a directory with config.json + model.safetensors), else ``transformer/`` under
+    ``--pretrained_model_name_or_path``, else seeded random weights; with ``--action_conditioned`` a ``HeadModelWithAction`` with the
+    reference's prelude ((256 + 1) * context - 1) and token counts (16 per predicted frame)."""
+    from ivideogpt_amd import HeadModelWithAction, LlamaForCausalLM, weights as W
+    if a.pretrained_transformer_path:
+        cfg, state = W.load_transformer_checkpoint(a.pretrained_transformer_path, None)
+    elif a.pretrained_model_name_or_path:
+        cfg, state = W.load_transformer_checkpoint(a.pretrained_model_name_or_path, "transformer")
+    else:
+        cfg, state = dict(W.LLAMA_SMALL), None
+    assert cfg["vocab_size"] == vocab, f"the transformer's vocabulary ({cfg['vocab_size']}) is not the tokenizer's ({vocab})"   # predict.py:113
+    if not a.action_conditioned:
+        if state is None:
+            state = W.random_llama_state_dict(cfg, 0)
+        W.validate_state_dict(state, W.llama_param_shapes(cfg), "transformer")
+        return LlamaForCausalLM(cfg, state).to(dev)
+    if state is None:
+        state = W.random_llama_state_dict(cfg, 0, action_dim=a.action_dim, reward_prediction=a.reward_prediction)
+    model = HeadModelWithAction(LlamaForCausalLM.from_config(cfg), action_dim=a.action_dim, prelude_tokens_num=(256 + 1) * a.context_length - 1,
+                                tokens_num_per_dyna=16, context=a.context_length, segment_length=a.segment_length,
+                                reward_prediction=a.reward_prediction).to(dev)
+    model.load_state_dict(state, strict=True)
+    return model
+
+
 def main(argv=None):
-    """``python train_gpt.py --eval_only``-style entry on synthetic clips and seeded random weights (no dataset / checkpoint ships):
-    every rank evaluates its shard of the batches; rank 0 prints the logs."""
+    """``python train_gpt.py --eval_only``-style entry; every rank evaluates its shard of the batches, rank 0 prints the logs as one
+    JSON line.  Default: synthetic clips and seeded random weights.  ``--use_eval_dataset``: the test set of ``--dataset_name`` (a
+    directory of per-episode ``.npz`` files, ``--dataset_root`` or the entry of ``--dataset_yaml``) through
+    ``ivideogpt_amd.data.EvalDataLoader(device='cuda')``, the reference's flag names (train_gpt.py:198-318); the line then also
+    carries ``eval/samples`` (rows that entered the means, over all ranks, wrapped duplicates included) and ``eval/batches``
+    (iterations per rank)."""
     import json
     from ivideogpt_amd import CompressiveVQModel, LlamaForCausalLM, parallel, weights as W
     from ivideogpt_amd.metrics import Evaluator
@@ -211,26 +244,62 @@ def main(argv=None):
     ap.add_argument("--i3d_random", type=int, default=None, metavar="SEED", help="seeded random I3D weights (synthetic runs)")
     ap.add_argument("--i3d_width_div", type=int, default=1, help="with --i3d_random: divide every width of the detector (quick runs)")
     ap.add_argument("--i3d_resize", type=int, default=224, help="side the detector resizes frames to (a multiple of 32)")
+    ap.add_argument("--use_eval_dataset", action="store_true", help="evaluate on the test episodes of --dataset_name instead of synthetic clips")
+    ap.add_argument("--dataset_name", default=None, help="bair_robot_pushing, tfds_robonet, vp2_robodesk, vp2_robosuite (any known name with --dataset_root)")
+    ap.add_argument("--dataset_root", default=None, help="directory of the test episodes (*.npz); default: the entry of --dataset_yaml")
+    ap.add_argument("--dataset_yaml", default="DATASET.yaml", help="the reference's DATASET.yaml (bair_test_dataset, robonet_test_dataset, ...)")
+    ap.add_argument("--resolution", type=int, default=None, help="frame side; default (and only accepted value): the tokenizer's")
+    ap.add_argument("--per_device_eval_batch_size", type=int, default=None, help="default: --batch")
+    ap.add_argument("--dataloader_num_workers", type=int, default=4, help="reader threads of the loader (at most 16)")
+    ap.add_argument("--max_eval_iters", type=int, default=100)
+    ap.add_argument("--action_conditioned", action="store_true", help="HeadModelWithAction checkpoint + the episodes' actions")
+    ap.add_argument("--action_dim", type=int, default=4)
+    ap.add_argument("--reward_prediction", action="store_true")
+    ap.add_argument("--use_frame_metrics", action="store_true", help="with --use_eval_dataset: log mse / psnr / ssim / lpips (the synthetic run always does)")
+    ap.add_argument("--pretrained_transformer_path", default=None, help="directory of the transformer checkpoint (config.json + model.safetensors)")
+    ap.add_argument("--seed", type=int, default=None, help="seeds python / numpy / torch (+ rank, as accelerate's device_specific set_seed)")
     a = ap.parse_args(argv)
+    if bool(a.lpips_vgg_path) != bool(a.lpips_lin_path):
+        ap.error("--lpips_vgg_path and --lpips_lin_path go together")
+    if a.use_eval_dataset and not a.dataset_name:
+        ap.error("--use_eval_dataset needs --dataset_name")
+    if a.use_eval_dataset and not a.use_frame_metrics and not a.use_fvd and a.eval_generate_times != 1:
+        ap.error("without --use_frame_metrics the loop compares one sample per trajectory (its eval/mse fallback): --eval_generate_times 1")
     rank, world, local = parallel.init_from_env()
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
+    if a.seed is not None:
+        import random
+        import numpy as np
+        for seeder in (random.seed, np.random.seed, torch.manual_seed, torch.cuda.manual_seed_all):
+            seeder(a.seed + rank)
     if a.pretrained_model_name_or_path:
         tok = CompressiveVQModel.from_pretrained(a.pretrained_model_name_or_path, subfolder="tokenizer").to(dev)
-        llm = LlamaForCausalLM.from_pretrained(a.pretrained_model_name_or_path, subfolder="transformer").to(dev)
     else:
         tcfg = W.tokenizer_config(**W.CTX_VAE64)
         tok = CompressiveVQModel(tcfg, W.random_tokenizer_state_dict(tcfg, 0, codebook_std=0.4)).to(dev)
-        llm = LlamaForCausalLM(dict(W.LLAMA_SMALL), W.random_llama_state_dict(dict(W.LLAMA_SMALL), 0)).to(dev)
     if a.context_length != tok.context_length:
         tok.set_context_length(a.context_length)
     res = tok.config["resolution"]
-    g = torch.Generator().manual_seed(1234)
-    batches = [torch.rand(a.batch, a.segment_length, 3, res, res, generator=g) for _ in range(a.iters * world)][rank::world]
     args = eval_args(context_length=a.context_length, segment_length=a.segment_length, eval_generate_times=a.eval_generate_times,
                      max_generate_batchsize=a.max_generate_batchsize, max_decode_batchsize=a.max_decode_batchsize, use_fvd=a.use_fvd)
-    if bool(a.lpips_vgg_path) != bool(a.lpips_lin_path):
-        ap.error("--lpips_vgg_path and --lpips_lin_path go together")
+    if a.use_eval_dataset:
+        from ivideogpt_amd.data import EvalDataLoader
+        if a.resolution not in (None, res):
+            ap.error(f"--resolution {a.resolution}: the tokenizer works at {res}")
+        llm = build_eval_model(a, tok.num_vq_embeddings + tok.num_dyn_embeddings + 2, dev)
+        batches = EvalDataLoader(a.dataset_name, a.segment_length, res, batch_size=a.per_device_eval_batch_size or a.batch,
+                                 num_workers=a.dataloader_num_workers, load_action=a.action_conditioned, device=dev, rank=rank, world=world,
+                                 root=a.dataset_root, dataset_yaml=a.dataset_yaml)
+        vars(args).update(action_conditioned=a.action_conditioned, reward_prediction=a.reward_prediction, use_frame_metrics=a.use_frame_metrics,
+                          max_eval_iters=a.max_eval_iters)
+    else:
+        if a.pretrained_model_name_or_path:
+            llm = LlamaForCausalLM.from_pretrained(a.pretrained_model_name_or_path, subfolder="transformer").to(dev)
+        else:
+            llm = LlamaForCausalLM(dict(W.LLAMA_SMALL), W.random_llama_state_dict(dict(W.LLAMA_SMALL), 0)).to(dev)
+        g = torch.Generator().manual_seed(1234)
+        batches = [torch.rand(a.batch, a.segment_length, 3, res, res, generator=g) for _ in range(a.iters * world)][rank::world]
     i3d = a.i3d_path
     if a.i3d_random is not None:
         from ivideogpt_amd.i3d import I3D
@@ -241,6 +310,10 @@ def main(argv=None):
     evaluator = Evaluator(lpips=(a.lpips_vgg_path, a.lpips_lin_path) if a.lpips_vgg_path else None, i3d=i3d)
     logs = evaluate(args, parallel.LocalAccelerator(dev), tok, llm, batches, evaluator, 0)
     if logs is not None:
+        if a.use_eval_dataset:
+            seen = batches.batches[:a.max_eval_iters] if a.max_eval_iters >= 0 else batches.batches
+            logs["eval/samples"] = sum(len(b) for b in seen) * world     # with more than one rank every batch is full (data.shard_batches)
+            logs["eval/batches"] = len(seen)
         print(json.dumps(logs))
     return logs
 
